@@ -24,9 +24,13 @@ weak scaling; M: the global grid is fixed -> strong scaling).  Stage 1 is sharde
 all-reduce(MAX) of packed (score, index) keys per step (`--exchange scores`: the north-star-literal all-reduce(SUM) of
 zero-initialised full score vectors).
 
-Timing: W untimed warm-up steps and a clock warm-up, then FIVE timed batches, each bracketed by barrier + synchronize and
-each made of a whole number of repetitions of the K steps so that it lasts >= 0.2 s; per batch the MAX over ranks, and the
-MEDIAN batch is reported.
+Timing: W untimed warm-up steps and a clock warm-up, then exactly K timed steps, dealt over `--batches` batches (default
+one), each bracketed by barrier + synchronize; per batch the MAX over ranks, and the MEDIAN batch is reported.
+A timed batch shorter than --min-batch-s (0.2 s) is reported on stderr: raise --steps for a steady-state number.
+
+--dump-outputs DIR: after the timed steps, what the headline's last timed step computed -- the per-window results, the
+stage-1 banks and both score manifolds at a fixed, seeded sample of points plus every window's two arg-max points -- as DIR/<name>.npy (float32 / float64, one rank only).
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -136,11 +140,11 @@ def cpu_baseline(cfg, budget_s=10.0, mp_budget_s=8.0, all_cores=True, windows=No
     return out
 
 
-def acq_line(modes=("coherent", "textbook", "noncoherent"), cpu_budget_s=5.0):
+def acq_line(steps, modes=("coherent", "textbook", "noncoherent"), cpu_budget_s=5.0):
     """Cold-start acquisition (BASELINE.json configs[4]) as a measured line: 32 PRNs x 125 Doppler bins x all
     2500 code delays of a 10 ms / 2.5 Msps window, the whole search (wipe-off + fold, forward rocFFT, spectrum product + inverse
     transforms + |.| surface + per-delay maximum -- one fused kernel in the coherent mode --, peak statistics) timed between HIP
-    events on its stream.
+    events on its stream, `steps` searches per mode.
     `value` = search cells (PRN x bin x delay) per second of the reference's coherent semantics (fixture O8); `modes` holds the
     textbook "1 ms coherent x 10 non-coherent" form too (BASELINE's wording; not a reference algorithm) and the reference's
     non-coherent mode (coherent = False: one 25 000-point correlation per bin, |.| over the ten lag aliases) -- on the same 125-bin
@@ -167,12 +171,11 @@ def acq_line(modes=("coherent", "textbook", "noncoherent"), cpu_budget_s=5.0):
             acq.search(d)
         torch.cuda.synchronize()
         t = dpe.engine.HipEventTimer()
-        n = 50
         t.start()
-        for _ in range(n):
+        for _ in range(steps):
             acq.search(d)
         t.stop()
-        ms = t.elapsed_ms() / n
+        ms = t.elapsed_ms() / steps
         res = acq.results()
         acq.search_signal(d)                        # (the first call plans the fine-frequency transform)
         t0 = time.perf_counter()
@@ -192,10 +195,10 @@ def acq_line(modes=("coherent", "textbook", "noncoherent"), cpu_budget_s=5.0):
             torch.cuda.synchronize()
             t = dpe.engine.HipEventTimer()
             t.start()
-            for _ in range(n):
+            for _ in range(steps):
                 acq.search(d)
             t.stop()
-            ms25 = t.elapsed_ms() / n
+            ms25 = t.elapsed_ms() / steps
             per_mode["noncoherent_25x500Hz"] = {"ms_per_window": ms25, "cells_per_s": len(prns) * b25.size * M / (ms25 * 1e-3)}
             del acq
     ms0 = per_mode[modes[0]]["ms_per_window"]
@@ -240,10 +243,10 @@ def acq_line(modes=("coherent", "textbook", "noncoherent"), cpu_budget_s=5.0):
     return out
 
 
-def acq_main(mode):
+def acq_main(mode, steps):
     """`bench.py --acq MODE`: the acquisition line alone, for the chosen mode first."""
     modes = (mode,) + tuple(m for m in ("coherent", "textbook", "noncoherent") if m != mode)
-    print(json.dumps(acq_line(modes=modes, cpu_budget_s=8.0)))
+    print(json.dumps(acq_line(steps, modes=modes, cpu_budget_s=8.0)))
 
 
 class Ctx:
@@ -268,9 +271,58 @@ def device_view(ptr, shape, typestr, dev):
     return torch.as_tensor(_Cai(), device=dev)
 
 
-def run_workload(name, ctx, args, steps, warmup, headline, cached=None):
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SCORE_SAMPLES = 1 << 21       # (window, grid point) pairs of each score manifold; all of them when there are fewer
+
+
+def dump_outputs(out_dir, res, bcs, bcm, dev):
+    """--dump-outputs: one batch's outputs as out_dir/<name>.npy -- the per-window results, the banks (float2 as a trailing
+    axis of 2) and, when the scores are written (`bcm` not None), both manifolds at the same (window, point) pairs -- a seeded
+    sample together with every window's position and velocity arg-max, so that the sample meets the results exactly -- whose
+    flat indices window * G + point go beside them.  Integers travel as float64 (exact below 2^53)."""
+    import torch
+    arrays = {
+        "pos_index": np.array([r["posIndex"] for r in res], dtype=np.float64),
+        "vel_index": np.array([r["velIndex"] for r in res], dtype=np.float64),
+        "pos_score": np.array([r["posScore"] for r in res], dtype=np.float32),
+        "vel_score": np.array([r["velScore"] for r in res], dtype=np.float32),
+        "pos_out_of_window": np.array([r["posOutOfWindow"] for r in res], dtype=np.float64),
+        "vel_out_of_window": np.array([r["velOutOfWindow"] for r in res], dtype=np.float64),
+        "z_val": np.stack([r["zVal"] for r in res]).astype(np.float64),
+        "z_val_mean": np.stack([r["zValMean"] for r in res]).astype(np.float64),
+        "weighted_sums": np.stack([r["weightedSums"] for r in res]).astype(np.float64),
+    }
+    code, carr = bcs.read_banks()
+    arrays["code_scores"] = code.view(np.float32).reshape(code.shape + (2,))
+    arrays["carr_scores"] = carr.view(np.float32).reshape(carr.shape + (2,))
+    if bcm is not None:
+        W, G = len(res), bcm.pos_grid.shape[0]
+        assert bcm.vel_grid.shape[0] == G
+        if W * G <= DUMP_SCORE_SAMPLES:
+            idx = np.arange(W * G, dtype=np.int64)
+        else:
+            w = np.arange(W, dtype=np.int64)
+            best = np.concatenate([w * G + np.array([r["posIndex"] for r in res], dtype=np.int64) - bcm.pos_off,
+                                   w * G + np.array([r["velIndex"] for r in res], dtype=np.int64) - bcm.vel_off])
+            assert best.min() >= 0 and best.max() < W * G
+            idx = np.unique(np.concatenate([np.random.default_rng(0).integers(0, W * G, DUMP_SCORE_SAMPLES), best]))
+        rows, cols = torch.from_numpy(idx // G).to(dev), torch.from_numpy(idx % G).to(dev)
+        for name, ptr, pitch in (("pos_scores_sample", bcm.PosScores, bcm.PosScoresPitch),
+                                 ("vel_scores_sample", bcm.VelScores, bcm.VelScoresPitch)):
+            arrays[name] = device_view(ptr, (W, pitch), "<f4", dev)[rows, cols].cpu().numpy()
+        arrays["scores_sample_index"] = idx.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes of outputs, more than %d (fewer --windows)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def run_workload(name, ctx, args, steps, warmup, headline, cached=None, dump_dir=None):
     """Times one configuration; rank 0 returns the result dict (None elsewhere).  `cached`: windows built for another
-    configuration of the same sampling shape (R and M share theirs)."""
+    configuration of the same sampling shape (R and M share theirs).  `dump_dir`: write the last timed step's outputs there
+    (one rank only)."""
     import torch
     import navlab_dpe_sdr_amd as dpe
     dist, dev, world, rank = ctx.dist, ctx.dev, ctx.world, ctx.rank
@@ -404,28 +456,37 @@ def run_workload(name, ctx, args, steps, warmup, headline, cached=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    def timed(n_batches, n_steps):
+    shortest = [math.inf]     # seconds of the shortest timed batch
+
+    def timed():
+        """the `steps` timed steps, dealt over --batches batches -> ms per step of each batch"""
         out_ms = []
-        for _ in range(n_batches):
+        for i in range(args.batches):
+            n = steps // args.batches + (i < steps % args.batches)
             fence()
             t0 = time.perf_counter()
-            for _ in range(n_steps):
+            for _ in range(n):
                 step()
             fence()
-            out_ms.append(max_over_ranks(time.perf_counter() - t0) / n_steps * 1e3)
+            dt = max_over_ranks(time.perf_counter() - t0)
+            shortest[0] = min(shortest[0], dt)
+            out_ms.append(dt / n * 1e3)
         return out_ms
+
+    def clock_warmup():
+        """Untimed: a GPU that idled at its lowest sclk takes on the order of a second of load to settle at its sustained
+        clock.  The metric is steady-state throughput, so the settle time stays outside the timed region."""
+        t_w = time.perf_counter()
+        while max_over_ranks(time.perf_counter() - t_w) < args.clock_warmup_s:
+            for _ in range(8):
+                step()
+            fence()
 
     pipe.set_in_flight(1)
     for _ in range(warmup):
         step()
     fence()
-    # Clock warm-up, untimed: a GPU that idled at its lowest sclk takes on the order of a second of load to settle at its
-    # sustained clock.  The metric is steady-state throughput, so the settle time stays outside the timed region.
-    t_w = time.perf_counter()
-    while max_over_ranks(time.perf_counter() - t_w) < args.clock_warmup_s:
-        for _ in range(8):
-            step()
-        fence()
+    clock_warmup()
     # Untimed side pass: HIP events around every kernel (`kernels_ms_per_step`), which also names the time-dominant kernel.
     bcs.profile(True); bcm.profile(True)
     n_side = 12
@@ -436,15 +497,13 @@ def run_workload(name, ctx, args, steps, warmup, headline, cached=None):
     side.update(bcm.profile(False))
     kernels_ms = {k: v[0] / max(v[1], 1) * (v[1] / n_side) for k, v in side.items()}   # per step (side chunks of a wide lag window add up)
     dominant = max(kernels_ms, key=kernels_ms.get)
-    est = timed(1, steps)[0] * 1e-3
-    reps = max(1, int(math.ceil(args.min_batch_s / max(est * steps, 1e-9))))
     # One stream (one lane): the isolated dominant kernel between HIP events for the `roofline` stanza (a pair of events around
     # every kernel costs ~2 % of a step, so only the dominant one carries them), and `one_stream_ms_per_step`.
     if dominant == "bcm_scan":
         bcm.profile(True)
     else:
         bcs.profile(dominant)
-    one_ms = timed(args.batches if n_lanes == 1 else 3, reps * steps)
+    one_ms = timed()
     kern = dict(bcm.profile(False)) if dominant == "bcm_scan" else dict(bcs.profile(False))
     one_stream_ms = float(np.median(one_ms))
     # The timed region proper: `--in-flight` lanes
@@ -452,10 +511,16 @@ def run_workload(name, ctx, args, steps, warmup, headline, cached=None):
         pipe.set_in_flight(n_lanes)
         for _ in range(2 * n_lanes):
             step()
-        batch_ms = timed(args.batches, reps * steps)
+        # the lanes in flight settle too: the first steps after the switch from one lane were observed to run slow (R: a
+        # 20-step timed region started right after the switch, up to 15 % below one started after this warm-up)
+        clock_warmup()
+        batch_ms = timed()
     else:
         batch_ms = one_ms
     ms_step = float(np.median(batch_ms))
+    if rank == 0 and shortest[0] < args.min_batch_s:
+        sys.stderr.write("bench.py: %s: a timed batch lasted %.3f s, less than --min-batch-s %g; raise --steps for a steady-state "
+                         "number\n" % (name, shortest[0], args.min_batch_s))
     # Stage-1 device status after the timed region: batches of the high-rate chip kernel compute their DC sums inside the stage-1
     # launch, and a correlator block that had to wait too long for them sums its window itself (right, but slower) -- bits 2 / 16
     # say that it happened; a timed region in which it did is not the steady state this line claims.
@@ -501,6 +566,9 @@ def run_workload(name, ctx, args, steps, warmup, headline, cached=None):
     fixes = [[int(r["posIndex"]), int(r["velIndex"]), float(r["posScore"]), float(r["velScore"])] for r in res[:16]]
     if world == 1:
         assert all(r["posOutOfWindow"] == 0 and r["velOutOfWindow"] == 0 for r in res), "bank window too narrow"
+    if dump_dir is not None:
+        b_, m_, _ = pipe.lane(t_last)
+        dump_outputs(dump_dir, res, b_, m_ if write_scores else None, dev)
 
     pcie_value = pcie_overlapped = None
     if args.include_h2d and headline and not ctx.use_dist:
@@ -575,7 +643,7 @@ def run_workload(name, ctx, args, steps, warmup, headline, cached=None):
                                                     "(profiles/archive/r3a_H_w64|w128|w256_bench.json)"} if name == "H" and W == 128 else {})},
             "one_stream_ms_per_step": one_stream_ms,
             "one_stream_value": units_per_step / (one_stream_ms * 1e-3),
-            "timing": {"timed_batches": args.batches, "steps_per_timed_batch": reps * steps, "batch_ms_per_step": batch_ms,
+            "timing": {"timed_steps": steps, "timed_batches": args.batches, "batch_ms_per_step": batch_ms,
                        "one_stream_batch_ms_per_step": one_ms,
                        "statistic": "median of the batches, each the max over ranks"},
             "x_realtime": windows_per_s / 50.0, "windows_per_s": windows_per_s,
@@ -648,7 +716,8 @@ def spawn_ranks(args, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=1000,
+                    help="timed steps of each line (R: about 0.7 s at the default)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--windows", type=int, default=None, help="windows per step (batch resident in HBM); default 256 (R, M) / 128 (H)")
     ap.add_argument("--config", choices=["R", "H", "M"], default=None,
@@ -670,8 +739,11 @@ def main():
                     help="time the cold-start acquisition search instead (8f row 4; separate JSON line, not the headline)")
     ap.add_argument("--clock-warmup-s", type=float, default=1.0,
                     help="seconds of untimed steps after --warmup, before the timed region (GPU clock settle)")
-    ap.add_argument("--batches", type=int, default=5, help="timed batches (the median is reported)")
-    ap.add_argument("--min-batch-s", type=float, default=0.2, help="each timed batch repeats the --steps steps until it lasts this long")
+    ap.add_argument("--batches", type=int, default=1,
+                    help="timed batches the --steps steps are dealt over, each between two synchronisations (the median is reported)")
+    ap.add_argument("--min-batch-s", type=float, default=0.2,
+                    help="warn when a timed batch lasts less than this: a short one measures launch overhead and clocks as much as the "
+                         "kernels (0: no warning)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=10.0,
                     help="seconds of one-thread oracle time behind the headline's cpu_baseline (H / M: 0.4 / 0.5 of it, at least one "
@@ -684,11 +756,17 @@ def main():
     ap.add_argument("--include-h2d", action="store_true",
                     help="also time the steps with the window batch uploaded from pinned host memory inside the timed "
                          "region (reported as pcie_inclusive_value; never the headline value)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step computed to DIR/<name>.npy (one rank only)")
     args = ap.parse_args()
     if args.no_pipelined:
         args.in_flight = 1
+    if not 1 <= args.batches <= args.steps:
+        ap.error("--batches must be between 1 and --steps")
+    if args.dump_outputs and (args.acq or args.gpus > 1 or os.environ.get("DPE_BENCH_FORCE_DIST") == "1"):
+        ap.error("--dump-outputs writes the one-rank hot path's outputs: not with --acq, --gpus > 1 or DPE_BENCH_FORCE_DIST")
     if args.acq:
-        return acq_main(args.acq)
+        return acq_main(args.acq, args.steps)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args, sys.argv[1:])          # does not return
 
@@ -747,27 +825,26 @@ def main():
     want_cpu = ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline
     others = {}
     if args.config is None and not args.no_extras:
-        extra_steps = min(args.steps, 20)
         if ctx.world == 1 and not ctx.use_dist:
             try:
-                out = acq_line()                  # BASELINE.json configs[4]
+                out = acq_line(args.steps)        # BASELINE.json configs[4]
                 emit(out)
                 others["acq"] = brief(out)
             except Exception as e:                # (an extra line must never cost the headline)
                 sys.stderr.write("bench.py: acquisition line failed: %r\n" % (e,))
-            out, hc = run_workload("H", ctx, args, extra_steps, min(args.warmup, 2), headline=False)
+            out, hc = run_workload("H", ctx, args, args.steps, min(args.warmup, 2), headline=False)
             if want_cpu:      # the CPU restatement beside every configuration; one thread, one whole window at H
                 out["cpu_baseline"] = cpu_baseline(configs["H"], budget_s=0.4 * args.cpu_budget_s, all_cores=False, windows=hc["data"])
             emit(out)
             others["H"] = brief(out)
             del hc
-        out, cached = run_workload("M", ctx, args, extra_steps, min(args.warmup, 2), headline=False)
+        out, cached = run_workload("M", ctx, args, args.steps, min(args.warmup, 2), headline=False)
         if want_cpu:
             out["cpu_baseline"] = cpu_baseline(configs["M"], budget_s=0.5 * args.cpu_budget_s, all_cores=False, windows=cached["data"])
         emit(out)
         if ctx.rank == 0:
             others["M"] = brief(out)
-    out, _ = run_workload(headline, ctx, args, args.steps, args.warmup, headline=True, cached=cached)
+    out, _ = run_workload(headline, ctx, args, args.steps, args.warmup, headline=True, cached=cached, dump_dir=args.dump_outputs)
     if want_cpu:
         cfg = configs[headline]
         out["cpu_baseline"] = cpu_baseline(dict(cfg, G=min(cfg["G"], 390625)), budget_s=args.cpu_budget_s,

@@ -93,3 +93,11 @@ def test_others_stanza_schema():
     assert len(json.dumps({"acq": a, "H": b, "M": b})) < 2500
     assert bench.brief(None) is None
     assert bench.FP32_VECTOR_PEAK_TFLOPS == 157.3 and bench.HBM_PEAK_GBS == 8000.0
+
+
+def test_step_and_dump_arguments_are_checked_before_any_gpu_work():
+    """More batches than timed steps, or --dump-outputs where it has no one-rank hot path to write: status 2, no JSON."""
+    for extra in (["--steps", "2", "--batches", "3"], ["--gpus", "2", "--dump-outputs", "out"], ["--acq", "coherent", "--dump-outputs", "out"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and not r.stdout.strip(), (extra, r.stderr)
+        assert ("--batches" if "--batches" in extra else "--dump-outputs") in r.stderr

@@ -26,18 +26,20 @@ def _launch(port, extra, nproc=2, expect_rc=0, timeout=300):
     return [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
 
 
-def test_eight_ranks_default_invocation_matches_one_rank():
-    """What the driver launches on an 8-GPU node -- the default invocation with --gpus 8 (M strong scaling, then the R headline,
-    weak scaling) -- with all eight ranks on this box's one GPU and gloo carrying the exchange: 8-way partition arithmetic of both
-    grids, stage 1 sharded over 8 ranks (one window each), key all-reduce.  Config M scans the same global grid whatever the rank
-    count, so its decoded fixes must be those of the one-rank run."""
-    lines = _launch(29571, ["--windows", "8", "--extra-windows", "8"], nproc=8, timeout=900)
+def test_four_ranks_default_invocation_matches_one_rank():
+    """The default invocation with --gpus 4 (M strong scaling, then the R headline, weak scaling) with all four ranks on one
+    GPU and gloo carrying the exchange: 4-way partition arithmetic of both grids, stage 1 sharded over 4 ranks (two windows
+    each; then, config M alone, one window each), key all-reduce.  (Four ranks rather than a full node's eight keep the
+    processes that hold the one GPU, this test's own included, within the six a shared GPU host admits;
+    tests/test_bench_cpu.py checks the 8-way partition of the strong-scaling grid.)  Config M scans the same global grid
+    whatever the rank count, so its decoded fixes must be those of the one-rank run."""
+    lines = _launch(29571, ["--windows", "8", "--extra-windows", "8"], nproc=4, timeout=900)
     assert len(lines) == 2, lines
     m, d = lines
-    assert m["n_gpus"] == 8 and m["scaling"] == "strong" and m["config"]["stage1"].startswith("sharded")
-    assert m["config"]["grid_points_per_manifold_global"] == 1000000 and m["config"]["grid_points_per_manifold_per_gpu"] == 125000
-    assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["config"]["stage1"].startswith("sharded")
-    assert d["config"]["grid_points_per_manifold_global"] == 8 * 390625 and d["config"]["grid_points_per_manifold_per_gpu"] == 390625
+    assert m["n_gpus"] == 4 and m["scaling"] == "strong" and m["config"]["stage1"].startswith("sharded")
+    assert m["config"]["grid_points_per_manifold_global"] == 1000000 and m["config"]["grid_points_per_manifold_per_gpu"] == 250000
+    assert d["n_gpus"] == 4 and d["scaling"] == "weak" and d["config"]["stage1"].startswith("sharded")
+    assert d["config"]["grid_points_per_manifold_global"] == 4 * 390625 and d["config"]["grid_points_per_manifold_per_gpu"] == 390625
     assert d["config"]["windows_per_step"] == 8 and d["value"] > 0
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DPE_BENCH_BACKEND")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "M", "--windows", "8"] + FAST
@@ -45,7 +47,7 @@ def test_eight_ranks_default_invocation_matches_one_rank():
     assert r.returncode == 0, r.stderr[-3000:]
     one = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert one["n_gpus"] == 1 and one["config"]["grid_points_per_manifold_per_gpu"] == 1000000
-    # rank 0 of 8 decodes the 1-rank run's ML points.  (Stage 1 runs with another tile partition when a rank holds one window
+    # rank 0 of 4 decodes the 1-rank run's ML points.  (Stage 1 runs with another tile partition when a rank holds two windows
     # instead of eight: banks agree to fp32 rounding, so a window whose two best grid points tie within that rounding may pick
     # the other one -- its score then still agrees.)
     same = 0
@@ -53,6 +55,18 @@ def test_eight_ranks_default_invocation_matches_one_rank():
         assert abs(a[2] - b[2]) <= 2e-6 * abs(b[2]) and abs(a[3] - b[3]) <= 2e-6 * abs(b[3])
         same += (a[0] == b[0]) + (a[1] == b[1])
     assert len(m["fixes"]) == 8 and same >= 14
+    # one window per rank: config M alone over 4 ranks and 4 windows against its one-rank run
+    four = _launch(29573, ["--config", "M", "--windows", "4"], nproc=4)
+    assert len(four) == 1 and four[0]["n_gpus"] == 4 and four[0]["config"]["windows_per_step"] == 4
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "M", "--windows", "4"] + FAST
+    r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    one4 = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    same = 0
+    for a, b in zip(four[0]["fixes"], one4["fixes"]):
+        assert abs(a[2] - b[2]) <= 2e-6 * abs(b[2]) and abs(a[3] - b[3]) <= 2e-6 * abs(b[3])
+        same += (a[0] == b[0]) + (a[1] == b[1])
+    assert len(four[0]["fixes"]) == 4 and same >= 6
 
 
 def test_windows_must_divide_over_the_ranks():
@@ -169,3 +183,41 @@ def test_default_invocation_carries_every_configuration_in_the_last_line():
     assert o["acq"]["cpu_baseline"]["value"] > 0 and 0 < o["acq"]["roofline"]["flop_frac"] < 1
     # the brief copies are the lines' own numbers
     assert o["H"]["ms_per_step"] == lines[1]["ms_per_step"] and o["M"]["value"] == lines[2]["value"] and o["acq"]["value"] == lines[0]["value"]
+
+
+def test_dump_outputs_hold_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: the headline's last timed step as float32 / float64 .npy files, at most 64 MB in all; the dumped
+    arg-max points are the line's `fixes`, the sample holds every window's two arg-max points with exactly the `fixes` scores
+    and no sampled score above them, and the inputs are seeded, so a run with another step count and batching writes the same
+    arrays.  --steps K times exactly K steps over --batches batches."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DPE_BENCH_BACKEND")}
+    dumps = []
+    for steps, batches in ((3, 3), (5, 1)):
+        out = str(tmp_path / ("steps%d" % steps))
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "R", "--windows", "16", "--steps", str(steps),
+               "--warmup", "1", "--clock-warmup-s", "0", "--batches", str(batches), "--no-cpu-baseline", "--dump-outputs", out]
+        r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["timing"]["timed_steps"] == steps and len(d["timing"]["batch_ms_per_step"]) == batches
+        a = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+        assert all(f.endswith(".npy") for f in os.listdir(out))
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20
+        assert a["pos_index"].shape == (16,) and a["z_val"].shape == (16, 8)
+        assert a["code_scores"].shape == (16, 8, 9, 2) and a["carr_scores"].shape == (16, 8, 41, 2)
+        fixes = np.stack([a["pos_index"], a["vel_index"], a["pos_score"], a["vel_score"]], axis=1)
+        assert np.array_equal(fixes, np.array(d["fixes"], dtype=np.float64))
+        idx = a["scores_sample_index"].astype(np.int64)
+        assert idx.size == a["pos_scores_sample"].size == a["vel_scores_sample"].size > 1000000
+        w = idx // 390625
+        assert np.all(a["pos_scores_sample"] <= a["pos_score"][w]) and np.all(a["vel_scores_sample"] <= a["vel_score"][w])
+        for kind in ("pos", "vel"):
+            best = np.arange(16) * 390625 + a[kind + "_index"].astype(np.int64)
+            at = np.searchsorted(idx, best)
+            assert np.array_equal(idx[at], best) and np.array_equal(a[kind + "_scores_sample"][at], a[kind + "_score"]), kind
+        dumps.append(a)
+    assert set(dumps[0]) == set(dumps[1])
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
