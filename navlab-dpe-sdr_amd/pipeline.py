@@ -20,7 +20,7 @@ def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
     """iq_windows: int16 [W, 2S] (host).  Returns fixes [W, 8] (= xCurrk1k1 per window) and the raw
     per-window result dicts.  One window per Update, fix fed back to the channel manager.
     enable_ekf: route the fix through cuEKF's real filter (EnableEKF=true) instead of the shipped pass-through.
-    reference_pair: dpe_bcm_config.referencePair; keep_scores: every result dict also carries the window's position scores;
+    reference_pair: dpe_bcm_config.referencePair; keep_scores: every result dict also carries the window's position and velocity scores;
     couple_velocity: the filter's F couples position and velocity over one window (cuekf.cu:111-143) or is the identity (ekf.py:47)."""
     import torch
     iq_windows = np.ascontiguousarray(iq_windows)
@@ -48,7 +48,8 @@ def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
         bcm.Update(bcs.CodeScores, bcs.CarrScores, bw, ce)
         r = bcm.results()[0]
         if keep_scores:
-            r["posScores"] = bcm.read_scores()[0][0].copy()
+            ps, vs = bcm.read_scores()
+            r["posScores"], r["velScores"] = ps[0].copy(), vs[0].copy()
         ekf.Update(r["zVal"], r["RVal"])    # EKF_PassMeas (the ML point is the new state) or the filter
         xk1k1, xkk1 = ekf.xCurrk1k1.copy(), ekf.xCurrkk1.copy()
         fixes[w] = xk1k1
@@ -67,7 +68,7 @@ def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
         BatchCorrScores.UpdatePrepared -> BatchCorrManifold.UpdatePrepared -> ChanMgrDev.step
     for every window and collects the fixes from the pinned ring afterwards (at most ring_depth - 1 windows ahead).
     reference_pair: dpe_bcm_config.referencePair (the prepared form re-evaluates from the attached manager's port arrays);
-    keep_scores (tests): waits for every window and keeps its position scores, its code banks and the channel manager's outputs the
+    keep_scores (tests): waits for every window and keeps its position and velocity scores, its code banks and the channel manager's outputs the
     window was scored with (`inputs` = ChanMgrDev.outputs() before the window) -- the loop then does read back.
     enable_ekf: cuEKF's filter inside the measurement kernel (dpe_chm_dev_set_ekf) instead of the pass-through; the fixes are then x_k|k."""
     import torch
@@ -103,7 +104,8 @@ def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
             while got <= w:
                 results.append(cm.fix(got))
                 got += 1
-            results[w]["posScores"] = bcm.read_scores(stream)[0][0].copy()
+            ps, vs = bcm.read_scores(stream)
+            results[w]["posScores"], results[w]["velScores"] = ps[0].copy(), vs[0].copy()
             results[w]["codeBank"] = bcs.read_banks(stream)[0][0].copy()
             results[w]["inputs"] = inputs
     while got < W:

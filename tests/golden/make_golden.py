@@ -19,12 +19,15 @@ reference callables that the CUDA authors used as their oracle (SURVEY.md sectio
   O8 Correlator.coarse_acquisition               correlator.py:53-103
   O11 libgnss/rinex.py parse_rinex on an excerpt of the reference's demofiles/nist1860.18n (data file)
   O10 ExtendedKalmanFilter._time_update_m5 / _measurement_update_m5 (the real filter, vector/ekf.py:160-178)
+  O13 Receiver.dp_track, several iterations on a moving receiver, pass-through and `_m5` filter
+      receiver.py:205-251,398-450; channel.py:158-245; ekf.py:25,27
   O9 Correlator.search_signal (coarse + fine_frequency_acquisition) on two consecutive windows and
      Receiver.scalar_acquisition's keep-the-better rule   correlator.py:38-51,105-133; receiver.py:452-520
 
 Only DATA (inputs + expected outputs) is written; no reference source is copied into the
 repo.  The two harness adaptations below are marked HARNESS and do not touch arithmetic.
 """
+import hashlib
 import os
 import shutil
 import subprocess
@@ -221,6 +224,136 @@ def make_o12(pg):
     run_o3(pg, "highrate_4ms", 25e6, 0.004, 32, ch, 60.0, np.array([1, 0, 0], dtype=bool), prefix="o12")
 
 
+# O13: the closed loop over several windows.  Receiver moving at O13_VEL from the handoff position; the estimator starts
+# O13_OFFSET (ECEF x, y, z, clock; metres) off it with zero velocity.  Seed and offset chosen so that every window's top-two
+# score gap exceeds the tests' tolerances by orders of magnitude (checked by tests/test_oracle_o13.py from the fixture).
+O13_W, O13_SEED, O13_AMP = 6, 17, 200.0
+O13_VEL = (4.0, -2.5, 1.5)
+O13_OFFSET = (80.0, 30.0, -50.0, -90.0)
+O13_STRIDE = 997          # scores are kept at every O13_STRIDE-th grid point (~392 of 390 625) plus the top 32
+O13_SYN = ("rc", "ri", "fc", "fi", "cp", "cp_ref")
+
+
+def o13_samples(o, ho, W=O13_W, seed=O13_SEED, amp=O13_AMP, vel=O13_VEL):
+    """-> iq int16 [W, 2S], truth [W, 8] (state at the start of each window), flips [W, K], syn {name: [W, K]}.
+    Channel parameters along the true trajectory from the oracle's cuChanMgr restatement (the pattern of
+    workload.build_windows), each window synthesised from its start-referenced parameters `syn`; the fixture keeps those
+    synthesis inputs and a digest of the samples, not the samples (tests/test_oracle_o13.py:o13_iq rebuilds them)."""
+    K = len(ho["prn_list"])
+    fs, T = 2.5e6, 0.02
+    S = int(round(fs * T))
+    cm = o.ChanMgr(ho["prn_list"], ho["rc"], ho["ri"], ho["fc"], ho["fi"], ho["cp"], ho["cp_timestamp"], ho["TOW"],
+                   ho["eph"], ho["rxTime"], T)
+    X0 = np.array(ho["X_ECEF"], dtype=np.float64)
+    rate = np.concatenate([np.asarray(vel, dtype=np.float64), X0[7:8]])
+    rng = np.random.Generator(np.random.PCG64(seed))
+    iq, truth, flips = np.empty((W, 2 * S), dtype=np.int16), np.empty((W, 8)), np.empty((W, K), dtype=bool)
+    syn = {n: [] for n in O13_SYN}
+    for w in range(W):
+        X = X0.copy()
+        X[:4] += rate * T * w
+        X[4:8] = rate
+        (cm.start if w == 0 else cm.update)(X, X, (0.0,))
+        ch = dict(rc=cm.rcStart, ri=cm.riStart, fc=cm.fc, fi=cm.fi, cp=cm.cpElaStart, cp_ref=cm.cpRef)
+        for n in O13_SYN:
+            syn[n].append(ch[n].copy())
+        flips[w] = rng.integers(0, 2, K).astype(bool)
+        iq[w] = dpe.synth.gen_iq(seed * 1000 + w, fs, S, dict(prn=ho["prn_list"], **ch), amp=amp, flip=flips[w])
+        truth[w] = X
+    return iq, truth, flips, {n: np.array(v) for n, v in syn.items()}
+
+
+def o13_start(ho, offset=O13_OFFSET):
+    """The estimator's initial state: handoff position and clock + offset, zero velocity and clock drift."""
+    x0 = np.array(ho["X_ECEF"], dtype=np.float64)
+    x0[:4] += np.asarray(offset, dtype=np.float64)
+    x0[4:] = 0.0
+    return x0
+
+
+def run_o13(pg, path, ho, x0, W, fs, T, kf):
+    """Receiver.dp_track (receiver.py:205-225), W iterations on the file at `path`, with taps.  kf: the `_m5` filter steps."""
+    prns = [int(p) for p in ho["prn_list"]]
+    rf = open_rawfile(pg, path, fs, T)
+    S = int(rf.S)
+    rx = pg.receiver.Receiver(rf, mcount_max=W + 4)
+    rx.add_channels(prns)
+    for k, p in enumerate(prns):
+        rx.channels[p].ephemerides = Eph(ho, k)
+    rx.ekf = pg.ekf.ExtendedKalmanFilter(np.asmatrix(x0).T, T=T)
+    if kf:      # HARNESS: the reference's own "Debug for CUDARecv" switch (ekf.py:25,27), set from outside
+        rx.ekf._time_update = rx.ekf._time_update_m5
+        rx.ekf._measurement_update = rx.ekf._measurement_update_m5
+    rx.navguess = pg.receiver.NavigationGuesses()
+    rx.rxTime = ho["rxTime"]
+    rx.ekf.X_ECEF = np.matrix(x0).T
+    rx.rxTime_a = rx.rxTime - (rx.ekf.X_ECEF[3, 0] / 299792458.0)
+    for k, p in enumerate(prns):
+        c = rx.channels[p]
+        c.rc[0], c.ri[0], c.fc[0], c.fi[0], c.cp[0] = ho["rc"][k], ho["ri"][k], ho["fc"][k], ho["fi"][k], float(ho["cp"][k])
+    names = ("rc", "ri", "fc", "fi", "cp")
+    rec = {}
+
+    def put(key, v):
+        rec.setdefault(key, []).append(v)
+
+    def chan(tag, mc):
+        for n in names:
+            put(tag + "_" + n, np.array([float(getattr(rx.channels[p], n)[mc]) for p in prns]))
+
+    for w in range(W):
+        rf.seek_rawfile(rf.S_skip)
+        rf.update_rawsnippet()
+        rx.dp_time_update_state()
+        chan("start", rx._mcount)                     # what the window is correlated with
+        rx.dp_time_update_channels_unfolded()
+        rx._mcount += 1
+        mc = rx._mcount
+        chan("end", mc)                               # after the time update: what the window is scored with
+        put("rxTime", rx.rxTime)
+        put("rxTime_a", rx.rxTime_a)
+        put("x_pred", np.asarray(rx.ekf.X_ECEF).ravel().copy())
+        gfv, gfp = rx.navguess.get_nav_guesses(rx.ekf.X_ECEF, rx.rxTime_a, ECEF_only=True)
+        rx.dp_measurement_estimation_unfolded(gXk_grid=(gfv, gfp))
+        pc, vf = np.asarray(rx.pos_corr).ravel().copy(), np.asarray(rx.vel_fft).ravel().copy()
+        e = np.asarray(rx.dp_measurement_estimation_unfolded()).ravel()
+        rx.dp_measurement_update_state(np.matrix(e).T)
+        rx.dp_measurement_update_channels()
+        chan("upd", mc)                               # after dp_measurement_update_channels
+        put("x_upd", np.asarray(rx.ekf.X_ECEF).ravel().copy())
+        put("rxTime_a_upd", rx.rxTime_a)
+        put("e", e)
+        for tag, v in (("pos", pc), ("vel", vf)):
+            top = np.argsort(-v, kind="stable")[:32]
+            put("argmax_" + tag, int(np.argmax(v)))
+            put(tag + "_sampled", v[::O13_STRIDE])
+            put("top_%s_idx" % tag, top)
+            put("top_" + tag, v[top])
+        assert rec["argmax_pos"][-1] == rec["top_pos_idx"][-1][0] and rec["argmax_vel"][-1] == rec["top_vel_idx"][-1][0]
+    rf.close_rawfile()
+    assert S == int(round(fs * T))
+    return {k: np.array(v) for k, v in rec.items()}
+
+
+def make_o13(pg):
+    """O13: W consecutive Receiver.dp_track iterations of the twin on a moving receiver, twice on the same samples: the
+    shipped pass-through (`_l5`, K = F = I) and the 8-state filter (`_m5`, F = I)."""
+    from oracle import oracle as o
+    ho = dpe.handoff.read_handoff(os.path.join(REF, "demofiles", "handoff_params_usrp6.csv"))
+    fs, T = 2.5e6, 0.02
+    iq, truth, flips, syn = o13_samples(o, ho)
+    path = os.path.join(SCRATCH, "o13.dat")
+    iq.tofile(path)
+    x0 = o13_start(ho)
+    out = dict(iq_sha256=hashlib.sha256(iq.tobytes()).hexdigest(), fs=fs, T=T, S=iq.shape[1] // 2, W=O13_W, seed=O13_SEED,
+               amp=O13_AMP, vel=np.array(O13_VEL), offset=np.array(O13_OFFSET), x0=x0, truth=truth, flips=flips,
+               prn=ho["prn_list"], score_stride=O13_STRIDE, **{"syn_" + n: v for n, v in syn.items()})
+    for tag, kf in (("pt", False), ("kf", True)):
+        for k, v in run_o13(pg, path, ho, x0, O13_W, fs, T, kf).items():
+            out[tag + "_" + k] = v
+    np.savez_compressed(os.path.join(HERE, "o13_dp_track.npz"), **out)
+
+
 def time_dp(pg, iters=3):
     """SURVEY 8d, CPU baseline (2): the PyGNSS DP path timed in the dev container -- per 20 ms window,
     dp_time_update_channels_unfolded (vector_correlate_unfolded x K, the BatchCorrScores twin) and
@@ -286,6 +419,9 @@ def main():
         return
     if "--only-o10" in sys.argv:
         make_o10(pg)
+        return
+    if "--only-o13" in sys.argv:
+        make_o13(pg)
         return
     if "--only-o12" in sys.argv:
         make_o12(pg)
@@ -417,6 +553,7 @@ def main():
     make_o10(pg)
     make_o11(pg)
     make_o12(pg)
+    make_o13(pg)
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print("%-28s %8d bytes" % (f, os.path.getsize(os.path.join(HERE, f))))
