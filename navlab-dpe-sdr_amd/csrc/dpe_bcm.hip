@@ -14,10 +14,11 @@
 //   vel:  idx  = idx0 + g_v (u_enu . delta_v - delta_tdot)          (exactly linear, :1917-1936)
 // followed by the reference's floor / floor(+1) linear interpolation (:1798-1812) and |.|^L.
 //
-// HBM traffic per window per manifold: 16 B/point grid read (float4, coalesced) + 4 B/point score
+// HBM traffic per window per manifold: 16 B/point grid read (scan layout, coalesced) + 4 B/point score
 // write; banks (K x (2L+1) float4 pairs) and SV coefficients live in LDS.
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "dpe_common.h"
 #include "dpe_prep.h"
@@ -43,7 +44,7 @@ constexpr int kPtsPerBlock = 256 * kPtsPerThread;
 
 // One manifold's share of the fused launch
 struct ScanSide {
-    const float4 *grid;       // [G] ENU-dt offsets of this rank's shard
+    const float4 *grid;       // [nTiles * kPtsPerBlock] ENU-dt offsets of this rank's shard in the scan layout (scan_grid_slot)
     const float2 *bank;       // [W][maxK][nEnt] score bank
     const BcmSvDev *sv;       // [W][maxK] coefficients (ignored when they ride in the kernel arguments)
     float *scores;            // [W][pitch] or nullptr (rows start on 128-byte lines, see dpe_bcm_scores_pitch)
@@ -52,6 +53,21 @@ struct ScanSide {
     int nEnt, split;          // bank entries per SV; blocks along x that work on this manifold
 };
 
+// The scan layout of a grid.  Point i = tile * kPtsPerBlock + lane + 256 it (lane < 256, it < kPtsPerThread) is one of the pair
+// (it & ~1, it | 1) of its lane; the tile holds, per pair p, the 256 lanes' {x_a, x_b, y_a, y_b} followed by their
+// {z_a, z_b, t_a, t_b} (a = point 2p, b = point 2p + 1).  Every load instruction of the scan reads 64 lanes x 16 B contiguous
+// and leaves the x / y / z / t pairs in the register pairs the packed fp32 math takes as they are; the grid is padded with
+// zeros to whole tiles, so no load needs a bounds check.  Returns the float index of coordinate c (0 x, 1 y, 2 z, 3 t).
+__host__ __device__ inline size_t scan_grid_slot(long long i, int c)
+{
+    const long long tile = i / kPtsPerBlock, r = i - tile * kPtsPerBlock;
+    const int it = (int)(r >> 8), lane = (int)(r & 255);
+    const long long v = tile * kPtsPerBlock + (long long)((it & ~1) + (c >> 1)) * 256 + lane;   // float4 slot
+    return (size_t)v * 4 + (size_t)((c & 1) * 2 + (it & 1));
+}
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+
 // COMPACT: 12-byte LDS entries {A, B, C} instead of 16 (three dword reads per pair instead of b64 + b32): the layout for
 // bank sets that do not fit the LDS otherwise (37 channels with +-130 .. +-172 entries) -- slower, always with the clamps.
 template <int LP, bool SECOND, bool CLAMP, bool WMEAN, bool COMPACT = false>
@@ -59,7 +75,7 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
                                           unsigned long long *__restrict__ keys, unsigned long long *__restrict__ oob,
                                           int keyStride, int keySlot)
 {
-    const float4 *__restrict__ grid = sd.grid;
+    const f4 *__restrict__ grid = reinterpret_cast<const f4 *>(sd.grid);
     const float2 *__restrict__ bank = sd.bank;
     float *__restrict__ scores = sd.scores;
     double *__restrict__ wsum = sd.wsum;
@@ -79,14 +95,28 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
     __shared__ double sW[4][5];
 
     const int w = blockIdx.y, tid = threadIdx.x;
-    // first tile's grid points: issued before the bank fill so both latencies overlap
-    float4 nxt[kPtsPerThread];
-    {
-        const long long b0 = (long long)blockIdx.x * kPtsPerBlock + tid;
+    // Persistent over point tiles: block (x, w) scores tiles x, x+gridDim.x, ... of window w, so the bank
+    // fill below is paid once per block and the next tile's grid points are prefetched under the
+    // current tile's arithmetic.  gridDim.x is a multiple of 8: blocks are dealt to the 8 XCDs round
+    // robin, so each XCD's L2 keeps re-serving the same 1/8 of the grid for every window.
+    // A thread's points: tile*1024 + tid + 256*it, held as PAIRS (scan_grid_slot) so that the geometry runs on packed fp32
+    // (v_pk_fma_f32: two points per instruction).  The tile count and offsets fit 32 bits (G < 2^32, checked at create).
+    constexpr int kPairs = kPtsPerThread / 2;
+    const unsigned nFull = (unsigned)(G / kPtsPerBlock);                         // tiles without padding
+    const unsigned nTiles = (unsigned)((G + kPtsPerBlock - 1) / kPtsPerBlock);
+    // two register sets for the grid points: tile n computes from one while tile n + nBlkX lands in the other
+    f4 bufA[2 * kPairs], bufB[2 * kPairs];
+    // One tile's loads as buffer loads: the descriptor of the tile is built by scalar instructions, the lane's byte offset is
+    // loop-invariant and the slot offset an immediate, so fetching a tile issues no vector instruction besides the loads.
+    const auto load = [&](f4 (&g)[2 * kPairs], unsigned tile) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<f4 *>(grid + (size_t)tile * kPtsPerBlock), 0, kPtsPerBlock * (int)sizeof(f4), 0x00020000);
 #pragma unroll
-        for (int it = 0; it < kPtsPerThread; ++it)
-            nxt[it] = (b0 + it * 256 < G) ? grid[b0 + it * 256] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+        for (int j = 0; j < 2 * kPairs; ++j)
+            g[j] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, tid * (int)sizeof(f4), j * 256 * (int)sizeof(f4), 0));
+    };
+    // first tile's grid points: issued before the bank fill so both latencies overlap
+    if (blockIdx.x < nTiles) load(bufA, blockIdx.x);
     const float2 *bw = bank + (size_t)w * maxK * nEnt;
     for (int i = tid; i < K * nEnt; i += 256) {
         const int k = i / nEnt, j = i - k * nEnt;
@@ -114,44 +144,28 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
     }
     __syncthreads();
 
-    // Persistent over point tiles: block (x, w) scores tiles x, x+gridDim.x, ... of window w, so the bank
-    // fill above is paid once per block and the next tile's grid points are prefetched under the
-    // current tile's arithmetic.  gridDim.x is a multiple of 8: blocks are dealt to the 8 XCDs round
-    // robin, so each XCD's L2 keeps re-serving the same 1/8 of the grid for every window.
-    // A thread's points: tile*1024 + tid + 256*it (each load instruction: 64 lanes x 16 B contiguous),
-    // held as PAIRS so that the geometry runs on packed fp32 (v_pk_fma_f32: two points per instruction).
-    constexpr int kPairs = kPtsPerThread / 2;
     const unsigned last = (unsigned)(nEnt - 1);
     // wave-uniform address -> scalar loads; inl: this manifold's coefficients come from pb.s[SECOND ? 0 : 1]
     const BcmSvDev *svw = params_ptr(sd.sv + (size_t)w * maxK, inl) + ((inl && !SECOND) ? DPE_MAX_CHAN : 0);
-    const long long nTiles = (G + kPtsPerBlock - 1) / kPtsPerBlock;
     // per-lane running maximum as (score, index): a lane visits its points in increasing index order, so a strict
     // "greater" keeps the first maximum; the packed 64-bit key is built once, after the tile loop
     float bestSc = -1.f;          // scores are >= 0
-    unsigned int bestIdx = 0u;
+    unsigned int bestTile = 0u, bestIt = 0u;
     unsigned int nOob = 0;
     // "Method 1" weighted-mean estimator (optional: wsum != nullptr): sum s, sum s*{x,y,z,t}, pair-packed fp32
     f2 w0 = f2{0.f, 0.f}, w1 = w0, w2 = w0, w3 = w0, w4 = w0;
-    for (long long tile = blockIdx.x; tile < nTiles; tile += nBlkX) {
-        const long long base = tile * kPtsPerBlock + tid;
+    // One tile from the registers g.  RAGGED: the last tile of a grid whose size is not a multiple of kPtsPerBlock -- its
+    // padded points are scored like the others but never stored, compared, summed or counted.  Every other tile runs without
+    // a per-point predicate.
+    const auto tile_body = [&](const f4 (&g)[2 * kPairs], unsigned tile, auto raggedTag) {
+        constexpr bool RAGGED = decltype(raggedTag)::value;
+        const long long base = (long long)tile * kPtsPerBlock + tid;   // (ragged tile only)
         f2 dx[kPairs], dy[kPairs], dz[kPairs], dw[kPairs], q[kPairs], score[kPairs];
 #pragma unroll
         for (int p = 0; p < kPairs; ++p) {
-            const float4 d0 = nxt[2 * p], d1 = nxt[2 * p + 1];
-            dx[p] = f2{d0.x, d1.x}; dy[p] = f2{d0.y, d1.y}; dz[p] = f2{d0.z, d1.z}; dw[p] = f2{d0.w, d1.w};
+            dx[p] = g[2 * p].xy; dy[p] = g[2 * p].zw; dz[p] = g[2 * p + 1].xy; dw[p] = g[2 * p + 1].zw;
             q[p] = dx[p] * dx[p] + dy[p] * dy[p] + dz[p] * dz[p];
             score[p] = f2{0.f, 0.f};
-        }
-        {   // prefetch the next tile of this block (whole lane in range: plain loads, no per-point predicate)
-            const long long b1 = base + (long long)nBlkX * kPtsPerBlock;
-            if (b1 + (kPtsPerThread - 1) * 256 < G) {
-#pragma unroll
-                for (int it = 0; it < kPtsPerThread; ++it) nxt[it] = grid[b1 + it * 256];
-            } else {
-#pragma unroll
-                for (int it = 0; it < kPtsPerThread; ++it)
-                    nxt[it] = (b1 + it * 256 < G) ? grid[b1 + it * 256] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
         }
         unsigned emax = 0;
 #pragma unroll DPE_SV_UNROLL
@@ -207,11 +221,11 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
                 score[p] += f2{c[0], c[1]};
             }
         }
-        // out-of-window bookkeeping off the fast path: recount only if this thread ever hit the zero
-        // slot (or owns padding beyond G)
-        if (CLAMP && (emax == last || base + (kPtsPerThread - 1) * 256 >= G)) {
+        // out-of-window bookkeeping off the fast path: recount only if this thread ever hit the zero slot (the ragged tile's
+        // padded points may have: they are skipped)
+        if (CLAMP && emax == last) {
             for (int it = 0; it < kPtsPerThread; ++it) {
-                if (base + it * 256 >= G) continue;
+                if (RAGGED && base + it * 256 >= G) continue;
                 const float px = dx[it >> 1][it & 1], py = dy[it >> 1][it & 1], pz = dz[it >> 1][it & 1];
                 const float pw = dw[it >> 1][it & 1], pq = q[it >> 1][it & 1];
                 for (int k = 0; k < K; ++k) {
@@ -235,7 +249,7 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
 #pragma unroll
             for (int p = 0; p < kPairs; ++p) {
                 f2 sc = score[p];
-                if (base + (kPtsPerThread - 1) * 256 >= G) {   // ragged last tile: padded points must not count
+                if (RAGGED) {   // padded points must not count
                     if (base + (2 * p) * 256 >= G) sc.x = 0.f;
                     if (base + (2 * p + 1) * 256 >= G) sc.y = 0.f;
                 }
@@ -246,31 +260,44 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
                 w4 = __builtin_elementwise_fma(sc, dw[p], w4);
             }
         }
-        const unsigned int gi0 = (unsigned int)(base + indexOffset);   // global index of the lane's first point (< 2^32, checked at create)
-        if (base + (kPtsPerThread - 1) * 256 < G) {
-            // whole lane inside the grid (every tile but the last): no per-point bounds checks, one store address
-            float *srow = scores ? scores + (size_t)w * sd.pitch + base : nullptr;
+        // scores are written once and never read back on this path: non-temporal stores keep ~0.8 GB per 256-window
+        // call from lingering as dirty L2 / Infinity-Cache lines whose write-back would run into the NEXT call's
+        // first kernels (measured: the following DC-sum kernel 25 -> 13 us, step 0.863 -> 0.851 ms)
+        if (scores) {
+            float *srow = scores + (size_t)w * sd.pitch + (size_t)tile * kPtsPerBlock;   // wave-uniform
 #pragma unroll
-            for (int it = 0; it < kPtsPerThread; ++it) {
-                const float sc = score[it >> 1][it & 1];
-                // scores are written once and never read back on this path: non-temporal stores keep ~0.8 GB per 256-window
-                // call from lingering as dirty L2 / Infinity-Cache lines whose write-back would run into the NEXT call's
-                // first kernels (measured: the following DC-sum kernel 25 -> 13 us, step 0.863 -> 0.851 ms)
-                if (scores) __builtin_nontemporal_store(sc, &srow[it * 256]);
-                if (sc > bestSc) { bestSc = sc; bestIdx = gi0 + it * 256; }
-            }
-        } else {
-#pragma unroll
-            for (int it = 0; it < kPtsPerThread; ++it) {
-                const long long i = base + it * 256;
-                if (i < G) {
-                    const float sc = score[it >> 1][it & 1];
-                    if (scores) __builtin_nontemporal_store(sc, &scores[(size_t)w * sd.pitch + i]);
-                    if (sc > bestSc) { bestSc = sc; bestIdx = gi0 + it * 256; }
-                }
-            }
+            for (int it = 0; it < kPtsPerThread; ++it)
+                if (!RAGGED || base + it * 256 < G) __builtin_nontemporal_store(score[it >> 1][it & 1], &srow[it * 256 + tid]);
         }
+        // the running maximum remembers (tile, it) of its point; the index is formed once, after the tile loop
+#pragma unroll
+        for (int it = 0; it < kPtsPerThread; ++it) {
+            const float sc = score[it >> 1][it & 1];
+            if ((!RAGGED || base + it * 256 < G) && sc > bestSc) { bestSc = sc; bestTile = tile; bestIt = (unsigned)it; }
+        }
+    };
+    // Full tiles, unrolled by two so that the prefetch alternates between the register sets (no moves carry a tile from one
+    // set to the other); the ragged tile, if this block owns it, comes last (it is the grid's last tile).
+    unsigned tile = blockIdx.x;
+    for (;;) {
+        if (tile >= nFull) break;
+        const unsigned t1 = tile + nBlkX;
+        if (t1 < nTiles) load(bufB, t1);
+        tile_body(bufA, tile, std::false_type{});
+        tile = t1;
+        if (tile >= nFull) {
+#pragma unroll
+            for (int j = 0; j < 2 * kPairs; ++j) bufA[j] = bufB[j];   // (once per block, for the ragged tile below)
+            break;
+        }
+        const unsigned t2 = tile + nBlkX;
+        if (t2 < nTiles) load(bufA, t2);
+        tile_body(bufB, tile, std::false_type{});
+        tile = t2;
     }
+    if (tile < nTiles) tile_body(bufA, tile, std::true_type{});
+    // global index of the lane's best point (< 2^32, checked at create)
+    const unsigned int bestIdx = (unsigned int)indexOffset + bestTile * (unsigned int)kPtsPerBlock + bestIt * 256u + (unsigned int)tid;
     unsigned long long best = bestSc < 0.f ? 0ull
                                            : (((unsigned long long)__float_as_uint(bestSc) << 32) |
                                               (unsigned long long)(0xFFFFFFFFu - bestIdx));
@@ -437,7 +464,8 @@ __global__ __launch_bounds__(256) void bcm_refpair_candidates_kernel(const float
     const int w = blockIdx.y;
     const BcmSvDev p0 = sv[(size_t)w * maxK];
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < G; i += (long long)gridDim.x * 256) {
-        const float4 g = grid[i];
+        const float *gf = reinterpret_cast<const float *>(grid);   // (the scan layout)
+        const float4 g = make_float4(gf[scan_grid_slot(i, 0)], gf[scan_grid_slot(i, 1)], gf[scan_grid_slot(i, 2)], gf[scan_grid_slot(i, 3)]);
         const double a = (double)p0.ue * g.x + (double)p0.un * g.y + (double)p0.uu * g.z;
         const double q = (double)g.x * g.x + (double)g.y * g.y + (double)g.z * g.z;
         const double idx0 = (double)p0.idx0 + (double)p0.g * ((double)g.w - a + (q - a * a) * (double)p0.h);
@@ -559,7 +587,7 @@ __global__ __launch_bounds__(64) void bcm_refpair_eval_kernel(BcmPortsDev p, int
 struct dpe_bcm {
     dpe_bcm_config cfg;
     std::vector<double> posGrid_h, velGrid_h;  // local shard, fp64 (for zVal)
-    float4 *posGrid_d = nullptr, *velGrid_d = nullptr;
+    float4 *posGrid_d = nullptr, *velGrid_d = nullptr;   // fp32, in the scan layout (dpe::scan_grid_slot)
     dpe_owner_detach_fn ownerDetach = nullptr;   // an attached device-resident channel manager: told first when this handle is destroyed
     void *owner = nullptr;
     bool gridsBorrowed = false;   // the fp32 device grids belong to another handle of the same dpe_pipe (dpe_bcm_create_sharing)
@@ -613,16 +641,18 @@ struct dpe_bcm {
     dpe::GraphCache graphs;
 };
 
+// The device copy is the scan layout (dpe::scan_grid_slot), zero-padded to whole tiles: the only fp32 copy on the device
 static int upload_grid(const double *src, int64_t G, std::vector<double> &keep, float4 **dst)
 {
     using namespace dpe;
     keep.assign(src, src + 4 * G);
-    std::vector<float4> f((size_t)G);
+    const size_t nPad = (size_t)((G + kPtsPerBlock - 1) / kPtsPerBlock) * kPtsPerBlock;
+    std::vector<float> f(4 * nPad, 0.f);
     for (int64_t i = 0; i < G; ++i)
-        f[i] = make_float4((float)src[4 * i], (float)src[4 * i + 1], (float)src[4 * i + 2], (float)src[4 * i + 3]);
-    *dst = dev_alloc<float4>((size_t)G);
+        for (int c = 0; c < 4; ++c) f[scan_grid_slot(i, c)] = (float)src[4 * i + c];
+    *dst = dev_alloc<float4>(nPad);
     DPE_REQUIRE(*dst, "[BatchCorrManifold] create: grid allocation failed (%lld points)", (long long)G);
-    DPE_CHECK_HIP(hipMemcpy(*dst, f.data(), sizeof(float4) * (size_t)G, hipMemcpyHostToDevice));
+    DPE_CHECK_HIP(hipMemcpy(*dst, f.data(), sizeof(float4) * nPad, hipMemcpyHostToDevice));
     return 0;
 }
 

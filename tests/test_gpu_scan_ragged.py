@@ -1,0 +1,94 @@
+"""The manifold scan at grid sizes that are not whole 1024-point tiles, on sharded grids (index offsets) and on grids with
+duplicated points: the ragged last tile, the first-maximum rule and the out-of-window counts against the oracle and
+against the scan's own score rows."""
+import numpy as np
+import pytest
+
+import navlab_dpe_sdr_amd as dpe
+
+from .helpers import assert_parity, make_case, pack_gpu_inputs, run_gpu, run_oracle
+
+L, B = 4, 20
+
+
+def _scan(case, pos, vel, pos_off=0, vel_off=0, weighted_mean=True):
+    """One BCS + BCM pass over all windows of `case` with the given grids; returns (results, pos scores, vel scores)."""
+    import torch
+    iq, cs, ce, bw = pack_gpu_inputs(case)
+    W, K = cs.shape
+    iq_d = torch.from_numpy(iq).to(torch.device("cuda:0"))
+    bcs = dpe.BatchCorrScores(case["fs"], samples_per_window=case["S"], lag_half_width=L, bin_half_width=B,
+                              max_windows=W, max_channels=K)
+    bcs.Start()
+    bcm = dpe.BatchCorrManifold(case["fs"], case["S"], bcs.NumFFTPoints, pos, vel, lag_half_width=L, bin_half_width=B,
+                                max_windows=W, max_channels=K, write_scores=True, weighted_mean=weighted_mean,
+                                pos_index_offset=pos_off, vel_index_offset=vel_off)
+    bcm.Start()
+    bcs.Update(iq_d, cs)
+    bcm.Update(bcs.CodeScores, bcs.CarrScores, bw, ce)
+    res = bcm.results()
+    ps, vs = bcm.read_scores()
+    bcm.Stop()
+    bcs.Stop()
+    return res, ps, vs
+
+
+def _first_max(row):
+    return int(np.argmax(row))   # numpy returns the first occurrence of the maximum
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G", [100, 1023, 1025, 2047, 3073])
+def test_ragged_sizes_against_oracle(G):
+    case = make_case(seed=40 + G % 7, G=G, W=2)
+    ref = run_oracle(case, L, B)
+    gpu = run_gpu(case, L, B)
+    assert_parity(gpu, ref)
+    for w in range(case["W"]):
+        r = gpu["res"][w]
+        assert r["posIndex"] == _first_max(gpu["pos"][w])
+        assert r["velIndex"] == _first_max(gpu["vel"][w])
+
+
+@pytest.mark.gpu
+def test_duplicated_points_keep_the_first_maximum():
+    """The grid twice over (plus a ragged tail of its first points): every copy of a point sits in another lane, slot or
+    tile and must score the same bits; the arg-max must name the first copy; out-of-window counts scale with the copies."""
+    G0 = 1300
+    case = make_case(seed=11, G=G0, W=2)
+    pos, vel = case["pos"], case["vel"]
+    res1, ps1, vs1 = _scan(case, pos, vel)
+    tail = 333
+    pos3 = np.concatenate([pos, pos, pos[:tail]])
+    vel3 = np.concatenate([vel, vel, vel[:tail]])
+    res3, ps3, vs3 = _scan(case, pos3, vel3)
+    for w in range(case["W"]):
+        for one, three in ((ps1[w], ps3[w]), (vs1[w], vs3[w])):
+            assert np.array_equal(three[:G0].view(np.uint32), one.view(np.uint32))
+            assert np.array_equal(three[G0:2 * G0].view(np.uint32), one.view(np.uint32))
+            assert np.array_equal(three[2 * G0:].view(np.uint32), one[:tail].view(np.uint32))
+        assert res3[w]["posIndex"] == res1[w]["posIndex"] == _first_max(ps3[w])
+        assert res3[w]["velIndex"] == res1[w]["velIndex"] == _first_max(vs3[w])
+    # out-of-window counts: the second copy adds as many as the first; the tail adds those of the first `tail` points
+    res_t, _, _ = _scan(case, pos[:tail], vel[:tail])
+    for w in range(case["W"]):
+        assert res3[w]["posOutOfWindow"] == 2 * res1[w]["posOutOfWindow"] + res_t[w]["posOutOfWindow"]
+        assert res3[w]["velOutOfWindow"] == 2 * res1[w]["velOutOfWindow"] + res_t[w]["velOutOfWindow"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G", [1024, 2049])
+def test_sharded_offsets(G):
+    """A shard with index offsets scores its points exactly as the unsharded handle does; the keys carry the global index."""
+    case = make_case(seed=23, G=G, W=2)
+    res0, ps0, vs0 = _scan(case, case["pos"], case["vel"])
+    po, vo = 5 * 1024 + 17, 3 * 1024 + 1000
+    res1, ps1, vs1 = _scan(case, case["pos"], case["vel"], pos_off=po, vel_off=vo)
+    assert np.array_equal(ps0.view(np.uint32), ps1.view(np.uint32))
+    assert np.array_equal(vs0.view(np.uint32), vs1.view(np.uint32))
+    for w in range(case["W"]):
+        assert res1[w]["posIndex"] == po + _first_max(ps0[w]) and res0[w]["posIndex"] == _first_max(ps0[w])
+        assert res1[w]["velIndex"] == vo + _first_max(vs0[w]) and res0[w]["velIndex"] == _first_max(vs0[w])
+        assert res1[w]["posOutOfWindow"] == res0[w]["posOutOfWindow"]
+        assert res1[w]["velOutOfWindow"] == res0[w]["velOutOfWindow"]
+        assert np.array_equal(res1[w]["weightedSums"], res0[w]["weightedSums"])
