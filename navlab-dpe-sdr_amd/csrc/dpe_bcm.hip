@@ -346,32 +346,11 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
     }
 }
 
-// Both manifolds in ONE launch: blockIdx.z = 0 scores the position grid, 1 the velocity grid (a lone
-// window then pays one launch instead of two and the two scans overlap).  Around the scans the kernel
-//  * clears the key / counter set of the NEXT Update (the two sets alternate), so that no clearing
-//    launch or memset node sits on the critical path, and
-//  * lets the last block to finish publish keys and out-of-window counts of all windows straight
-//    into the pinned host mirror (system-scope stores): dpe_bcm_results needs no D2H copy command.
-// `done` cycles 0 .. total-1 through atomicInc and is back at 0 when the kernel ends.
-template <int LP, bool CLAMP_P, bool CLAMP_V, bool WMEAN, bool COMPACT = false>
-__global__ __launch_bounds__(256) void bcm_scan_kernel(BcmParamBlock pb, int inl, ScanSide sp, ScanSide sv, int K, int maxK,
-                                                       int lpower, unsigned long long *__restrict__ keys,
-                                                       unsigned long long *__restrict__ oob,
-                                                       unsigned long long *__restrict__ clearPtr, int clearN,
-                                                       unsigned int *__restrict__ done,
-                                                       unsigned long long *__restrict__ hostKeys,
-                                                       unsigned long long *__restrict__ hostOob,
-                                                       unsigned long long seqValue)
+// ---- the scans' common epilogue: the last block out publishes the results
+__device__ __forceinline__ void scan_publish(unsigned long long *__restrict__ keys, unsigned long long *__restrict__ oob,
+                                             unsigned int *__restrict__ done, unsigned long long *__restrict__ hostKeys,
+                                             unsigned long long *__restrict__ hostOob, unsigned long long seqValue)
 {
-    (void)pb;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
-        for (int i = threadIdx.x; i < clearN; i += 256) clearPtr[i] = 0ull;
-    if (blockIdx.z == 0) {
-        if (blockIdx.x < (unsigned)sp.split) scan_body<LP, true, CLAMP_P, WMEAN, COMPACT>(sp, inl, K, maxK, lpower, keys, oob, 2, 0);
-    } else {
-        if (blockIdx.x < (unsigned)sv.split) scan_body<LP, false, CLAMP_V, WMEAN, COMPACT>(sv, inl, K, maxK, lpower, keys, oob, 2, 1);
-    }
-    // ---- last block out publishes the results
     // Thread 0 issued this block's key / counter atomics and has their return values, i.e. they are
     // performed at the device's coherence point; its ticket follows in program order.  The block that
     // draws the last ticket therefore reads final values with agent-scope loads.
@@ -413,6 +392,40 @@ __global__ __launch_bounds__(256) void bcm_scan_kernel(BcmParamBlock pb, int inl
         }
     }
 }
+
+// Both manifolds in ONE launch: blockIdx.z = 0 scores the position grid, 1 the velocity grid (a lone
+// window then pays one launch instead of two and the two scans overlap).  Around the scans the kernel
+//  * clears the key / counter set of the NEXT Update (the two sets alternate), so that no clearing
+//    launch or memset node sits on the critical path, and
+//  * lets the last block to finish publish keys and out-of-window counts of all windows straight
+//    into the pinned host mirror (system-scope stores): dpe_bcm_results needs no D2H copy command.
+// `done` cycles 0 .. total-1 through atomicInc and is back at 0 when the kernel ends.
+template <int LP, bool CLAMP_P, bool CLAMP_V, bool WMEAN, bool COMPACT = false>
+__global__ __launch_bounds__(256) void bcm_scan_kernel(BcmParamBlock pb, int inl, ScanSide sp, ScanSide sv, int K, int maxK,
+                                                       int lpower, unsigned long long *__restrict__ keys,
+                                                       unsigned long long *__restrict__ oob,
+                                                       unsigned long long *__restrict__ clearPtr, int clearN,
+                                                       unsigned int *__restrict__ done,
+                                                       unsigned long long *__restrict__ hostKeys,
+                                                       unsigned long long *__restrict__ hostOob,
+                                                       unsigned long long seqValue)
+{
+    (void)pb;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
+        for (int i = threadIdx.x; i < clearN; i += 256) clearPtr[i] = 0ull;
+    if (blockIdx.z == 0) {
+        if (blockIdx.x < (unsigned)sp.split) scan_body<LP, true, CLAMP_P, WMEAN, COMPACT>(sp, inl, K, maxK, lpower, keys, oob, 2, 0);
+    } else {
+        if (blockIdx.x < (unsigned)sv.split) scan_body<LP, false, CLAMP_V, WMEAN, COMPACT>(sv, inl, K, maxK, lpower, keys, oob, 2, 1);
+    }
+    scan_publish(keys, oob, done, hostKeys, hostOob, seqValue);
+}
+
+}  // namespace dpe
+
+#include "dpe_bcm_axes.h"
+
+namespace dpe {
 
 // Device-resident inputs (dpe_bcm_update_dev): the per-SV coefficients of both manifolds from the reference's own port arrays
 // on the device (cuChanMgr / cuEKF outputs, dpeflow.cpp:178-191,212; captured once by the reference at
@@ -637,6 +650,16 @@ struct dpe_bcm {
     bool publish = true;        // false: the scan leaves keys / counts in device memory only (set by the device-resident channel manager's attach)
     bool lastPublished = true;  // what the last Update did
     double posExtent = 0, velExtent = 0;
+    // grids given by their axes (dpe_bcm_create_axes): the handle keeps the global axes, never a per-point copy
+    bool axes = false;
+    struct Axes {
+        int dim[4];
+        std::vector<double> v[4];   // fp64, for decoding an index into a point
+    } posAx, velAx;
+    float *axes_d = nullptr;        // both manifolds' fp32 axes in one block (layout: AxesSide), t padded by kAxT
+    int axOff[2][4] = {};           // float offsets of the x, y, z, t axes of each manifold in axes_d
+    bool axesBorrowed = false;      // axes_d belongs to another lane of the same dpe_pipe
+    double *posAx64_d = nullptr, *velAx64_d = nullptr;   // fp64 global axes for a measurement formed on the device (dpe_bcm_hook_get)
     dpe::KernelProfiler prof;  // slot 0: the fused position + velocity scan
     dpe::GraphCache graphs;
 };
@@ -730,6 +753,66 @@ static void launch_scan(bool clampP, bool clampV, bool wmean, bool compact, cons
     if (clampP) { if (clampV) DPE_SCAN_PICK(true, true); else DPE_SCAN_PICK(true, false); }
     else { if (clampV) DPE_SCAN_PICK(false, true); else DPE_SCAN_PICK(false, false); }
 #undef DPE_SCAN_PICK
+}
+
+// Grids given by their axes (dpe_bcm_create_axes): the same launch with AxesSide in place of ScanSide
+struct AxesLaunch {
+    ScanLaunch a;
+    dpe::AxesSide sp, sv;
+};
+
+template <int LP, bool CP, bool CV, bool WM>
+static void launch_axes4(const AxesLaunch &x)
+{
+    const ScanLaunch &a = x.a;
+    hipLaunchKernelGGL((dpe::bcm_scan_axes_kernel<LP, CP, CV, WM>), a.grid, dim3(256), a.lds, a.st, a.pb, a.inl, x.sp, x.sv, a.K, a.maxK,
+                       a.lp, a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+}
+
+template <bool CP, bool CV, bool WM>
+static void launch_axes3(const AxesLaunch &x)
+{
+    if (x.a.lp == 1) launch_axes4<1, CP, CV, WM>(x);
+    else if (x.a.lp == 2) launch_axes4<2, CP, CV, WM>(x);
+    else launch_axes4<0, CP, CV, WM>(x);
+}
+
+static void launch_axes(bool clampP, bool clampV, bool wmean, const AxesLaunch &x)
+{
+#define DPE_AXES_PICK(CP, CV) do { if (wmean) launch_axes3<CP, CV, true>(x); else launch_axes3<CP, CV, false>(x); } while (0)
+    if (clampP) { if (clampV) DPE_AXES_PICK(true, true); else DPE_AXES_PICK(true, false); }
+    else { if (clampV) DPE_AXES_PICK(false, true); else DPE_AXES_PICK(false, false); }
+#undef DPE_AXES_PICK
+}
+
+template <int LP>
+static void allow_big_lds_axes()
+{
+#define DPE_AXES_LDS(CP, CV, WM) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_axes_kernel<LP, CP, CV, WM>, \
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
+    DPE_AXES_LDS(true, true, false); DPE_AXES_LDS(true, false, false); DPE_AXES_LDS(false, true, false); DPE_AXES_LDS(false, false, false);
+    DPE_AXES_LDS(true, true, true); DPE_AXES_LDS(true, false, true); DPE_AXES_LDS(false, true, true); DPE_AXES_LDS(false, false, true);
+#undef DPE_AXES_LDS
+}
+
+// One manifold's AxesSide (m = 0 position, 1 velocity) for this handle's slice; the tile count comes back in *nTiles
+static dpe::AxesSide axes_side(const dpe_bcm *h, int m, long long *nTiles)
+{
+    const dpe_bcm::Axes &ax = m ? h->velAx : h->posAx;
+    const long long off = m ? h->cfg.velGridIndexOffset : h->cfg.posGridIndexOffset, G = m ? h->cfg.velGridSize : h->cfg.posGridSize;
+    const long long dimT = ax.dim[3];
+    dpe::AxesSide s{};
+    s.ax = h->axes_d;
+    s.offX = h->axOff[m][0]; s.offY = h->axOff[m][1]; s.offZ = h->axOff[m][2]; s.offT = h->axOff[m][3];
+    s.dimY = ax.dim[1]; s.dimZ = ax.dim[2]; s.dimT = (int)dimT;
+    s.nChunks = (int)((dimT + dpe::kAxT - 1) / dpe::kAxT);
+    s.chunk = (int)((dimT + s.nChunks - 1) / s.nChunks);   // chunks of (nearly) equal length: no chunk of a few entries
+    const long long rowBegin = off / dimT, rowEnd = (off + G + dimT - 1) / dimT;
+    s.rowBegin = (unsigned)rowBegin; s.nRows = (unsigned)(rowEnd - rowBegin);
+    s.fullBegin = (unsigned)((off + dimT - 1) / dimT); s.fullEnd = (unsigned)((off + G) / dimT);
+    s.gBegin = (unsigned)off; s.G = (unsigned)G;
+    *nTiles = (rowEnd - rowBegin + 255) / 256 * s.nChunks;
+    return s;
 }
 
 template <int LP, bool CP, bool CV>
@@ -886,6 +969,69 @@ static int ref_pair_fixup(dpe_bcm *h, const float *codeBank_dev, int nWindows, i
     return 0;
 }
 
+// The buffers every handle has, whatever holds its grids (create and create_axes)
+static int bcm_finish_create(dpe_bcm *h, const dpe_bcm_config *cfg, dpe_bcm **out)
+{
+    using namespace dpe;
+    const size_t W = cfg->maxWindows, K = cfg->maxChannels;
+    // score rows start on 128-byte lines: a wave's 64 consecutive scores are then two whole lines instead of one whole and two
+    // partial ones (config R, 390 625-point rows: 0.779 -> 0.755 ms per step, the write-back of a step's 0.8 GB drains faster)
+    h->posPitch = (cfg->posGridSize + 31) / 32 * 32;
+    h->velPitch = (cfg->velGridSize + 31) / 32 * 32;
+    if (cfg->writeScores) {
+        h->posScores_d = dev_alloc<float>(W * (size_t)h->posPitch);
+        h->velScores_d = dev_alloc<float>(W * (size_t)h->velPitch);
+    }
+    h->sv_d = dev_alloc<BcmSvDev>(2 * W * K);
+    h->keys_d = dev_alloc<unsigned long long>(8 * W);   // two alternating sets of {keys [W][2], out-of-window counts [W][2]}
+    h->wsumHalf = (size_t)(dpe_bcm::kMaxSplit + 8 * W) * 5;   // >= nWindows * blocks-per-window of any launch
+    h->wsum_d = dev_alloc<double>(2 * h->wsumHalf);
+    if ((cfg->writeScores && (!h->posScores_d || !h->velScores_d)) || !h->sv_d || !h->keys_d || !h->wsum_d ||
+        hipHostMalloc((void **)&h->svBase_h, dpe_bcm::kStaging * 2 * W * K * sizeof(BcmSvDev), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void **)&h->devWin_h, 2 * sizeof(BcmDevWin), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void **)&h->keys_h, (4 * W + 8) * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
+        set_error("[BatchCorrManifold] create: device allocation failed");
+        dpe_bcm_destroy(h);
+        return -1;
+    }
+    // dynamic LDS above 64 KB needs the opt-in attribute
+    allow_big_lds<0, true, true>();  allow_big_lds<1, true, true>();  allow_big_lds<2, true, true>();
+    allow_big_lds<0, false, true>(); allow_big_lds<1, false, true>(); allow_big_lds<2, false, true>();
+    allow_big_lds<0, true, false>();  allow_big_lds<1, true, false>();  allow_big_lds<2, true, false>();
+    allow_big_lds<0, false, false>(); allow_big_lds<1, false, false>(); allow_big_lds<2, false, false>();
+    if (h->refPair &&
+        hipHostMalloc((void **)&h->refBank_h, W * K * (size_t)(2 * cfg->lagHalfWidth + 1) * sizeof(float2), hipHostMallocDefault) != hipSuccess) {
+        set_error("[BatchCorrManifold] create: host allocation failed");
+        dpe_bcm_destroy(h);
+        return -1;
+    }
+    h->oob_h = h->keys_h + 2 * W;
+    for (size_t i = 0; i < 4 * W + 8; ++i) h->keys_h[i] = 0ull;
+    h->pollAllowed = getenv("DPE_BCM_NO_POLL") == nullptr;
+#ifdef DPE_EXPERIMENTS
+    if (const char *e = getenv("DPE_BCM_SPLIT")) h->splitForce = atoi(e) > 0 && atoi(e) <= (int)dpe_bcm::kMaxSplit ? atoi(e) : 0;
+#endif
+    h->sv_h = h->svBase_h;
+    const auto finish = [&]() -> int {   // a failure from here on must not leak the handle
+        for (hipEvent_t &e : h->stagingFree) DPE_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        DPE_CHECK_HIP(hipMemset(h->keys_d, 0, 8 * W * sizeof(unsigned long long)));
+        h->done_d = dev_alloc<unsigned int>(1);
+        DPE_REQUIRE(h->done_d, "[BatchCorrManifold] create: device allocation failed");
+        DPE_CHECK_HIP(hipMemset(h->done_d, 0, sizeof(unsigned int)));
+        DPE_CHECK_HIP(hipHostGetDevicePointer((void **)&h->keys_hd, h->keys_h, 0));
+        DPE_CHECK_HIP(hipHostGetDevicePointer((void **)&h->svBase_hd, h->svBase_h, 0));
+        DPE_CHECK_HIP(hipHostGetDevicePointer((void **)&h->devWin_hd, h->devWin_h, 0));
+        return 0;
+    };
+    if (finish()) {
+        dpe_bcm_destroy(h);
+        return -1;
+    }
+    h->win_h.resize(W);
+    *out = h;
+    return 0;
+}
+
 extern "C" {
 
 int dpe_bcm_create(const dpe_bcm_config *cfg, dpe_bcm **out)
@@ -948,7 +1094,6 @@ int dpe_bcm_create_sharing(const dpe_bcm_config *cfg, dpe_bcm *donor, dpe_bcm **
     }
     h->posExtent = posExt * 1.000001 + maxR2 / 2.0e7 + 1e-3;   // + second-order term bound (range > 2e7 m) + fp32 slack
     h->velExtent = velExt * 1.000001 + 1e-6;
-    const size_t W = cfg->maxWindows, K = cfg->maxChannels;
     if (donor) {      // a further lane of a dpe_pipe: the same grids, one device copy
         h->posGrid_h = donor->posGrid_h; h->velGrid_h = donor->velGrid_h;
         h->posGrid_d = donor->posGrid_d; h->velGrid_d = donor->velGrid_d;
@@ -958,62 +1103,97 @@ int dpe_bcm_create_sharing(const dpe_bcm_config *cfg, dpe_bcm *donor, dpe_bcm **
         dpe_bcm_destroy(h);
         return -1;
     }
-    // score rows start on 128-byte lines: a wave's 64 consecutive scores are then two whole lines instead of one whole and two
-    // partial ones (config R, 390 625-point rows: 0.779 -> 0.755 ms per step, the write-back of a step's 0.8 GB drains faster)
-    h->posPitch = (cfg->posGridSize + 31) / 32 * 32;
-    h->velPitch = (cfg->velGridSize + 31) / 32 * 32;
-    if (cfg->writeScores) {
-        h->posScores_d = dev_alloc<float>(W * (size_t)h->posPitch);
-        h->velScores_d = dev_alloc<float>(W * (size_t)h->velPitch);
+    return bcm_finish_create(h, cfg, out);
+}
+
+// Grids given by their axes.  donor != nullptr: a further lane of a dpe_pipe, which uses donor's device copy of the axes.
+int dpe_bcm_create_axes_sharing(const dpe_bcm_config *cfg, const dpe_grid_axes *pos, const dpe_grid_axes *vel, dpe_bcm *donor,
+                                dpe_bcm **out)
+{
+    using namespace dpe;
+    DPE_REQUIRE(cfg && pos && vel && out, "[BatchCorrManifold] create_axes: null argument");
+    DPE_REQUIRE(!cfg->posGrid && !cfg->velGrid, "[BatchCorrManifold] create_axes: posGrid / velGrid must be NULL (the grids are the axes)");
+    DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_axes: referencePair is not supported with grid axes");
+    DPE_REQUIRE(cfg->samplesPerWindow > 0 && (cfg->samplesPerWindow % 2) == 0,
+                "[BatchCorrManifold] create_axes: samplesPerWindow must be even and positive");
+    DPE_REQUIRE(cfg->samplingFrequency > 0 && cfg->numFFTPoints > 0, "[BatchCorrManifold] create_axes: bad fs / numFFTPoints");
+    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
+                "[BatchCorrManifold] create_axes: maxWindows/maxChannels out of range");
+    DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1 && cfg->lPower >= 1, "[BatchCorrManifold] create_axes: bad L/B/LPower");
+    const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
+    DPE_REQUIRE((size_t)cfg->maxChannels * (nEntMax * 16 + 32) + (size_t)kAxStageBytes <= 150 * 1024,
+                "[BatchCorrManifold] create_axes: score banks (%zu B) and the score stage (%d B) exceed the LDS (no 12-byte bank entries with grid axes)",
+                (size_t)cfg->maxChannels * nEntMax * 16, kAxStageBytes);
+    const dpe_grid_axes *ga[2] = {pos, vel};
+    const int64_t size[2] = {cfg->posGridSize, cfg->velGridSize}, offset[2] = {cfg->posGridIndexOffset, cfg->velGridIndexOffset};
+    double ext[2], r2[2];
+    for (int m = 0; m < 2; ++m) {
+        const char *name = m ? "velocity" : "position";
+        double mx[4] = {0, 0, 0, 0};
+        int64_t prod = 1;
+        for (int c = 0; c < 4; ++c) {
+            DPE_REQUIRE(ga[m]->dim[c] >= 1 && ga[m]->axis[c], "[BatchCorrManifold] create_axes: %s axis %d: dim %d < 1 or no array", name, c,
+                        ga[m]->dim[c]);
+            for (int i = 0; i < ga[m]->dim[c]; ++i) {
+                const double v = ga[m]->axis[c][i];
+                DPE_REQUIRE(std::isfinite(v), "[BatchCorrManifold] create_axes: %s axis %d entry %d is not finite", name, c, i);
+                mx[c] = std::max(mx[c], std::fabs(v));
+            }
+            DPE_REQUIRE(prod <= 0xFFFFFFFFll / ga[m]->dim[c], "[BatchCorrManifold] create_axes: %s grid index does not fit 32 bits", name);
+            prod *= ga[m]->dim[c];
+        }
+        DPE_REQUIRE(size[m] > 0 && offset[m] >= 0 && offset[m] + size[m] <= prod,
+                    "[BatchCorrManifold] create_axes: %s slice [%lld, %lld) beyond the axis product %lld", name, (long long)offset[m],
+                    (long long)(offset[m] + size[m]), (long long)prod);
+        // every index the scan forms, including those of the lanes that run past the slice's last row, fits 32 bits
+        const int64_t dimT = ga[m]->dim[3], rowEnd = (offset[m] + size[m] + dimT - 1) / dimT;
+        DPE_REQUIRE((rowEnd + 256) * dimT + kAxT < 0xFFFFFFFFll, "[BatchCorrManifold] create_axes: %s grid index does not fit 32 bits", name);
+        r2[m] = mx[0] * mx[0] + mx[1] * mx[1] + mx[2] * mx[2];
+        ext[m] = std::sqrt(r2[m]) + mx[3];   // bounds |delta_t| + |delta_xyz| over the grid, as the point-list extents
     }
-    h->sv_d = dev_alloc<BcmSvDev>(2 * W * K);
-    h->keys_d = dev_alloc<unsigned long long>(8 * W);   // two alternating sets of {keys [W][2], out-of-window counts [W][2]}
-    h->wsumHalf = (size_t)(dpe_bcm::kMaxSplit + 8 * W) * 5;   // >= nWindows * blocks-per-window of any launch
-    h->wsum_d = dev_alloc<double>(2 * h->wsumHalf);
-    if ((cfg->writeScores && (!h->posScores_d || !h->velScores_d)) || !h->sv_d || !h->keys_d || !h->wsum_d ||
-        hipHostMalloc((void **)&h->svBase_h, dpe_bcm::kStaging * 2 * W * K * sizeof(BcmSvDev), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&h->devWin_h, 2 * sizeof(BcmDevWin), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&h->keys_h, (4 * W + 8) * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
-        set_error("[BatchCorrManifold] create: device allocation failed");
-        dpe_bcm_destroy(h);
-        return -1;
+    DPE_REQUIRE(r2[0] < 3.0e3 * 3.0e3, "[BatchCorrManifold] create_axes: position grid extends beyond 3 km from its centre");
+    dpe_bcm *h = new dpe_bcm();
+    h->cfg = *cfg;
+    h->axes = true;
+    h->posExtent = ext[0] * 1.000001 + r2[0] / 2.0e7 + 1e-3;
+    h->velExtent = ext[1] * 1.000001 + 1e-6;
+    dpe_bcm::Axes *ax[2] = {&h->posAx, &h->velAx};
+    size_t nf = 0;
+    for (int m = 0; m < 2; ++m)
+        for (int c = 0; c < 4; ++c) {
+            ax[m]->dim[c] = ga[m]->dim[c];
+            ax[m]->v[c].assign(ga[m]->axis[c], ga[m]->axis[c] + ga[m]->dim[c]);
+            h->axOff[m][c] = (int)nf;
+            nf += (size_t)ga[m]->dim[c] + (c == 3 ? kAxT : 0);
+        }
+    if (donor) {
+        DPE_REQUIRE(donor->axes && !donor->axesBorrowed, "[BatchCorrManifold] create: the grids to share are not these grids");
+        h->axes_d = donor->axes_d;
+        h->axesBorrowed = true;
+    } else {
+        std::vector<float> f(nf, 0.f);
+        for (int m = 0; m < 2; ++m)
+            for (int c = 0; c < 4; ++c)
+                for (int i = 0; i < ax[m]->dim[c]; ++i) f[(size_t)h->axOff[m][c] + i] = (float)ax[m]->v[c][i];
+        h->axes_d = dev_alloc<float>(nf);
+        if (!h->axes_d) {
+            set_error("[BatchCorrManifold] create_axes: device allocation failed");
+            dpe_bcm_destroy(h);
+            return -1;
+        }
+        if (hipMemcpy(h->axes_d, f.data(), sizeof(float) * nf, hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("[BatchCorrManifold] create_axes: axes upload failed");
+            dpe_bcm_destroy(h);
+            return -1;
+        }
     }
-    // dynamic LDS above 64 KB needs the opt-in attribute
-    allow_big_lds<0, true, true>();  allow_big_lds<1, true, true>();  allow_big_lds<2, true, true>();
-    allow_big_lds<0, false, true>(); allow_big_lds<1, false, true>(); allow_big_lds<2, false, true>();
-    allow_big_lds<0, true, false>();  allow_big_lds<1, true, false>();  allow_big_lds<2, true, false>();
-    allow_big_lds<0, false, false>(); allow_big_lds<1, false, false>(); allow_big_lds<2, false, false>();
-    if (h->refPair &&
-        hipHostMalloc((void **)&h->refBank_h, W * K * (size_t)(2 * cfg->lagHalfWidth + 1) * sizeof(float2), hipHostMallocDefault) != hipSuccess) {
-        set_error("[BatchCorrManifold] create: host allocation failed");
-        dpe_bcm_destroy(h);
-        return -1;
-    }
-    h->oob_h = h->keys_h + 2 * W;
-    for (size_t i = 0; i < 4 * W + 8; ++i) h->keys_h[i] = 0ull;
-    h->pollAllowed = getenv("DPE_BCM_NO_POLL") == nullptr;
-#ifdef DPE_EXPERIMENTS
-    if (const char *e = getenv("DPE_BCM_SPLIT")) h->splitForce = atoi(e) > 0 && atoi(e) <= (int)dpe_bcm::kMaxSplit ? atoi(e) : 0;
-#endif
-    h->sv_h = h->svBase_h;
-    const auto finish = [&]() -> int {   // a failure from here on must not leak the handle
-        for (hipEvent_t &e : h->stagingFree) DPE_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        DPE_CHECK_HIP(hipMemset(h->keys_d, 0, 8 * W * sizeof(unsigned long long)));
-        h->done_d = dev_alloc<unsigned int>(1);
-        DPE_REQUIRE(h->done_d, "[BatchCorrManifold] create: device allocation failed");
-        DPE_CHECK_HIP(hipMemset(h->done_d, 0, sizeof(unsigned int)));
-        DPE_CHECK_HIP(hipHostGetDevicePointer((void **)&h->keys_hd, h->keys_h, 0));
-        DPE_CHECK_HIP(hipHostGetDevicePointer((void **)&h->svBase_hd, h->svBase_h, 0));
-        DPE_CHECK_HIP(hipHostGetDevicePointer((void **)&h->devWin_hd, h->devWin_h, 0));
-        return 0;
-    };
-    if (finish()) {
-        dpe_bcm_destroy(h);
-        return -1;
-    }
-    h->win_h.resize(W);
-    *out = h;
-    return 0;
+    allow_big_lds_axes<0>(); allow_big_lds_axes<1>(); allow_big_lds_axes<2>();
+    return bcm_finish_create(h, cfg, out);
+}
+
+int dpe_bcm_create_axes(const dpe_bcm_config *cfg, const dpe_grid_axes *pos, const dpe_grid_axes *vel, dpe_bcm **out)
+{
+    return dpe_bcm_create_axes_sharing(cfg, pos, vel, nullptr, out);
 }
 
 int dpe_bcm_destroy(dpe_bcm *h)
@@ -1021,6 +1201,9 @@ int dpe_bcm_destroy(dpe_bcm *h)
     if (!h) return 0;
     if (h->ownerDetach) h->ownerDetach(h->owner, 1);
     if (h->gridsBorrowed) h->posGrid_d = h->velGrid_d = nullptr;
+    if (h->axesBorrowed) h->axes_d = nullptr;
+    (void)hipFree(h->axes_d);
+    (void)hipFree(h->posAx64_d); (void)hipFree(h->velAx64_d);
     void *bufs[] = {h->posGrid64_d, h->velGrid64_d, h->posGrid_d, h->velGrid_d, h->posScores_d, h->velScores_d, h->sv_d, h->keys_d, h->wsum_d, h->done_d, h->refPatched_d};
     for (void *b : bufs) (void)hipFree(b);
     if (h->svBase_h) (void)hipHostFree(h->svBase_h);
@@ -1104,8 +1287,15 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
         }
     }
     h->lastW = nWindows;
-    h->lastSplit[0] = scan_split(h->cfg.posGridSize, nWindows, h->splitForce);
-    h->lastSplit[1] = scan_split(h->cfg.velGridSize, nWindows, h->splitForce);
+    long long axTiles[2] = {0, 0};
+    AxesLaunch ax{};
+    if (h->axes) {   // (scan_split sizes the launch in 1024-point tiles; an axes tile is 256 rows x one chunk of up to kAxT slots,
+                     //  up to 4096 point evaluations, so this gives a quarter of the blocks per evaluation of the point-list scan)
+        ax.sp = axes_side(h, 0, &axTiles[0]);
+        ax.sv = axes_side(h, 1, &axTiles[1]);
+    }
+    h->lastSplit[0] = scan_split(h->axes ? axTiles[0] * kPtsPerBlock : h->cfg.posGridSize, nWindows, h->splitForce);
+    h->lastSplit[1] = scan_split(h->axes ? axTiles[1] * kPtsPerBlock : h->cfg.velGridSize, nWindows, h->splitForce);
     // Two key / counter sets alternate between Updates: this call reduces into set `cur` (zero since it
     // was cleared by the previous call's position scan, or by create) and clears the other one.
     // (h->cur only advances once the launch is enqueued: a call that fails earlier must not skip a clearing)
@@ -1162,7 +1352,17 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
     // the kernel's last block writes keys and counts into the pinned host mirror: dpe_bcm_results only
     // has to synchronise
     h->prof.begin(0, stream);
-    launch_scan(!posInside, !velInside, h->cfg.weightedMean != 0, h->compact, a);
+    if (h->axes) {
+        ax.a = a;
+        ax.a.lds = (size_t)nChan * (nLag > nBin ? nLag : nBin) * 16 + kAxStageBytes;
+        ax.sp.bank = a.sp.bank; ax.sp.sv = a.sp.sv; ax.sp.scores = a.sp.scores; ax.sp.wsum = a.sp.wsum;
+        ax.sp.pitch = a.sp.pitch; ax.sp.nEnt = a.sp.nEnt; ax.sp.split = a.sp.split;
+        ax.sv.bank = a.sv.bank; ax.sv.sv = a.sv.sv; ax.sv.scores = a.sv.scores; ax.sv.wsum = a.sv.wsum;
+        ax.sv.pitch = a.sv.pitch; ax.sv.nEnt = a.sv.nEnt; ax.sv.split = a.sv.split;
+        launch_axes(!posInside, !velInside, h->cfg.weightedMean != 0, ax);
+    } else {
+        launch_scan(!posInside, !velInside, h->cfg.weightedMean != 0, h->compact, a);
+    }
     h->prof.end(0, stream);
     const bool captured = h->graphs.capturing;
     DPE_REQUIRE(h->graphs.end(stream) == 0, "[BatchCorrManifold] Update: hipGraph instantiate/launch failed");
@@ -1270,7 +1470,18 @@ int dpe_bcm_hook_get(dpe_bcm *h, dpe_bcm_hook *out)
     using namespace dpe;
     DPE_REQUIRE(h && out, "[BatchCorrManifold] hook: null argument");
     const size_t W = h->cfg.maxWindows, maxK = h->cfg.maxChannels;
-    if (!h->posGrid64_d) {
+    if (h->axes && !h->posAx64_d) {   // the global axes in fp64 (a few KB): the measurement kernel decodes its index from them
+        dpe_bcm::Axes *ax[2] = {&h->posAx, &h->velAx};
+        double **dst[2] = {&h->posAx64_d, &h->velAx64_d};
+        for (int m = 0; m < 2; ++m) {
+            std::vector<double> v;
+            for (int c = 0; c < 4; ++c) v.insert(v.end(), ax[m]->v[c].begin(), ax[m]->v[c].end());
+            *dst[m] = dev_alloc<double>(v.size());
+            DPE_REQUIRE(*dst[m], "[BatchCorrManifold] hook: axes allocation failed");
+            DPE_CHECK_HIP(hipMemcpy(*dst[m], v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice));
+        }
+    }
+    if (!h->axes && !h->posGrid64_d) {
         h->posGrid64_d = dev_alloc<double>(h->posGrid_h.size());
         h->velGrid64_d = dev_alloc<double>(h->velGrid_h.size());
         DPE_REQUIRE(h->posGrid64_d && h->velGrid64_d, "[BatchCorrManifold] hook: fp64 grid allocation failed");
@@ -1284,6 +1495,12 @@ int dpe_bcm_hook_get(dpe_bcm *h, dpe_bcm_hook *out)
     out->keys_d[1] = h->keys_d + 4 * W;
     out->posGrid64_d = h->posGrid64_d;
     out->velGrid64_d = h->velGrid64_d;
+    out->posAx64_d = h->posAx64_d;
+    out->velAx64_d = h->velAx64_d;
+    for (int c = 0; c < 4; ++c) {
+        out->posDim[c] = h->axes ? h->posAx.dim[c] : 0;
+        out->velDim[c] = h->axes ? h->velAx.dim[c] : 0;
+    }
     out->posG = h->cfg.posGridSize; out->velG = h->cfg.velGridSize;
     out->posOffset = h->cfg.posGridIndexOffset; out->velOffset = h->cfg.velGridIndexOffset;
     out->fs = h->cfg.samplingFrequency; out->Cf = (double)h->cfg.numFFTPoints;
@@ -1328,6 +1545,23 @@ static void make_meas(const dpe_bcm_window &win, const double *p, const double *
     z[5] = R[3] * v[0] + R[4] * v[1] + R[5] * v[2] + c[5];
     z[6] = R[6] * v[0] + R[7] * v[1] + R[8] * v[2] + c[6];
     z[7] = v[3] + c[7];
+}
+
+// Point `index` (global) of manifold m: a row of the point list, or decoded from the axes ((ix dimY + iy) dimZ + iz) dimT + it
+static const double *grid_point(const dpe_bcm *h, int m, int64_t index, double tmp[4])
+{
+    if (!h->axes) return (m ? h->velGrid_h.data() : h->posGrid_h.data()) + 4 * (index - (m ? h->cfg.velGridIndexOffset : h->cfg.posGridIndexOffset));
+    const dpe_bcm::Axes &ax = m ? h->velAx : h->posAx;
+    for (int c = 3; c >= 0; --c) {
+        tmp[c] = ax.v[c][(size_t)(index % ax.dim[c])];
+        index /= ax.dim[c];
+    }
+    return tmp;
+}
+
+static int64_t axes_size(const dpe_bcm::Axes &ax)
+{
+    return (int64_t)ax.dim[0] * ax.dim[1] * ax.dim[2] * ax.dim[3];
 }
 
 static void decode_key(unsigned long long key, float *score, int64_t *index)
@@ -1408,7 +1642,8 @@ int dpe_bcm_results(dpe_bcm *h, dpe_bcm_result *results, dpe_stream_t stream)
         const int64_t pl = r.posIndex - h->cfg.posGridIndexOffset, vl = r.velIndex - h->cfg.velGridIndexOffset;
         DPE_REQUIRE(pl >= 0 && pl < h->cfg.posGridSize && vl >= 0 && vl < h->cfg.velGridSize,
                     "[BatchCorrManifold] results: arg-max index outside the local shard");
-        make_meas(h->win_h[w], h->posGrid_h.data() + 4 * pl, h->velGrid_h.data() + 4 * vl, r.zVal);
+        double pt[4], vt[4];
+        make_meas(h->win_h[w], grid_point(h, 0, r.posIndex, pt), grid_point(h, 1, r.velIndex, vt), r.zVal);
     }
     return 0;
 }
@@ -1483,7 +1718,12 @@ int dpe_bcm_results_from_keys(dpe_bcm *h, const uint64_t *keys_host, int32_t nWi
                               int64_t posGridGlobalSize, const double *velGridGlobal, int64_t velGridGlobalSize,
                               dpe_bcm_result *results)
 {
-    DPE_REQUIRE(h && keys_host && posGridGlobal && velGridGlobal && results, "[BatchCorrManifold] results_from_keys: null argument");
+    DPE_REQUIRE(h && keys_host && results && (posGridGlobal != nullptr) == (velGridGlobal != nullptr) && (posGridGlobal || h->axes),
+                "[BatchCorrManifold] results_from_keys: null argument (both global grids, or neither for a handle with grid axes)");
+    if (!posGridGlobal) {   // an axes handle decodes from its axes, which are the global ones
+        posGridGlobalSize = axes_size(h->posAx);
+        velGridGlobalSize = axes_size(h->velAx);
+    }
     DPE_REQUIRE(nWindows >= 1 && nWindows <= h->lastW, "[BatchCorrManifold] results_from_keys: bad nWindows");
     if (fetch_device_frame(h)) return -1;   // (the reduced keys came through a synchronising copy: the scan has finished)
     for (int w = 0; w < nWindows; ++w) {
@@ -1498,7 +1738,9 @@ int dpe_bcm_results_from_keys(dpe_bcm *h, const uint64_t *keys_host, int32_t nWi
         r.posOutOfWindow = r.velOutOfWindow = -1;
         for (int j = 0; j < 8; ++j) r.zValMean[j] = 0.0;   // needs the all-reduced weightedSums; see sharding.py
         for (int j = 0; j < 10; ++j) (&r.weightedSums[0][0])[j] = 0.0;
-        make_meas(h->win_h[w], posGridGlobal + 4 * r.posIndex, velGridGlobal + 4 * r.velIndex, r.zVal);
+        double pt[4], vt[4];
+        make_meas(h->win_h[w], posGridGlobal ? posGridGlobal + 4 * r.posIndex : grid_point(h, 0, r.posIndex, pt),
+                  velGridGlobal ? velGridGlobal + 4 * r.velIndex : grid_point(h, 1, r.velIndex, vt), r.zVal);
     }
     return 0;
 }

@@ -179,8 +179,10 @@ static int chm_dev_args(dpe_chm_dev *h, int mode, int meas, const double *xk1k1,
         a.keys = reinterpret_cast<const unsigned long long *>(keys);
         a.posGrid = h->hm.posGrid64_d; a.velGrid = h->hm.velGrid64_d;
         a.posG = h->hm.posG; a.velG = h->hm.velG; a.posOff = h->hm.posOffset; a.velOff = h->hm.velOffset;
+        a.posAx = h->hm.posAx64_d; a.velAx = h->hm.velAx64_d;
+        for (int c = 0; c < 4; ++c) { a.posDim[c] = h->hm.posDim[c]; a.velDim[c] = h->hm.velDim[c]; }
         if (h->comm) {   // the keys carry GLOBAL indices and have been reduced over the ranks: decode against the global grids
-            a.posGrid = h->gPos_d; a.velGrid = h->gVel_d;
+            a.posGrid = h->gPos_d; a.velGrid = h->gVel_d;   // (nullptr for grid axes: those are global already)
             a.posG = h->gPosG; a.velG = h->gVelG; a.posOff = 0; a.velOff = 0;
         }
         a.ring = h->ring_hd;
@@ -360,7 +362,17 @@ int dpe_chm_dev_set_shard(dpe_chm_dev *h, dpe_comm *comm, const double *posGridG
 {
     DPE_REQUIRE(h && !h->started, "[cuChanMgr] set_shard: before Start");
     DPE_REQUIRE(h->bcm && h->ring_h, "[cuChanMgr] set_shard: attach a BatchCorrManifold first (dpe_chm_dev_attach)");
-    DPE_REQUIRE(comm && posGridGlobal && velGridGlobal && posG >= 1 && velG >= 1, "[cuChanMgr] set_shard: bad arguments");
+    DPE_REQUIRE(comm && (posGridGlobal != nullptr) == (velGridGlobal != nullptr), "[cuChanMgr] set_shard: bad arguments");
+    if (!posGridGlobal) {   // a BatchCorrManifold with grid axes: the keys decode against its axes, which are the global ones
+        DPE_REQUIRE(h->hm.posAx64_d, "[cuChanMgr] set_shard: NULL global grids need a BatchCorrManifold made with grid axes (dpe_bcm_create_axes)");
+        (void)hipFree(h->gPos_d); (void)hipFree(h->gVel_d);
+        h->gPos_d = h->gVel_d = nullptr;
+        h->gPosG = (long long)h->hm.posDim[0] * h->hm.posDim[1] * h->hm.posDim[2] * h->hm.posDim[3];
+        h->gVelG = (long long)h->hm.velDim[0] * h->hm.velDim[1] * h->hm.velDim[2] * h->hm.velDim[3];
+        h->comm = comm;
+        return 0;
+    }
+    DPE_REQUIRE(posG >= 1 && velG >= 1 && !h->hm.posAx64_d, "[cuChanMgr] set_shard: bad arguments (a handle with grid axes takes NULL global grids)");
     // the shard this rank's scan covers must lie inside the global grids (its keys then decode to rows of them)
     DPE_REQUIRE(h->hm.posOffset >= 0 && h->hm.posOffset + h->hm.posG <= posG && h->hm.velOffset >= 0 && h->hm.velOffset + h->hm.velG <= velG,
                 "[cuChanMgr] set_shard: the attached BatchCorrManifold scans [%lld, %lld) / [%lld, %lld), outside the global grids (%lld, %lld)",

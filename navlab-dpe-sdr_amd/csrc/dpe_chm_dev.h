@@ -279,6 +279,17 @@ struct EkfDev {
     int coupled, pad;
     double Tc;
 };
+// Point `index` (global) of a tensor grid given by its axes (x [dim0], y [dim1], z [dim2], t [dim3] back to back)
+__device__ inline const double *axes_point(const double *ax, const int dim[4], long long index, double out[4])
+{
+    const double *a[4] = {ax, ax + dim[0], ax + dim[0] + dim[1], ax + dim[0] + dim[1] + dim[2]};
+    for (int c = 3; c >= 0; --c) {
+        out[c] = a[c][index % dim[c]];
+        index /= dim[c];
+    }
+    return out;
+}
+
 struct ChmKArgs {
     ChmDevState *st;
     ChmPorts p;
@@ -289,6 +300,8 @@ struct ChmKArgs {
     int meas;
     const unsigned long long *keys; // {posKey, velKey, posOutOfWindow, velOutOfWindow} of the window just scanned
     const double *posGrid, *velGrid;
+    const double *posAx, *velAx;    // grid axes (x, y, z, t back to back) instead of point lists: the index is decoded from them
+    int posDim[4], velDim[4];
     long long posG, velG, posOff, velOff;
     dpe_fix_record *ring;           // pinned, device address
     int ringDepth;
@@ -688,7 +701,10 @@ __device__ static inline void chm_k1(const ChmKArgs &a)
             iv = (long long)(0xFFFFFFFFu - (unsigned)(kv & 0xFFFFFFFFull)) - a.velOff;
             if (kp == 0ull || ip < 0 || ip >= a.posG) { measBad = 4; ip = 0; }
             if (kv == 0ull || iv < 0 || iv >= a.velG) { measBad = 4; iv = 0; }
-            const double *g = a.posGrid + 4 * ip, *v = a.velGrid + 4 * iv, *R = a.p.enu2ecef, *cc = a.p.xkk1;
+            double gAx[4], vAx[4];   // (grid axes: the point decoded from its global index)
+            const double *g = a.posAx ? axes_point(a.posAx, a.posDim, ip + a.posOff, gAx) : a.posGrid + 4 * ip;
+            const double *v = a.velAx ? axes_point(a.velAx, a.velDim, iv + a.velOff, vAx) : a.velGrid + 4 * iv;
+            const double *R = a.p.enu2ecef, *cc = a.p.xkk1;
             {
 #pragma clang fp contract(off)   // (the host form's BCM_MakePosMeas / MakeVelMeas run without fused multiply-adds: the same doubles here)
                 z[0] = R[0] * g[0] + R[1] * g[1] + R[2] * g[2] + cc[0];   // :1990-1999

@@ -64,7 +64,8 @@ int dpe_pipe_destroy(dpe_pipe *p)
     return 0;
 }
 
-int dpe_pipe_create(const dpe_bcs_config *bcsCfg, const dpe_bcm_config *bcmCfg, int32_t inFlight, dpe_pipe **out)
+static int pipe_create(const dpe_bcs_config *bcsCfg, const dpe_bcm_config *bcmCfg, const dpe_grid_axes *pos, const dpe_grid_axes *vel,
+                       int32_t inFlight, dpe_pipe **out)
 {
     DPE_REQUIRE(bcsCfg && bcmCfg && out, "[Pipe] create: null argument");
     DPE_REQUIRE(inFlight >= 1 && inFlight <= 8, "[Pipe] create: inFlight %d not in 1..8", inFlight);
@@ -75,7 +76,9 @@ int dpe_pipe_create(const dpe_bcs_config *bcsCfg, const dpe_bcm_config *bcmCfg, 
     p->lanes.resize((size_t)inFlight);
     for (int i = 0; i < inFlight; ++i) {
         dpe_pipe::Lane &l = p->lanes[(size_t)i];
-        if (dpe_bcs_create(bcsCfg, &l.bcs) || dpe_bcm_create_sharing(bcmCfg, i ? p->lanes[0].bcm : nullptr, &l.bcm)) {
+        dpe_bcm *donor = i ? p->lanes[0].bcm : nullptr;
+        if (dpe_bcs_create(bcsCfg, &l.bcs) ||
+            (pos ? dpe_bcm_create_axes_sharing(bcmCfg, pos, vel, donor, &l.bcm) : dpe_bcm_create_sharing(bcmCfg, donor, &l.bcm))) {
             dpe_pipe_destroy(p);
             return -1;
         }
@@ -91,6 +94,18 @@ int dpe_pipe_create(const dpe_bcs_config *bcsCfg, const dpe_bcm_config *bcmCfg, 
     p->active = inFlight;
     *out = p;
     return 0;
+}
+
+int dpe_pipe_create(const dpe_bcs_config *bcsCfg, const dpe_bcm_config *bcmCfg, int32_t inFlight, dpe_pipe **out)
+{
+    return pipe_create(bcsCfg, bcmCfg, nullptr, nullptr, inFlight, out);
+}
+
+int dpe_pipe_create_axes(const dpe_bcs_config *bcsCfg, const dpe_bcm_config *bcmCfg, const dpe_grid_axes *pos, const dpe_grid_axes *vel,
+                         int32_t inFlight, dpe_pipe **out)
+{
+    DPE_REQUIRE(pos && vel, "[Pipe] create_axes: null axes");
+    return pipe_create(bcsCfg, bcmCfg, pos, vel, inFlight, out);
 }
 
 int dpe_pipe_in_flight(const dpe_pipe *p)

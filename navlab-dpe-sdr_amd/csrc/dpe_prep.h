@@ -161,6 +161,10 @@ struct dpe_bcm_hook {
     dpe::BcmDevWin *devWin_hd;                 // pinned window frame (device address) the NEXT Update's results will be decoded with
     const unsigned long long *keys_d[2];       // the two alternating key sets: {pos, vel} keys then {pos, vel} out-of-window counts per window
     const double *posGrid64_d, *velGrid64_d;   // fp64 copies of the local grids (made by the first call of dpe_bcm_hook_get)
+    // a handle with grid axes (dpe_bcm_create_axes) has no point list: posGrid64_d / velGrid64_d are nullptr and the GLOBAL axes are
+    // here instead (fp64, x / y / z / t back to back at axOff), index ((ix dim[1] + iy) dim[2] + iz) dim[3] + it
+    const double *posAx64_d, *velAx64_d;
+    int posDim[4], velDim[4];
     long long posG, velG, posOffset, velOffset;
     double fs, Cf;
     int S, L, B, maxWindows, maxChannels;
@@ -169,6 +173,9 @@ struct dpe_bcm_hook {
 int dpe_bcm_hook_get(dpe_bcm *h, dpe_bcm_hook *out);
 // dpe_bcm_create for a further lane of a dpe_pipe (dpe_pipe.hip): the fp32 device grids are donor's (which must outlive the handle)
 int dpe_bcm_create_sharing(const dpe_bcm_config *cfg, dpe_bcm *donor, dpe_bcm **out);
+// the same for grids given by their axes (dpe_bcm_create_axes): the device copy of the axes is donor's
+int dpe_bcm_create_axes_sharing(const dpe_bcm_config *cfg, const dpe_grid_axes *pos, const dpe_grid_axes *vel, dpe_bcm *donor,
+                                dpe_bcm **out);
 // enable = 0: the device-parameter Updates of this handle leave keys and counts in device memory only (no ticket, no stores over the
 // host link at the end of the scan); dpe_bcm_results then fetches them with a copy.  Set by dpe_chm_dev_attach.
 int dpe_bcm_hook_set_publish(dpe_bcm *h, int enable);

@@ -19,7 +19,7 @@ EXPORTS = [
     "dpe_host_alloc_pinned", "dpe_host_free_pinned", "dpe_device_alloc", "dpe_device_free", "dpe_memcpy_h2d",
     "dpe_memcpy_d2h", "dpe_stream_create", "dpe_stream_destroy", "dpe_stream_synchronize",
     "dpe_bcs_create", "dpe_bcs_destroy", "dpe_bcs_update", "dpe_bcs_outputs", "dpe_bcs_read_info",
-    "dpe_bcs_export_dense", "dpe_bcm_create", "dpe_bcm_destroy", "dpe_bcm_update", "dpe_bcm_results",
+    "dpe_bcs_export_dense", "dpe_bcm_create", "dpe_bcm_create_axes", "dpe_bcm_destroy", "dpe_bcm_update", "dpe_bcm_results",
     "dpe_bcm_scores", "dpe_bcm_scores_pitch", "dpe_bcm_keys", "dpe_bcm_results_from_keys", "dpe_event_create", "dpe_event_record",
     "dpe_event_elapsed_ms", "dpe_event_destroy", "dpe_chm_create", "dpe_chm_destroy", "dpe_chm_start",
     "dpe_chm_update", "dpe_chm_outputs", "dpe_bcs_profile", "dpe_bcm_profile", "dpe_acq_create", "dpe_acq_destroy",
@@ -33,7 +33,7 @@ EXPORTS = [
     "dpe_chm_dev_create", "dpe_chm_dev_destroy", "dpe_chm_dev_attach", "dpe_chm_dev_ports", "dpe_chm_dev_start", "dpe_chm_dev_update",
     "dpe_chm_dev_step", "dpe_chm_dev_fix", "dpe_chm_dev_read", "dpe_bcs_update_prepared", "dpe_bcm_update_prepared", "dpe_bcs_set_dev_hint",
     "dpe_chm_dev_set_shard", "dpe_chm_dev_set_ekf",
-    "dpe_pipe_create", "dpe_pipe_destroy", "dpe_pipe_in_flight", "dpe_pipe_submit", "dpe_pipe_acquire", "dpe_pipe_mark_stage1",
+    "dpe_pipe_create", "dpe_pipe_create_axes", "dpe_pipe_destroy", "dpe_pipe_in_flight", "dpe_pipe_submit", "dpe_pipe_acquire", "dpe_pipe_mark_stage1",
     "dpe_pipe_commit", "dpe_pipe_lane", "dpe_pipe_set_in_flight", "dpe_pipe_lane_at", "dpe_pipe_results", "dpe_pipe_samples_consumed", "dpe_pipe_join", "dpe_pipe_synchronize",
 ]
 
@@ -137,6 +137,28 @@ def _ptr(x):
     if hasattr(x, "data_ptr"):
         return C.c_void_p(x.data_ptr())
     return C.c_void_p(int(x))
+
+
+def _grids(pos_grid, vel_grid, pos_index_offset, vel_index_offset):
+    """The two manifold grids as the C-ABI takes them: [G, 4] point lists, or GridAxes (whose slice sets size and index
+    offset).  Returns (pos, vel, pos_offset, vel_offset, axes?)."""
+    from .grid_axes import GridAxes
+    pa, va = isinstance(pos_grid, GridAxes), isinstance(vel_grid, GridAxes)
+    if pa != va:
+        raise DpeError("[BatchCorrManifold] grids: give both manifolds as GridAxes or both as point lists")
+    if pa:
+        if pos_index_offset or vel_index_offset:
+            raise DpeError("[BatchCorrManifold] grids: a GridAxes slice carries its own index offset (GridAxes.shard)")
+        return pos_grid, vel_grid, pos_grid.begin, vel_grid.begin, True
+    return (np.ascontiguousarray(pos_grid, dtype=np.float64), np.ascontiguousarray(vel_grid, dtype=np.float64),
+            int(pos_index_offset), int(vel_index_offset), False)
+
+
+def _bcm_config(S, L, B, LPower, W, K, Cf, fs, pos, vel, pos_off, vel_off, axes, write_scores, weighted_mean, reference_pair):
+    dp = C.POINTER(C.c_double)
+    return BcmConfig(S, L, B, LPower, W, K, Cf, fs, None if axes else pos.ctypes.data_as(dp), None if axes else vel.ctypes.data_as(dp),
+                     pos.shape[0], vel.shape[0], pos_off, vel_off, 1 if write_scores else 0, 1 if weighted_mean else 0,
+                     1 if reference_pair else 0, 0)
 
 
 STREAM_NONE = "none"      # Pipe.submit / acquire: the samples are already resident (DPE_STREAM_NONE: no cross-stream wait)
@@ -406,8 +428,9 @@ class BatchCorrManifold:
                  lag_half_width=8, bin_half_width=48, max_windows=1, max_channels=8, write_scores=True,
                  pos_index_offset=0, vel_index_offset=0, weighted_mean=False, reference_pair=False):
         self.fs, self.S, self.C = float(SamplingFrequency), int(samples_per_window), int(NumFFTPoints)
-        self.pos_grid = np.ascontiguousarray(pos_grid, dtype=np.float64)
-        self.vel_grid = np.ascontiguousarray(vel_grid, dtype=np.float64)
+        # [G, 4] point lists, or GridAxes (grid_axes.py): then the handle never holds a per-point copy of the grid
+        self.pos_grid, self.vel_grid, pos_index_offset, vel_index_offset, self.axes = _grids(pos_grid, vel_grid, pos_index_offset,
+                                                                                            vel_index_offset)
         self.LPower, self.L, self.B = int(LPower), int(lag_half_width), int(bin_half_width)
         self.max_windows, self.max_channels = int(max_windows), int(max_channels)
         self.write_scores = bool(write_scores)
@@ -420,12 +443,13 @@ class BatchCorrManifold:
     def Start(self):
         if self.Started:
             return 0
-        cfg = BcmConfig(self.S, self.L, self.B, self.LPower, self.max_windows, self.max_channels, self.C, self.fs,
-                        self.pos_grid.ctypes.data_as(C.POINTER(C.c_double)),
-                        self.vel_grid.ctypes.data_as(C.POINTER(C.c_double)),
-                        self.pos_grid.shape[0], self.vel_grid.shape[0], self.pos_off, self.vel_off,
-                        1 if self.write_scores else 0, 1 if self.weighted_mean else 0, 1 if self.reference_pair else 0, 0)
-        _check(lib().dpe_bcm_create(C.byref(cfg), C.byref(self._h)))
+        cfg = _bcm_config(self.S, self.L, self.B, self.LPower, self.max_windows, self.max_channels, self.C, self.fs, self.pos_grid,
+                          self.vel_grid, self.pos_off, self.vel_off, self.axes, self.write_scores, self.weighted_mean, self.reference_pair)
+        if self.axes:
+            pa, va = self.pos_grid.c_struct(), self.vel_grid.c_struct()
+            _check(lib().dpe_bcm_create_axes(C.byref(cfg), C.byref(pa), C.byref(va), C.byref(self._h)))
+        else:
+            _check(lib().dpe_bcm_create(C.byref(cfg), C.byref(self._h)))
         self._bind_outputs()
         return 0
 
@@ -486,15 +510,23 @@ class BatchCorrManifold:
         _check(lib().dpe_bcm_exchange_keys(self._h, comm._h, keys.ctypes.data_as(C.POINTER(C.c_uint64)), _stream(stream)))
         return keys
 
-    def results_from_keys(self, keys_host, pos_grid_global, vel_grid_global):
+    def results_from_keys(self, keys_host, pos_grid_global=None, vel_grid_global=None):
+        """Measurement from reduced keys.  The global grids may be None (or GridAxes) for a handle made from GridAxes: it then
+        decodes from its own axes, which are the global ones."""
+        from .grid_axes import GridAxes
         keys_host = np.ascontiguousarray(keys_host, dtype=np.uint64)
         W = keys_host.shape[0]
-        pg = np.ascontiguousarray(pos_grid_global, dtype=np.float64)
-        vg = np.ascontiguousarray(vel_grid_global, dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        if pos_grid_global is None or isinstance(pos_grid_global, GridAxes):
+            if not (vel_grid_global is None or isinstance(vel_grid_global, GridAxes)):
+                raise DpeError("[BatchCorrManifold] results_from_keys: both global grids as point lists, or neither")
+            args = (None, C.c_int64(0), None, C.c_int64(0))
+        else:
+            pg = np.ascontiguousarray(pos_grid_global, dtype=np.float64)
+            vg = np.ascontiguousarray(vel_grid_global, dtype=np.float64)
+            args = (pg.ctypes.data_as(dp), C.c_int64(pg.shape[0]), vg.ctypes.data_as(dp), C.c_int64(vg.shape[0]))
         res = (BcmResult * W)()
-        _check(lib().dpe_bcm_results_from_keys(self._h, keys_host.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_int32(W),
-                                               pg.ctypes.data_as(C.POINTER(C.c_double)), C.c_int64(pg.shape[0]),
-                                               vg.ctypes.data_as(C.POINTER(C.c_double)), C.c_int64(vg.shape[0]), res))
+        _check(lib().dpe_bcm_results_from_keys(self._h, keys_host.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_int32(W), *args, res))
         return [dict(zVal=np.array(r.zVal), posIndex=r.posIndex, velIndex=r.velIndex, posScore=r.posScore,
                      velScore=r.velScore) for r in res]
 
@@ -569,19 +601,20 @@ class Pipe:
         self.L, self.B = int(lag_half_width), int(bin_half_width)
         self.max_windows, self.max_channels = int(max_windows), int(max_channels)
         self.bcm_max_windows = int(bcm_max_windows) if bcm_max_windows else self.max_windows   # (stage 1 sharded by window: the scan sees all)
-        self.pos_grid = np.ascontiguousarray(pos_grid, dtype=np.float64)
-        self.vel_grid = np.ascontiguousarray(vel_grid, dtype=np.float64)
+        self.pos_grid, self.vel_grid, po, vo, axes = _grids(pos_grid, vel_grid, pos_index_offset, vel_index_offset)
         self._bcm_kw = dict(LPower=int(LPower), lag_half_width=self.L, bin_half_width=self.B, max_windows=self.bcm_max_windows,
-                            max_channels=self.max_channels, write_scores=bool(write_scores), pos_index_offset=int(pos_index_offset),
-                            vel_index_offset=int(vel_index_offset), weighted_mean=bool(weighted_mean))
+                            max_channels=self.max_channels, write_scores=bool(write_scores),
+                            pos_index_offset=0 if axes else po, vel_index_offset=0 if axes else vo, weighted_mean=bool(weighted_mean))
         bcs = BcsConfig(self.S, self.L, self.B, self.max_windows, self.max_channels, 0, self.fs)
-        dp = C.POINTER(C.c_double)
-        bcm = BcmConfig(self.S, self.L, self.B, int(LPower), self.bcm_max_windows, self.max_channels, carr_fft_len(self.S), self.fs,
-                        self.pos_grid.ctypes.data_as(dp), self.vel_grid.ctypes.data_as(dp), self.pos_grid.shape[0],
-                        self.vel_grid.shape[0], int(pos_index_offset), int(vel_index_offset), 1 if write_scores else 0,
-                        1 if weighted_mean else 0, 0, 0)
+        bcm = _bcm_config(self.S, self.L, self.B, int(LPower), self.bcm_max_windows, self.max_channels, carr_fft_len(self.S), self.fs,
+                          self.pos_grid, self.vel_grid, po, vo, axes, write_scores, weighted_mean, False)
         self._h = C.c_void_p(None)
-        _check(lib().dpe_pipe_create(C.byref(bcs), C.byref(bcm), C.c_int32(in_flight), C.byref(self._h)))
+        if axes:
+            pa, va = self.pos_grid.c_struct(), self.vel_grid.c_struct()
+            _check(lib().dpe_pipe_create_axes(C.byref(bcs), C.byref(bcm), C.byref(pa), C.byref(va), C.c_int32(in_flight),
+                                              C.byref(self._h)))
+        else:
+            _check(lib().dpe_pipe_create(C.byref(bcs), C.byref(bcm), C.c_int32(in_flight), C.byref(self._h)))
         self.lanes = self.in_flight = int(in_flight)
         self._faces = {}      # handle pair -> (BatchCorrScores, BatchCorrManifold) faces of a lane
         self._nw = {}         # ticket -> (windows, channels) of the batches the lanes hold
@@ -795,7 +828,14 @@ class ChanMgrDev:
 
     def set_shard(self, comm, pos_grid_global, vel_grid_global):
         """dpe_chm_dev_set_shard: the attached BatchCorrManifold scans a shard; step() all-reduces the keys over `comm` before the
-        measurement kernel, which decodes them against these GLOBAL grids ([G, 4] each)."""
+        measurement kernel, which decodes them against these GLOBAL grids ([G, 4] each; None, or GridAxes, for a BatchCorrManifold
+        made from GridAxes: its axes are the global ones)."""
+        from .grid_axes import GridAxes
+        if pos_grid_global is None or isinstance(pos_grid_global, GridAxes):
+            if not (vel_grid_global is None or isinstance(vel_grid_global, GridAxes)):
+                raise DpeError("[cuChanMgr] set_shard: both global grids as point lists, or neither")
+            _check(lib().dpe_chm_dev_set_shard(self._h, comm._h, None, C.c_int64(0), None, C.c_int64(0)))
+            return
         p = np.ascontiguousarray(pos_grid_global, dtype=np.float64)
         v = np.ascontiguousarray(vel_grid_global, dtype=np.float64)
         _check(lib().dpe_chm_dev_set_shard(self._h, comm._h, p.ctypes.data_as(C.c_void_p), C.c_int64(p.shape[0]),

@@ -6,6 +6,8 @@
 //   dpe_flow --samples f.dat --handoff handoff.csv --out X.csv [--fs 2.5e6] [--T 0.02] [--iters 3000]
 //            [--grid-dim 25] [--spacing 1.0] [--grid-type 0|2] [--load-grid rngrid.csv] [--lpower 1]
 //            [--init-delta dx dy dz dt]
+//            [--grid-axes]                       the built grids go to the engine as their axes (dpe_bcm_create_axes), not as
+//                                                point lists (BatchCorrManifold's GridAxes parameter; not with --load-grid)
 //            [--device-loop [--fix-lag n]]       cuChanMgr on the device (dpe_chm_dev_*): measurement, pass-through and channel
 //                                                update in one kernel behind the scan, nothing read back per window; the flow
 //                                                thread enqueues up to n (default 8) windows ahead of the fixes it has collected
@@ -35,7 +37,7 @@
 static int run_device_loop(const std::string &samples, const std::string &handoff, const std::string &out, const std::string &rinex,
                            const std::string &loadGrid, double fs, double T, int iters, int gridDim, int gridType, int lpower, float spacing,
                            const float *delta, int L, int B, int fixLag, int device, bool timing, int ranks, int rank,
-                           const std::string &rendezvous, const std::string &commName, bool enableEkf)
+                           const std::string &rendezvous, const std::string &commName, bool enableEkf, bool gridAxes)
 {
     dsp::Flow flow;
     auto *bcs = new dsp::BatchCorrScores;
@@ -62,6 +64,7 @@ static int run_device_loop(const std::string &samples, const std::string &handof
     CHECK(flow.SetModParam("BatchCorrManifold", "VelGridDimSize", gridDim));
     CHECK(flow.SetModParam("BatchCorrManifold", "GridDimSpacing", spacing));
     CHECK(flow.SetModParam("BatchCorrManifold", "GridType", gridType));
+    CHECK(flow.SetModParam("BatchCorrManifold", "GridAxes", gridAxes));
     CHECK(flow.SetModParam("BatchCorrManifold", "LPower", lpower));
     CHECK(flow.SetModParam("BatchCorrManifold", "DeviceLoop", true));
     CHECK(flow.SetModParam("BatchCorrScores", "DeviceLoop", true));
@@ -143,7 +146,7 @@ int main(int argc, char **argv)
     int ranks = 1, rank = 0, device = -1;
     double fs = 2.5e6, T = 0.02;
     int iters = 3000, gridDim = 25, gridType = 0, lpower = 1;
-    bool useGraph = false, timing = false, enableEkf = false, shardStage1 = false, deviceLoop = false;
+    bool useGraph = false, timing = false, enableEkf = false, shardStage1 = false, deviceLoop = false, gridAxes = false;
     int fixLag = 8;
     float spacing = 1.0f, delta[4] = {0, 0, 0, 0};
     for (int i = 1; i < argc; ++i) {
@@ -201,6 +204,7 @@ int main(int argc, char **argv)
         else if (a == "--timing") { timing = true; }
         else if (a == "--ekf") { enableEkf = true; }
         else if (a == "--device-loop") { deviceLoop = true; }
+        else if (a == "--grid-axes") { gridAxes = true; }
         else if (a == "--fix-lag") { fixLag = std::atoi(next()); ++i; }
         else if (a == "--init-delta") { next(4); for (int j = 0; j < 4; ++j) delta[j] = (float)std::atof(argv[i + 1 + j]); i += 4; }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
@@ -233,7 +237,7 @@ int main(int argc, char **argv)
         return 2;
     }
     if (deviceLoop) return run_device_loop(samples, handoff, out, rinex, loadGrid, fs, T, iters, gridDim, gridType, lpower, spacing, delta, L, B,
-                                           fixLag, device, timing, ranks, rank, rendezvous, commName, enableEkf);
+                                           fixLag, device, timing, ranks, rank, rendezvous, commName, enableEkf, gridAxes);
     dsp::Flow flow;                                             // dpeflow.cpp:55-62
     flow.Add(new dsp::DPInit);
     flow.Add(new dsp::SampleBlock);
@@ -259,6 +263,7 @@ int main(int argc, char **argv)
     CHECK(flow.SetModParam("BatchCorrManifold", "VelGridDimSize", gridDim));
     CHECK(flow.SetModParam("BatchCorrManifold", "GridDimSpacing", spacing));
     CHECK(flow.SetModParam("BatchCorrManifold", "GridType", gridType));
+    CHECK(flow.SetModParam("BatchCorrManifold", "GridAxes", gridAxes));
     CHECK(flow.SetModParam("BatchCorrManifold", "LPower", lpower));
     CHECK(flow.SetModParam("cuChanMgr", "DopplerSign", 1));
     CHECK(flow.SetModParam("cuEKF", "EnableEKF", enableEkf));   // dpeflow.cpp:90 ships false

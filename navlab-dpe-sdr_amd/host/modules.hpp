@@ -479,6 +479,8 @@ class BatchCorrManifold : public Module {
         InsertParam("GridLogFileName", gridLog, CHAR_t, sizeof(gridLog), 0);
         InsertParam("LoadPosGrid", &loadPosGrid, BOOL_t, sizeof(bool), sizeof(bool));
         InsertParam("LoadPosGridFilename", loadPosGridFilename, CHAR_t, sizeof(loadPosGridFilename), 0);
+        // true (and LoadPosGrid false): the built grids go to the engine as their four axes (dpe_bcm_create_axes), no point list
+        InsertParam("GridAxes", &gridAxes, BOOL_t, sizeof(bool), sizeof(bool));
         InsertParam("UseGraph", &useGraph, BOOL_t, sizeof(bool), sizeof(bool));
         InsertParam("ReferencePair", &referencePair, BOOL_t, sizeof(bool), sizeof(bool));   // dpe_bcm_config.referencePair
         InsertParam("DeviceLoop", &deviceLoop, BOOL_t, sizeof(bool), sizeof(bool));         // coefficient blocks from cuChanMgrDev, no wait for the fix
@@ -500,8 +502,19 @@ class BatchCorrManifold : public Module {
         if (!inputs[0] || !inputs[1] || !inputs[6] || !inputs[7] || !inputs[11]) DPE_MOD_FAIL("Start: inputs not connected");
         const int dimP[4] = {posDim, posDim, posDim, posDim}, dimV[4] = {velDim, velDim, velDim, velDim};   // :2328-2329
         const double sp[4] = {spacing, spacing, spacing, spacing};                                         // :2332
-        utils::build_grid((utils::ManifoldGridTypes)gridType, dimP, sp, posGrid, &timeGrid, false);
-        utils::build_grid((utils::ManifoldGridTypes)gridType, dimV, sp, velGrid, nullptr, true);
+        axes = gridAxes && !loadPosGrid;   // (a loaded CSV grid keeps the point-list path for both manifolds)
+        if (axes) {
+            posGrid.clear(); velGrid.clear();
+            for (int c = 0; c < 4; ++c) {
+                posAx[c].resize(dimP[c]); velAx[c].resize(dimV[c]);
+                for (int i = 0; i < dimP[c]; ++i) posAx[c][i] = utils::grid_axis((utils::ManifoldGridTypes)gridType, i, dimP[c], sp[c]);
+                for (int i = 0; i < dimV[c]; ++i) velAx[c][i] = utils::grid_axis(utils::Uniform, i, dimV[c], sp[c]);   // (:293-307)
+            }
+            timeGrid = posAx[3];
+        } else {
+            utils::build_grid((utils::ManifoldGridTypes)gridType, dimP, sp, posGrid, &timeGrid, false);
+            utils::build_grid((utils::ManifoldGridTypes)gridType, dimV, sp, velGrid, nullptr, true);
+        }
         if (loadPosGrid) {                                                                                 // :2422-2448
             const int r = utils::load_grid_csv(loadPosGridFilename, (long long)posGrid.size() / 4, posGrid);
             if (r == -1) DPE_MOD_FAIL("Open loadGridFile failed: " << loadPosGridFilename);
@@ -513,8 +526,18 @@ class BatchCorrManifold : public Module {
         cfg.numFFTPoints = *(int *)inputs[11]->Data;
         cfg.lagHalfWidth = inputs[0]->AuxValue; cfg.binHalfWidth = inputs[1]->AuxValue;
         cfg.lPower = LPower; cfg.maxWindows = 1; cfg.maxChannels = DPE_MAX_CHAN;
-        cfg.posGrid = posGrid.data(); cfg.velGrid = velGrid.data();
-        cfg.posGridSize = (int64_t)posGrid.size() / 4; cfg.velGridSize = (int64_t)velGrid.size() / 4;
+        dpe_grid_axes pa = {}, va = {};
+        if (axes) {
+            for (int c = 0; c < 4; ++c) {
+                pa.dim[c] = dimP[c]; pa.axis[c] = posAx[c].data();
+                va.dim[c] = dimV[c]; va.axis[c] = velAx[c].data();
+            }
+            cfg.posGridSize = (int64_t)dimP[0] * dimP[1] * dimP[2] * dimP[3];
+            cfg.velGridSize = (int64_t)dimV[0] * dimV[1] * dimV[2] * dimV[3];
+        } else {
+            cfg.posGrid = posGrid.data(); cfg.velGrid = velGrid.data();
+            cfg.posGridSize = (int64_t)posGrid.size() / 4; cfg.velGridSize = (int64_t)velGrid.size() / 4;
+        }
         if (shardCount > 1 || comm_requested()) {
             if (shardRank < 0 || shardRank >= shardCount) DPE_MOD_FAIL("Start: ShardRank " << shardRank << " not in [0, " << shardCount << ")");
             // contiguous index ranges, remainder to the first ranks (keeps the reference's index order, "t fastest")
@@ -526,13 +549,13 @@ class BatchCorrManifold : public Module {
             int64_t pb, pe, vb, ve;
             range(cfg.posGridSize, pb, pe);
             range(cfg.velGridSize, vb, ve);
-            cfg.posGrid = posGrid.data() + 4 * pb; cfg.posGridSize = pe - pb; cfg.posGridIndexOffset = pb;
-            cfg.velGrid = velGrid.data() + 4 * vb; cfg.velGridSize = ve - vb; cfg.velGridIndexOffset = vb;
+            cfg.posGrid = axes ? nullptr : posGrid.data() + 4 * pb; cfg.posGridSize = pe - pb; cfg.posGridIndexOffset = pb;
+            cfg.velGrid = axes ? nullptr : velGrid.data() + 4 * vb; cfg.velGridSize = ve - vb; cfg.velGridIndexOffset = vb;
             if (dpe_comm_create(shardRank, shardCount, commRendezvous, commBackend, &comm)) DPE_MOD_FAIL("Start: " << dpe_last_error());
         }
         cfg.writeScores = 1;
         cfg.referencePair = referencePair ? 1 : 0;
-        if (dpe_bcm_create(&cfg, &h)) return -1;
+        if (axes ? dpe_bcm_create_axes(&cfg, &pa, &va, &h) : dpe_bcm_create(&cfg, &h)) return -1;
         dpe_bcm_set_graph(h, useGraph ? 1 : 0);
         const float *ps, *vs;
         dpe_bcm_scores(h, &ps, &vs);
@@ -574,8 +597,9 @@ class BatchCorrManifold : public Module {
             // sharded grid: every rank ends with the same reduced keys and decodes the same global ML point
             uint64_t keys[2];
             if (dpe_bcm_exchange_keys(h, comm, keys, st)) DPE_MOD_FAIL("Update: " << dpe_last_error());
-            if (dpe_bcm_results_from_keys(h, keys, 1, posGrid.data(), (int64_t)posGrid.size() / 4, velGrid.data(),
-                                          (int64_t)velGrid.size() / 4, &r)) DPE_MOD_FAIL("Update: " << dpe_last_error());
+            if (dpe_bcm_results_from_keys(h, keys, 1, axes ? nullptr : posGrid.data(), (int64_t)posGrid.size() / 4,
+                                          axes ? nullptr : velGrid.data(), (int64_t)velGrid.size() / 4, &r))
+                DPE_MOD_FAIL("Update: " << dpe_last_error());
         } else if (dpe_bcm_results(h, &r, st)) return -1;                                                  // synchronises, :2606-2632
         std::memcpy(zVal, r.zVal, sizeof(zVal));
         last = r;
@@ -597,10 +621,12 @@ class BatchCorrManifold : public Module {
     const std::vector<double> &TimeGrid() const { return timeGrid; }
     const std::vector<double> &PosGrid() const { return posGrid; }
     const std::vector<double> &VelGrid() const { return velGrid; }
+    bool Axes() const { return axes; }           // the grids went to the engine as axes: PosGrid() / VelGrid() are empty
 
   private:
     dpe_bcm *h = nullptr;
-    bool Started = false, loadPosGrid = false;
+    bool Started = false, loadPosGrid = false, gridAxes = false, axes = false;
+    std::vector<double> posAx[4], velAx[4];
     int posDim = 25, velDim = 25, gridType = 0, LPower = 1;
     bool useGraph = false, deviceLoop = false;
     bool referencePair = false;   // reproduce the reference's floor(idx) / floor(idx + 1) pair where it double-counts (dpe_hip.h)
@@ -845,8 +871,8 @@ class cuChanMgrDev : public Module {
             if (dpe_chm_dev_set_ekf(h, &ec)) DPE_MOD_FAIL("Start: " << dpe_last_error());
         }
         if (bcm->Comm() &&
-            dpe_chm_dev_set_shard(h, bcm->Comm(), bcm->PosGrid().data(), (int64_t)bcm->PosGrid().size() / 4, bcm->VelGrid().data(),
-                                  (int64_t)bcm->VelGrid().size() / 4))
+            dpe_chm_dev_set_shard(h, bcm->Comm(), bcm->Axes() ? nullptr : bcm->PosGrid().data(), (int64_t)bcm->PosGrid().size() / 4,
+                                  bcm->Axes() ? nullptr : bcm->VelGrid().data(), (int64_t)bcm->VelGrid().size() / 4))
             DPE_MOD_FAIL("Start: " << dpe_last_error());
         if (xFilename[0]) {
             fp = std::fopen(xFilename, "w");
