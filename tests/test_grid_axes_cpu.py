@@ -96,6 +96,10 @@ class _Raw:   # axes the Python class itself would refuse (dim 0)
     ("point lists too", dict(with_points=True), "posGrid / velGrid must be NULL"),
     ("compact banks", dict(K=37, L=174, B=20), "exceed the LDS"),
     ("slice beyond product", dict(size=25 ** 4, offset=1), "beyond the axis product"),
+    # one entry past the widest banks admitted at K = 37 (max(L, B) = 113, run on the GPU by test_gpu_axes_scan.py):
+    # 37 x (229 x 16 + 32) + 17408 = 154160 > 153600 bytes
+    ("one lag entry past the LDS", dict(K=37, L=114, B=20), "score banks (135568 B) and the score stage (17408 B) exceed the LDS"),
+    ("one bin entry past the LDS", dict(K=37, L=4, B=114), "score banks (135568 B) and the score stage (17408 B) exceed the LDS"),
 ])
 def test_create_axes_refusals(what, kw, msg):
     g = dpe.GridAxes.uniform(25, 1.0)
