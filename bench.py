@@ -12,10 +12,13 @@ path over a batch of `--windows` windows resident in HBM: BatchCorrScores (DC su
 BatchCorrManifold (pos scan, vel scan, fused arg-max) for every window, each with its own channel state.
 metric = manifold gridpoints x SVs correlated per second (both manifolds), whole job.
 
-Without --config the run first prints one line each for the other configurations BASELINE.json names (same format,
-"headline": false):  acq (configs[4]: cold-start acquisition search, N = 1 only), H (configs[2]: 25 Msps, 12 SVs, 1e5-point
-grids; N = 1 only) and M (configs[3]: 1e6-point GLOBAL grids
-sharded over the N GPUs, strong scaling), then the headline line.
+A plain run does only what that figure needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the one
+JSON line.  Everything else it can measure runs with --full:  without --config the run then first prints one line each for the
+other configurations BASELINE.json names (same format, "headline": false):  acq (configs[4]: cold-start acquisition search,
+N = 1 only), H (configs[2]: 25 Msps, 12 SVs, 1e5-point grids; N = 1 only) and M (configs[3]: 1e6-point GLOBAL grids
+sharded over the N GPUs, strong scaling), then the headline line.  Every line then carries its CPU baseline, the H, M and R
+lines their one-lane passes (`kernels_ms_per_step`, `one_stream_ms_per_step`, `roofline`) and the headline the measured HBM
+ceiling.
 
 N > 1: the grid dimension is sharded (R, H: each rank scores its own contiguous slice of an N-times larger global grid ->
 weak scaling; M: the global grid is fixed -> strong scaling).  Stage 1 is sharded by WINDOW: rank r correlates windows
@@ -24,7 +27,8 @@ weak scaling; M: the global grid is fixed -> strong scaling).  Stage 1 is sharde
 all-reduce(MAX) of packed (score, index) keys per step (`--exchange scores`: the north-star-literal all-reduce(SUM) of
 zero-initialised full score vectors).
 
-Timing: W untimed warm-up steps and a clock warm-up, then exactly K timed steps, dealt over `--batches` batches (default
+Timing: W untimed warm-up steps and a clock warm-up on one lane (with --full, the one-lane passes after them), a clock
+warm-up of the `--in-flight` lanes, then exactly K timed steps, dealt over `--batches` batches (default
 one), each bracketed by barrier + synchronize; per batch the MAX over ranks, and the MEDIAN batch is reported.
 A timed batch shorter than --min-batch-s (0.2 s) is reported on stderr: raise --steps for a steady-state number.
 
@@ -487,25 +491,29 @@ def run_workload(name, ctx, args, steps, warmup, headline, cached=None, dump_dir
         step()
     fence()
     clock_warmup()
-    # Untimed side pass: HIP events around every kernel (`kernels_ms_per_step`), which also names the time-dominant kernel.
-    bcs.profile(True); bcm.profile(True)
-    n_side = 12
-    for _ in range(n_side):
-        step()
-    fence()
-    side = dict(bcs.profile(False))
-    side.update(bcm.profile(False))
-    kernels_ms = {k: v[0] / max(v[1], 1) * (v[1] / n_side) for k, v in side.items()}   # per step (side chunks of a wide lag window add up)
-    dominant = max(kernels_ms, key=kernels_ms.get)
-    # One stream (one lane): the isolated dominant kernel between HIP events for the `roofline` stanza (a pair of events around
-    # every kernel costs ~2 % of a step, so only the dominant one carries them), and `one_stream_ms_per_step`.
-    if dominant == "bcm_scan":
-        bcm.profile(True)
-    else:
-        bcs.profile(dominant)
-    one_ms = timed()
-    kern = dict(bcm.profile(False)) if dominant == "bcm_scan" else dict(bcs.profile(False))
-    one_stream_ms = float(np.median(one_ms))
+    # The one-lane passes (--full; or the timed region itself with --in-flight 1, whose ms_per_step has always been this pass's,
+    # events around the dominant kernel included)
+    one_stream = args.full or n_lanes == 1
+    if one_stream:
+        # Untimed side pass: HIP events around every kernel (`kernels_ms_per_step`), which also names the time-dominant kernel.
+        bcs.profile(True); bcm.profile(True)
+        n_side = 12
+        for _ in range(n_side):
+            step()
+        fence()
+        side = dict(bcs.profile(False))
+        side.update(bcm.profile(False))
+        kernels_ms = {k: v[0] / max(v[1], 1) * (v[1] / n_side) for k, v in side.items()}   # per step (side chunks of a wide lag window add up)
+        dominant = max(kernels_ms, key=kernels_ms.get)
+        # One stream (one lane): the isolated dominant kernel between HIP events for the `roofline` stanza (a pair of events around
+        # every kernel costs ~2 % of a step, so only the dominant one carries them), and `one_stream_ms_per_step`.
+        if dominant == "bcm_scan":
+            bcm.profile(True)
+        else:
+            bcs.profile(dominant)
+        one_ms = timed()
+        kern = dict(bcm.profile(False)) if dominant == "bcm_scan" else dict(bcs.profile(False))
+        one_stream_ms = float(np.median(one_ms))
     # The timed region proper: `--in-flight` lanes
     if n_lanes > 1:
         pipe.set_in_flight(n_lanes)
@@ -610,24 +618,11 @@ def run_workload(name, ctx, args, steps, warmup, headline, cached=None, dump_dir
         units_per_step = W * 2.0 * G_global * K                    # (gridpoint, SV) pairs, both manifolds, all ranks
         value = units_per_step / (ms_step * 1e-3)
         windows_per_s = W / (ms_step * 1e-3)
-        # --- roofline of the time-dominant kernel, SURVEY 8(d) algorithmic bytes per launch ON THIS RANK
-        stage1 = bcs.stage1_kernel
-        kname = {"bcm_scan": "bcm_scan_kernel", "bcs_bank": stage1, "bcs_finalize": "bcs_finalize_kernel",
-                 "bcs_sum": "bcs_sum_kernel"}[dominant]
-        alg = {"bcm_scan": 2 * W * 20.0 * G,            # 16 B grid read + 4 B score write per point, both manifolds in one launch
-               "bcs_bank": Wl * 4.0 * S,                # every int16 I/Q sample once (all SVs of a window share the read)
-               "bcs_sum": Wl * 4.0 * S,
-               "bcs_finalize": Wl * K * (nLag + nBin) * 8.0}[dominant]
-        ms_k, n_k = kern[dominant]
-        avg_ms = ms_k / n_k if n_k else None
-        ach = alg / (avg_ms * 1e-3) / 1e9 if avg_ms else 0.0
-        whole_bytes = W * (4.0 * S + 2 * 20.0 * G_global)         # per step, samples counted once for the node
-        traffic, tsrc = pmc_traffic(name, W, kname) if world == 1 else (None, None)
         out = {
             "metric": "manifold gridpoints x SVs correlated/sec", "value": value, "unit": "gridpoint*SV/s",
             "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": ms_step,
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic", "headline": bool(headline),
+            "data": "synthetic", "headline": bool(headline), "full": bool(args.full),
             "config": {"workload": cfg["name"], "samples_per_window": S, "svs": K, "grid_points_per_manifold_per_gpu": G,
                        "grid_points_per_manifold_global": G_global, "manifolds": 2, "windows_per_step": W, "distinct_windows": distinct,
                        "lag_half_width": L, "bin_half_width": B, "exchange": args.exchange if ctx.use_dist else "none",
@@ -641,29 +636,43 @@ def run_workload(name, ctx, args, steps, warmup, headline, cached=None, dump_dir
                        # per-window time measured equal at 64 / 128 / 256 windows per step (profiles/archive/r3a_H_w*_bench.json)
                        **({"windows_per_step_note": "128 per step against SURVEY 8(d)'s >= 256: same time per window at 64 / 128 / 256 "
                                                     "(profiles/archive/r3a_H_w64|w128|w256_bench.json)"} if name == "H" and W == 128 else {})},
-            "one_stream_ms_per_step": one_stream_ms,
-            "one_stream_value": units_per_step / (one_stream_ms * 1e-3),
             "timing": {"timed_steps": steps, "timed_batches": args.batches, "batch_ms_per_step": batch_ms,
-                       "one_stream_batch_ms_per_step": one_ms,
                        "statistic": "median of the batches, each the max over ranks"},
             "x_realtime": windows_per_s / 50.0, "windows_per_s": windows_per_s,
-            "roofline": {"bound": "hbm", "bound_physical": BOUND_PHYSICAL.get(kname, "valu"), "kernel": kname,
-                         "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": tsrc,
-                         "algorithmic_bytes_per_launch": alg, "avg_launch_ms": avg_ms,
-                         "whole_step_algorithmic_bytes": whole_bytes,
-                         "whole_step_frac": whole_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "note": "algorithmic bytes (SURVEY 8d) over the kernel's HIP-event time; bound_physical names the "
-                                 "measured limiter (SQ counters under profiles/), the kernels are not HBM-bound"},
-            "kernels_ms_per_step": kernels_ms, "stage1_kernel": stage1, "stage1_dev_status": stage1_status,
+            "stage1_kernel": bcs.stage1_kernel, "stage1_dev_status": stage1_status,
             # the decoded ML grid points (global indices, scores) of the last step's first windows: the same for every rank
             # count that scans the same global grid (config M), which is what the multi-rank tests compare
             "fixes": fixes,
         }
+        if one_stream:
+            # --- roofline of the time-dominant kernel, SURVEY 8(d) algorithmic bytes per launch ON THIS RANK
+            kname = {"bcm_scan": "bcm_scan_kernel", "bcs_bank": bcs.stage1_kernel, "bcs_finalize": "bcs_finalize_kernel",
+                     "bcs_sum": "bcs_sum_kernel"}[dominant]
+            alg = {"bcm_scan": 2 * W * 20.0 * G,            # 16 B grid read + 4 B score write per point, both manifolds in one launch
+                   "bcs_bank": Wl * 4.0 * S,                # every int16 I/Q sample once (all SVs of a window share the read)
+                   "bcs_sum": Wl * 4.0 * S,
+                   "bcs_finalize": Wl * K * (nLag + nBin) * 8.0}[dominant]
+            ms_k, n_k = kern[dominant]
+            avg_ms = ms_k / n_k if n_k else None
+            ach = alg / (avg_ms * 1e-3) / 1e9 if avg_ms else 0.0
+            whole_bytes = W * (4.0 * S + 2 * 20.0 * G_global)         # per step, samples counted once for the node
+            traffic, tsrc = pmc_traffic(name, W, kname) if world == 1 else (None, None)
+            out["one_stream_ms_per_step"] = one_stream_ms
+            out["one_stream_value"] = units_per_step / (one_stream_ms * 1e-3)
+            out["timing"]["one_stream_batch_ms_per_step"] = one_ms
+            out["roofline"] = {"bound": "hbm", "bound_physical": BOUND_PHYSICAL.get(kname, "valu"), "kernel": kname,
+                               "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                               "traffic": traffic, "traffic_source": tsrc,
+                               "algorithmic_bytes_per_launch": alg, "avg_launch_ms": avg_ms,
+                               "whole_step_algorithmic_bytes": whole_bytes,
+                               "whole_step_frac": whole_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "note": "algorithmic bytes (SURVEY 8d) over the kernel's HIP-event time; bound_physical names the "
+                                       "measured limiter (SQ counters under profiles/), the kernels are not HBM-bound"}
+            out["kernels_ms_per_step"] = kernels_ms
         if pcie_value is not None:
             out["pcie_inclusive_value"] = pcie_value
             out["pcie_inclusive_overlapped_value"] = pcie_overlapped
-        if world == 1 and headline:
+        if args.full and world == 1 and headline:
             # measured ceiling beside the nominal peak: stream copy and triad over 1 GiB arrays
             cp, tr = dpe.engine.hbm_ceiling(1 << 30, 10, stream)
             out["roofline"]["measured_ceiling"] = {
@@ -724,7 +733,12 @@ def main():
                     help="time only this configuration.  R = BASELINE.json configs[1] (the metric's configuration, the default "
                          "headline); H = configs[2] (25 Msps, 12 SVs, 1e5-point grids); M = configs[3] (1e6-point global grids, "
                          "strong scaling over the GPUs).  Without it: H (N = 1) and M lines first, then the R headline")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline configuration")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline figure: without --config the acq, H and M lines before the "
+                         "headline, the CPU baselines, the one-lane passes (per-kernel times, one_stream_ms_per_step, the roofline "
+                         "stanza) and the measured HBM ceiling.  Without it a run warms up, times --steps steps, writes "
+                         "--dump-outputs and prints the one line")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the headline configuration")
     ap.add_argument("--extra-windows", type=int, default=None, help="windows per step of the extra (non-headline) lines")
     ap.add_argument("--comm", choices=["torch", "dpe"], default="torch",
                     help="who carries the N > 1 data-path exchange: torch.distributed (RCCL through PyTorch), or the C-ABI's own "
@@ -744,13 +758,13 @@ def main():
     ap.add_argument("--min-batch-s", type=float, default=0.2,
                     help="warn when a timed batch lasts less than this: a short one measures launch overhead and clocks as much as the "
                          "kernels (0: no warning)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--cpu-budget-s", type=float, default=10.0,
                     help="seconds of one-thread oracle time behind the headline's cpu_baseline (H / M: 0.4 / 0.5 of it, at least one "
                          "whole window each); below 5 the all-cores leg is skipped")
     ap.add_argument("--in-flight", type=int, default=2,
                     help="batches in flight in the timed region (lanes of the library's dpe_pipe: stage 1 of step n + 1 beside the scan "
-                         "of step n); 1 = one stream.  `one_stream_ms_per_step` is reported beside it either way")
+                         "of step n); 1 = one stream.  `one_stream_ms_per_step` is reported beside it with --full")
     ap.add_argument("--no-pipelined", action="store_true", help="same as --in-flight 1 (kept for the profile collection scripts)")
     ap.add_argument("--no-scores", action="store_true", help="skip the per-point score write (arg-max only)")
     ap.add_argument("--include-h2d", action="store_true",
@@ -822,9 +836,9 @@ def main():
     headline = args.config or "R"
     cached = None
     configs = {"R": dpe.workload.CONFIG_R, "H": dpe.workload.CONFIG_H, "M": dpe.workload.CONFIG_M}
-    want_cpu = ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline
     others = {}
-    if args.config is None and not args.no_extras:
+    if args.full and args.config is None and not args.no_extras:
         if ctx.world == 1 and not ctx.use_dist:
             try:
                 out = acq_line(args.steps)        # BASELINE.json configs[4]

@@ -11,7 +11,7 @@ mkdir -p $R/gpurun_out
 for r in $(seq $ROUNDS); do
   for b in "$@"; do
     if [ "$b" = tree ]; then L=$R/navlab-dpe-sdr_amd/libdpe_hip.so; else L=$R/scratch/ab/$b/libdpe_hip.so; fi
-    DPE_LIB_PATH=$L python3 bench.py --config $CFG --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
+    DPE_LIB_PATH=$L python3 bench.py --full --config $CFG --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

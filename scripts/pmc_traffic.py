@@ -22,7 +22,7 @@ def main():
                 if row["Counter_Name"] == c:
                     acc[short(row["Kernel_Name"])][(c, row["Dispatch_Id"])].append(float(row["Counter_Value"]))
     out = {"source": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) --kernel-trace --output-format csv -- "
-                     "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline [--config C]   (scripts/collect_profiles.sh)",
+                     "python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline [--config C]   (scripts/collect_profiles.sh)",
            "note": "KB per launch (mean over launches, summed over the counter's instances); FETCH_SIZE doubled per "
                    "MI355X_MICROARCH.md; bcs_sum_kernel cross-check: 2*FETCH = windows*S*4 bytes",
            "windows_per_step": windows, "config": config, "kernels": {}}

@@ -27,13 +27,13 @@ def _launch(port, extra, nproc=2, expect_rc=0, timeout=300):
 
 
 def test_four_ranks_default_invocation_matches_one_rank():
-    """The default invocation with --gpus 4 (M strong scaling, then the R headline, weak scaling) with all four ranks on one
+    """The --full invocation with --gpus 4 (M strong scaling, then the R headline, weak scaling) with all four ranks on one
     GPU and gloo carrying the exchange: 4-way partition arithmetic of both grids, stage 1 sharded over 4 ranks (two windows
     each; then, config M alone, one window each), key all-reduce.  (Four ranks rather than a full node's eight keep the
     processes that hold the one GPU, this test's own included, within the six a shared GPU host admits;
     tests/test_bench_cpu.py checks the 8-way partition of the strong-scaling grid.)  Config M scans the same global grid
     whatever the rank count, so its decoded fixes must be those of the one-rank run."""
-    lines = _launch(29571, ["--windows", "8", "--extra-windows", "8"], nproc=4, timeout=900)
+    lines = _launch(29571, ["--full", "--windows", "8", "--extra-windows", "8"], nproc=4, timeout=900)
     assert len(lines) == 2, lines
     m, d = lines
     assert m["n_gpus"] == 4 and m["scaling"] == "strong" and m["config"]["stage1"].startswith("sharded")
@@ -77,8 +77,8 @@ def test_windows_must_divide_over_the_ranks():
 
 @pytest.mark.parametrize("exchange,port", [("keys", 29561), ("scores", 29562)])
 def test_two_rank_bench_lines(exchange, port):
-    """Default invocation: the M line (strong scaling, 1e6-point global grids) then the R headline, rank 0 only."""
-    lines = _launch(port, ["--windows", "4", "--extra-windows", "4", "--exchange", exchange])
+    """--full without --config: the M line (strong scaling, 1e6-point global grids) then the R headline, rank 0 only."""
+    lines = _launch(port, ["--full", "--windows", "4", "--extra-windows", "4", "--exchange", exchange])
     assert len(lines) == 2, lines
     m, d = lines
     assert m["headline"] is False and m["scaling"] == "strong" and m["n_gpus"] == 2 and m["value"] > 0
@@ -157,11 +157,11 @@ def test_one_rank_rccl_self_test_through_the_c_abi():
 
 
 def test_default_invocation_carries_every_configuration_in_the_last_line():
-    """`python bench.py` (N = 1): acq, H and M lines first, then the R headline whose `others` stanza repeats them in brief --
+    """`python bench.py --full` (N = 1): acq, H and M lines first, then the R headline whose `others` stanza repeats them in brief --
     time, value, roofline fractions, device status, CPU baseline -- because the driver records the last line only.  The timed
     regions run with two batches in flight (the library's dpe_pipe), the one-stream time beside them."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DPE_BENCH_BACKEND")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--clock-warmup-s", "0", "--min-batch-s", "0.01",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--clock-warmup-s", "0", "--min-batch-s", "0.01",
            "--batches", "2", "--cpu-budget-s", "0.5", "--windows", "32", "--extra-windows", "32"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -170,6 +170,7 @@ def test_default_invocation_carries_every_configuration_in_the_last_line():
     d = lines[-1]
     assert d["config"]["workload"].startswith("R:") and d["config"]["in_flight"] == 2 and d["one_stream_ms_per_step"] > 0
     assert d["roofline"]["kernel"] == "bcm_scan_kernel" and 0 < d["roofline"]["frac"] < 1.0
+    assert d["full"] is True and d["roofline"]["measured_ceiling"]["triad_GBps"] > 0
     assert d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["value"] > 0
     o = d["others"]
     assert set(o) == {"acq", "H", "M"}
@@ -183,6 +184,29 @@ def test_default_invocation_carries_every_configuration_in_the_last_line():
     assert o["acq"]["cpu_baseline"]["value"] > 0 and 0 < o["acq"]["roofline"]["flop_frac"] < 1
     # the brief copies are the lines' own numbers
     assert o["H"]["ms_per_step"] == lines[1]["ms_per_step"] and o["M"]["value"] == lines[2]["value"] and o["acq"]["value"] == lines[0]["value"]
+
+
+def test_plain_invocation_prints_the_headline_alone():
+    """`python bench.py` without --full: the R headline alone, without the extra configurations, CPU baselines, one-lane passes
+    or HBM ceiling.  With --in-flight 1 the one-lane pass is the timed region itself, so its figures come along."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DPE_BENCH_BACKEND")}
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--clock-warmup-s", "0", "--min-batch-s",
+            "0.01", "--windows", "16"]
+    for extra in ([], ["--in-flight", "1"]):
+        r = subprocess.run(base + extra, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, lines
+        d = lines[0]
+        assert d["headline"] is True and d["full"] is False and d["config"]["workload"].startswith("R:")
+        assert d["ms_per_step"] > 0 and d["value"] > 0 and d["timing"]["timed_steps"] == 2 and len(d["fixes"]) == 16
+        assert not {"others", "cpu_baseline"} & set(d)
+        if extra:
+            assert d["config"]["in_flight"] == 1 and d["one_stream_ms_per_step"] == d["ms_per_step"]
+            assert "kernels_ms_per_step" in d and "measured_ceiling" not in d["roofline"]
+        else:
+            assert d["config"]["in_flight"] == 2
+            assert not {"roofline", "kernels_ms_per_step", "one_stream_ms_per_step", "one_stream_value"} & set(d)
 
 
 def test_dump_outputs_hold_the_last_timed_step_and_repeat(tmp_path):
