@@ -583,6 +583,61 @@ int dpe_acq_scalar_acquisition(dpe_acq *h, const int16_t *window0_dev, const int
 /* |coarse_result_matrix| as float [nPrn][nBins][S/N] and its per-lag maximum over bins [nPrn][S/N] */
 int dpe_acq_surface(dpe_acq *h, const float **surface_dev, const float **maxPerCode_dev);
 
+/* ------------------------------------------------------------------ Scalar tracking ---- */
+/* The stage between acquisition and the DPE loop.  Only the reference's Python twin has it: Receiver.scalar_track
+ * (pygnss/pythonreceiver/receiver.py:522-542), i.e. per window and channel Correlator.scalar_correlate (scalar/correlator.py:135-283),
+ * Channel.scalar_correlation / scalar_time_update / scalar_measurement_update (scalar/channel.py:104-122, 173-191, 247-273) with the
+ * components Channel.__init__ wires up (channel.py:51-62): DLL / PLL discriminators, two second-order bilinear loop filters, lock
+ * detector (N = 20, k = 1.5, thresholds 50 / 240) and SNR meter (N = 20).  The loops are channel-local, so dpe_trk_track runs ONE
+ * kernel launch for all channels and all windows of the call: one block per channel walks the windows in order (csrc/dpe_trk.hip).
+ * The twin's "EXTREME ERROR" branch -- no boundary case applies; here also: parameters that are not finite, a code phase outside
+ * [0, 1023] -- sets bit 0 of the device status word and freezes the channel (its later records hold NaN correlations, case -1). */
+typedef struct dpe_trk dpe_trk;
+typedef struct dpe_trk_config {
+    double samplingFrequency;
+    double T;                     /* window length in s; S = round(T fs) samples (rawfile.py:164); at most 1.5 ms */
+    int32_t nChan;
+    int32_t order;                /* loop order: 0 or 2 = the twin's second-order loops (loopfilter.py:37-50); nothing else is built */
+    double codeBnp;               /* code-loop noise bandwidth in Hz, 0 -> 3 (channel.py:57) */
+    double carrBnp;               /* carrier-loop noise bandwidth in Hz, 0 -> 40 (channel.py:58) */
+    double dopplerSign;           /* rawfile.ds, 0 -> +1; fcaid = ds F_CA / F_L1 (rawfile.py:98) */
+    int64_t logCapacityWindows;   /* the log is a ring of this many windows; the cp_sign streams hold 2 x that + 2 entries */
+    int32_t prn[DPE_MAX_CHAN];
+    int32_t reserved;
+} dpe_trk_config;
+/* One log record per window and channel, doubles in this order -- the twin's array names (channel.py:17-21), then two of ours:
+ * cp rc ri fc fi iE qE iP qP iL qL dc di efc efi dpc dpi fc_bias fi_bias lock lockval snr | case (0, 1, 2 boundaries inside the
+ * window; -1 frozen) and the number of code periods the window completed.  As in the twin, row m holds the parameters window m was
+ * correlated with and the measurement update that FOLLOWED window m - 1 (NaN in the first row after dpe_trk_set_params). */
+#define DPE_TRK_LOG_DOUBLES 24
+typedef struct dpe_trk_chan_state {
+    int32_t prn, lock, frozen, reserved;
+    int64_t cp, nWindows, nSigns;            /* completed code periods, windows tracked, cp_sign entries -- since dpe_trk_set_params */
+    double rc, ri, fc, fi, fc_bias, fi_bias; /* parameters of the next window */
+    double paRe, paIm;                       /* Correlator.p_a */
+} dpe_trk_chan_state;
+int dpe_trk_create(const dpe_trk_config *cfg, dpe_trk **out);
+int dpe_trk_destroy(dpe_trk *h);
+/* Channel.set_scalar_params (channel.py:82-102) for every channel, from what dpe_acq_scalar_acquisition returned (entry k must be
+ * the tracker's PRN k; found / cppr / cppm are not read): start parameters, fi_bias = fi, fc_bias = fc - F_CA - fcaid fi, both loop
+ * filters reset.  Also resets the detectors, the code-period count, the log and the status word.  Synchronises. */
+int dpe_trk_set_params(dpe_trk *h, const dpe_acq_track_init *init /* [nChan] */, dpe_stream_t stream);
+/* Tracks nWindows consecutive windows of S interleaved int16 I/Q samples each.  Asynchronous; the loop state stays in the handle on
+ * the device, so successive calls continue the record (track(M) == track(M / 2) twice, bit for bit). */
+int dpe_trk_track(dpe_trk *h, const int16_t *samples_dev, int32_t nWindows, dpe_stream_t stream);
+/* Teacher-forced correlator, the sample phase of dpe_trk_track without the loop: window m, channel k with params[m][k] = {rc, ri,
+ * fc, fi} and a carried p_a of zero.  out[m][k][32] (host): the segment sums E, P, L (re, im) of the up to three segments the
+ * boundaries idxs1, idxs2 cut (18), iE qE iP qP iL qL as scalar_correlate combines them (6), case, completed code periods, idxs1,
+ * idxs2, the two prompt signs, two spare.  Touches no loop state.  Synchronises. */
+int dpe_trk_correlate(dpe_trk *h, const int16_t *samples_dev, int32_t nWindows, const double *params /* host [nWindows][nChan][4] */,
+                      double *out /* host [nWindows][nChan][32] */, dpe_stream_t stream);
+/* Log records of windows [firstWindow, firstWindow + nWindows) counted from dpe_trk_set_params: out[nWindows][nChan][DPE_TRK_LOG_DOUBLES]. Synchronises. */
+int dpe_trk_read_log(dpe_trk *h, int64_t firstWindow, int32_t nWindows, double *out, dpe_stream_t stream);
+/* Entries [first, first + n) of channel `chan`'s signal-synchronous prompt signs, -sign(Re p_s) as the twin's cp_sign (0, 1 or 2 per window). Synchronises. */
+int dpe_trk_read_cp_signs(dpe_trk *h, int32_t chan, int64_t first, int32_t n, int8_t *out, dpe_stream_t stream);
+int dpe_trk_state(dpe_trk *h, dpe_trk_chan_state *out /* [nChan] */, dpe_stream_t stream);   /* synchronises */
+int dpe_trk_dev_status(dpe_trk *h, int32_t *status, dpe_stream_t stream);                    /* bit 0: a channel froze; synchronises */
+
 /* Per-kernel timing (HIP events recorded on the launch stream around each kernel).  Returns and
  * resets the totals accumulated since the previous call, then sets the enable flag.
  * BCS slots: 0 DC-sum (not launched for single windows, where the bank kernel carries the sums), 1 bank (one launch per

@@ -35,6 +35,8 @@ EXPORTS = [
     "dpe_chm_dev_set_shard", "dpe_chm_dev_set_ekf",
     "dpe_pipe_create", "dpe_pipe_create_axes", "dpe_pipe_destroy", "dpe_pipe_in_flight", "dpe_pipe_submit", "dpe_pipe_acquire", "dpe_pipe_mark_stage1",
     "dpe_pipe_commit", "dpe_pipe_lane", "dpe_pipe_set_in_flight", "dpe_pipe_lane_at", "dpe_pipe_results", "dpe_pipe_samples_consumed", "dpe_pipe_join", "dpe_pipe_synchronize",
+    "dpe_trk_create", "dpe_trk_destroy", "dpe_trk_set_params", "dpe_trk_track", "dpe_trk_correlate", "dpe_trk_read_log",
+    "dpe_trk_read_cp_signs", "dpe_trk_state", "dpe_trk_dev_status",
 ]
 
 
@@ -990,6 +992,101 @@ class Acquisition:
     def close(self):
         if self._h:
             lib().dpe_acq_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:            # at interpreter shutdown module globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+class TrkConfig(C.Structure):
+    _fields_ = [("samplingFrequency", C.c_double), ("T", C.c_double), ("nChan", C.c_int32), ("order", C.c_int32),
+                ("codeBnp", C.c_double), ("carrBnp", C.c_double), ("dopplerSign", C.c_double), ("logCapacityWindows", C.c_int64),
+                ("prn", C.c_int32 * 37), ("reserved", C.c_int32)]
+
+
+class TrkChanState(C.Structure):
+    _fields_ = [("prn", C.c_int32), ("lock", C.c_int32), ("frozen", C.c_int32), ("reserved", C.c_int32),
+                ("cp", C.c_int64), ("nWindows", C.c_int64), ("nSigns", C.c_int64),
+                ("rc", C.c_double), ("ri", C.c_double), ("fc", C.c_double), ("fi", C.c_double), ("fc_bias", C.c_double),
+                ("fi_bias", C.c_double), ("paRe", C.c_double), ("paIm", C.c_double)]
+
+
+class ScalarTracker:
+    """Receiver.scalar_track (receiver.py:522-542) for `prns`: every channel's early / prompt / late loop over all windows
+    of a call in one kernel launch (dpe_trk_*).  Loop bandwidths default to the twin's (channel.py:57-58)."""
+    LOG_NAMES = ("cp", "rc", "ri", "fc", "fi", "iE", "qE", "iP", "qP", "iL", "qL", "dc", "di", "efc", "efi", "dpc", "dpi",
+                 "fc_bias", "fi_bias", "lock", "lockval", "snr", "case", "cp_compl")
+    CORR_WIDTH = 32
+
+    def __init__(self, SamplingFrequency, prns, T=1e-3, log_capacity_windows=4096, code_bnp=0.0, carr_bnp=0.0, ds=1.0):
+        self.fs, self.T = float(SamplingFrequency), float(T)
+        self.S = int(round(self.T * self.fs))
+        self.prns = [int(p) for p in prns]
+        cfg = TrkConfig(self.fs, self.T, len(self.prns), 2, float(code_bnp), float(carr_bnp), float(ds), int(log_capacity_windows),
+                        (C.c_int32 * 37)(*self.prns), 0)
+        self._h = C.c_void_p(None)
+        _check(lib().dpe_trk_create(C.byref(cfg), C.byref(self._h)))
+        self.n_windows = 0
+
+    def set_params(self, init, stream=None):
+        """init: one dict per channel with prn, rc, ri, fc, fi -- as Acquisition.scalar_acquisition returns them
+        (Channel.set_scalar_params, channel.py:82-102)."""
+        a = (AcqTrackInit * len(self.prns))()
+        for r, c in zip(a, init):
+            r.prn, r.found, r.rc, r.ri, r.fc, r.fi = int(c["prn"]), int(bool(c.get("found", True))), c["rc"], c["ri"], c["fc"], c["fi"]
+        _check(lib().dpe_trk_set_params(self._h, a, _stream(stream)))
+        self.n_windows = 0
+
+    def track(self, Samples, n_windows, stream=None):
+        """Samples: device int16 [n_windows, 2*S], consecutive windows.  Asynchronous; successive calls continue the record."""
+        _check(lib().dpe_trk_track(self._h, _ptr(Samples), C.c_int32(n_windows), _stream(stream)))
+        self.n_windows += int(n_windows)
+
+    def correlate(self, Samples, params, stream=None):
+        """Teacher-forced correlator: params [M, K, 4] = rc, ri, fc, fi per window and channel, carried p_a = 0.  Returns
+        dict(seg [M, K, 3 segments, 3 taps E P L] complex, epl [M, K, 3] complex, case, cp_compl, idxs1, idxs2, signs [M, K, 2])."""
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        M, K = p.shape[0], p.shape[1]
+        assert p.shape == (M, len(self.prns), 4)
+        out = np.empty((M, K, self.CORR_WIDTH), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        _check(lib().dpe_trk_correlate(self._h, _ptr(Samples), C.c_int32(M), p.ctypes.data_as(dp), out.ctypes.data_as(dp), _stream(stream)))
+        seg = (out[..., 0:18:2] + 1j * out[..., 1:18:2]).reshape(M, K, 3, 3)
+        return dict(seg=seg, epl=out[..., 18:24:2] + 1j * out[..., 19:24:2], case=out[..., 24].astype(np.int64),
+                    cp_compl=out[..., 25].astype(np.int64), idxs1=out[..., 26], idxs2=out[..., 27], signs=out[..., 28:30].astype(np.int8))
+
+    def read_log(self, first=0, n=None, stream=None):
+        """{name: [n, K]} for the windows [first, first + n) since set_params, names as the twin's logs (LOG_NAMES)."""
+        n = self.n_windows - first if n is None else int(n)
+        out = np.empty((n, len(self.prns), len(self.LOG_NAMES)), dtype=np.float64)
+        _check(lib().dpe_trk_read_log(self._h, C.c_int64(first), C.c_int32(n), out.ctypes.data_as(C.POINTER(C.c_double)), _stream(stream)))
+        return {name: out[:, :, j].copy() for j, name in enumerate(self.LOG_NAMES)}
+
+    def state(self, stream=None):
+        st = (TrkChanState * len(self.prns))()
+        _check(lib().dpe_trk_state(self._h, st, _stream(stream)))
+        return [{f[0]: getattr(r, f[0]) for f in TrkChanState._fields_ if f[0] != "reserved"} for r in st]
+
+    def read_cp_signs(self, chan, first=0, n=None, stream=None):
+        """Channel `chan`'s cp_sign stream (int8), entries [first, first + n); n = None: up to the last one written."""
+        if n is None:
+            n = self.state(stream)[chan]["nSigns"] - first
+        out = np.empty(int(n), dtype=np.int8)
+        _check(lib().dpe_trk_read_cp_signs(self._h, C.c_int32(chan), C.c_int64(first), C.c_int32(int(n)),
+                                           out.ctypes.data_as(C.POINTER(C.c_int8)), _stream(stream)))
+        return out
+
+    def dev_status(self, stream=None):
+        st = C.c_int32()
+        _check(lib().dpe_trk_dev_status(self._h, C.byref(st), _stream(stream)))
+        return st.value
+
+    def close(self):
+        if self._h:
+            lib().dpe_trk_destroy(self._h)
             self._h = C.c_void_p(None)
 
     def __del__(self):

@@ -83,6 +83,42 @@ def gen_iq(seed, fs, S, ch, amp=48.0, sigma=300.0, dc=(3.0, -2.0), flip=None):
     return iq
 
 
+def gen_iq_record(seed, fs, n_samples, ch, amp=48.0, sigma=300.0, nav_bits=None):
+    """One CONTINUOUS record of interleaved int16 I/Q: code and carrier phase run on over any window boundary
+    (sample n at t = n / fs: code phase t fc + rc, carrier phase fi t + ri, `ch` as for gen_iq, referred to sample 0) and
+    a nav-bit sign every 20 code periods.  nav_bits[k]: +-1 per bit of channel k (drawn from the seed when None);
+    bit j of channel k covers the code periods [20 j - ch["cp_ref"][k] % 20, ...), i.e. the first edge falls
+    cp_ref % 20 code periods after the start of the code period sample 0 lies in (20 when that is 0; bit 0 is then unused).  No DC offset.
+    Returns (iq int16 [2 n_samples], nav_bits list of int8 arrays)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    K = len(ch["prn"])
+    n = np.arange(n_samples, dtype=np.float64)
+    t = n / fs
+    amp = np.broadcast_to(np.asarray(amp, dtype=np.float64), (K,))
+    x = np.zeros(n_samples, dtype=np.complex128)
+    bits_out = []
+    for k in range(K):
+        chips = ca_code(int(ch["prn"][k])).astype(np.float64)
+        cph = t * ch["fc"][k] + ch["rc"][k]
+        ci = np.floor(cph).astype(np.int64)
+        period = ci // L_CA                                     # code periods since the one sample 0 lies in
+        first_edge = int(ch["cp_ref"][k]) % 20 if "cp_ref" in ch else 0
+        bit_idx = (period - first_edge + 20) // 20              # 0 before the first edge
+        nb = int(bit_idx.max()) + 1
+        if nav_bits is None:
+            bits = (2 * rng.integers(0, 2, nb) - 1).astype(np.int8)
+        else:
+            bits = np.asarray(nav_bits[k], dtype=np.int8)
+            assert bits.size >= nb, "channel %d needs %d nav bits" % (k, nb)
+        bits_out.append(bits[:nb].copy())
+        x += amp[k] * bits[bit_idx] * chips[np.mod(ci, L_CA)] * np.exp(2j * np.pi * (ch["fi"][k] * t + ch["ri"][k]))
+    x += sigma * (rng.standard_normal(n_samples) + 1j * rng.standard_normal(n_samples))
+    iq = np.empty(2 * n_samples, dtype=np.int16)
+    iq[0::2] = np.clip(np.rint(x.real), -32768, 32767).astype(np.int16)
+    iq[1::2] = np.clip(np.rint(x.imag), -32768, 32767).astype(np.int16)
+    return iq, bits_out
+
+
 def rand_grid(seed, G, half=(110.0, 110.0, 110.0, 132.0)):
     """rngrid3-format random ENU-dt grid (SURVEY.md 8d iii): columns x,y,z,delta_t (m)."""
     rng = np.random.Generator(np.random.PCG64(seed))
