@@ -638,6 +638,66 @@ int dpe_trk_read_cp_signs(dpe_trk *h, int32_t chan, int64_t first, int32_t n, in
 int dpe_trk_state(dpe_trk *h, dpe_trk_chan_state *out /* [nChan] */, dpe_stream_t stream);   /* synchronises */
 int dpe_trk_dev_status(dpe_trk *h, int32_t *status, dpe_stream_t stream);                    /* bit 0: a channel froze; synchronises */
 
+/* ---- Scalar navigation: the stage between scalar tracking and the handoff the DPE loop starts from.  The twin's
+ * parse_ephemerides (libgnss/dataparser.py:10-70) with Word / Subframe / Ephemerides (libgnss/ephemeris.py:16-297) on one channel's
+ * cp_sign stream, and calculate_nav_soln / perform_least_sqrs (scalar/naveng.py:10-224) per tracked epoch.  The decode and
+ * dpe_nav_solve are host fp64; dpe_nav_solve_log solves every logged epoch of a dpe_trk handle in one kernel launch, reading cp, rc
+ * and fi from the tracker's device-resident log (csrc/dpe_nav.hip). */
+typedef struct dpe_nav dpe_nav;
+#define DPE_NAV_EPH_DOUBLES 21    /* sqrt_A e i_0 OMEGA_0 omega M_0 delta_n OMEGADOT IDOT C_rc C_rs C_uc C_us C_ic C_is t_oe t_oc a_f0 a_f1 a_f2 T_GD */
+#define DPE_NAV_MODE_FULL 0       /* five consecutive subframes: ephemerides and timestamp from the signal (the twin's rule) */
+#define DPE_NAV_MODE_ASSISTED 1   /* timestamp only, from two consecutive TLM / HOW pairs; ephemerides come from the caller */
+/* decode status bits */
+#define DPE_NAV_DEC_FEW_PREAMBLES 1   /* no preamble hit with its +6000 ... +24000 companions (assisted: no parity-valid TLM / HOW pair) */
+#define DPE_NAV_DEC_PARITY 2          /* a word of the five subframes failed parity (its subframe is not decoded) */
+#define DPE_NAV_DEC_IODE 4            /* a subframe's IODE differs from the first one's (it is not added) */
+#define DPE_NAV_DEC_POLARITY_FLIP 8   /* the five preamble polarities are neither all +1 nor all -1 */
+#define DPE_NAV_DEC_CP_SLIP 16        /* the supplied per-window cp values do not advance by one */
+#define DPE_NAV_DEC_NO_HISTORY 32     /* fewer than 40 entries before the first subframe (no d29 / d30) */
+#define DPE_NAV_DEC_POLARITY_D30 64   /* a preamble's polarity contradicts d30 of the word before it (the twin asserts) */
+#define DPE_NAV_DEC_INCOMPLETE 128    /* full mode: not every ephemeris field was decoded */
+typedef struct dpe_nav_decoded {
+    double eph[DPE_NAV_EPH_DOUBLES];              /* NaN where not decoded */
+    int32_t week, accuracy, health, iode, iodc;   /* -1 where not decoded */
+    int32_t tow;                                  /* timestamp: TOW = HOW x 6 - 6 of the first subframe added ... */
+    int64_t cp;                                   /* ... and the code-period count of its first entry; -1: none */
+    int32_t status, nPreambleHits;
+    int32_t subframeId[5], polarity[5];
+    int32_t parity[50];                           /* [subframe][word]: 1 passed, 0 failed, -1 not formed */
+    int64_t subframeCp[5];
+} dpe_nav_decoded;
+/* solve status bits */
+#define DPE_NAV_SOL_RANK_POS 1        /* the position geometry is rank deficient (or fewer than four channels): the update is zero */
+#define DPE_NAV_SOL_NOT_CONVERGED 2   /* |last update| > 1e-5 m after 10 iterations */
+#define DPE_NAV_SOL_KEPLER 4          /* a Kepler iteration did not converge */
+#define DPE_NAV_SOL_RANK_VEL 8        /* the velocity geometry is rank deficient: the velocity is zero */
+typedef struct dpe_nav_fix {
+    double X_ECEF[8];                 /* x y z c dt | vx vy vz c dt' */
+    double rxTime, rxTime_a, lastUpdate;
+    int32_t iterations, status;
+} dpe_nav_fix;
+int dpe_nav_create(int32_t nChan, double dopplerSign, dpe_nav **out);
+int dpe_nav_destroy(dpe_nav *h);
+/* signs[n]: channel `chan`'s cp_sign entries, the first one of code period cpFirst (dpe_trk_read_cp_signs).  cpLog (optional,
+ * nCpLog per-window cp values of the same range): checked for slips as the twin does.  Fills *out; a full decode that is complete
+ * stores ephemerides and timestamp in the handle, an assisted one the timestamp.  Host only. */
+int dpe_nav_decode(dpe_nav *h, int32_t chan, const int8_t *signs, int64_t n, int64_t cpFirst, int32_t mode, const double *cpLog,
+                   int64_t nCpLog, dpe_nav_decoded *out);
+/* Caller-supplied ephemerides [nChan][DPE_NAV_EPH_DOUBLES] and / or timestamps (tow[nChan], cp[nChan]); a null pointer leaves that part. */
+int dpe_nav_set_ephemerides(dpe_nav *h, const double *eph, const int32_t *tow, const int64_t *cp);
+/* One epoch on the host: cp, rc, fi [nChan] (the tracker's log row).  chanMask: bit k selects channel k (0: all).  rxTime0: NaN
+ * for max(transmit time) + 0.068.  */
+int dpe_nav_solve(dpe_nav *h, const double *cp, const double *rc, const double *fi, uint64_t chanMask, double rxTime0, dpe_nav_fix *out);
+/* Epochs firstWindow + i x stride, i < nEpochs, of the tracker's log in one launch (one wave per epoch, one lane per channel).
+ * rxTime0 NaN: as above; else epoch i is solved at rxTime0 + i x rxTimeStep (receiver.py:561-569).  out: host [nEpochs]. Synchronises. */
+int dpe_nav_solve_log(dpe_nav *h, dpe_trk *trk, int64_t firstWindow, int32_t nEpochs, int32_t stride, uint64_t chanMask, double rxTime0,
+                      double rxTimeStep, dpe_nav_fix *out, dpe_stream_t stream);
+/* Receiver.load_measurement_logs (receiver.py:877-940) for the log alone: rows[nWindows][nChan][DPE_TRK_LOG_DOUBLES] (host) become
+ * windows [0, nWindows) of the tracker's log, nWindows <= logCapacityWindows -- a saved record for dpe_nav_solve_log.  As in the twin
+ * the loop filters' history is not loaded: tracking continues only after dpe_trk_set_params.  Synchronises. */
+int dpe_nav_load_log(dpe_trk *trk, int32_t nWindows, const double *rows, dpe_stream_t stream);
+int dpe_nav_status(dpe_nav *h, int32_t *status);   /* OR of the solve status bits since create */
+
 /* Per-kernel timing (HIP events recorded on the launch stream around each kernel).  Returns and
  * resets the totals accumulated since the previous call, then sets the enable flag.
  * BCS slots: 0 DC-sum (not launched for single windows, where the bank kernel carries the sums), 1 bank (one launch per

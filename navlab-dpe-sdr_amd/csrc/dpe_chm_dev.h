@@ -27,7 +27,14 @@ DPE_HD static inline double half_week(double t)  // CHM_Correct_Week_Crossover :
     return t > 302400.0 ? t - 604800.0 : (t < -302400.0 ? t + 604800.0 : t);
 }
 
-DPE_HD static inline bool solve_kepler(double M, double e, double &E)  // :97-107
+// The remainder the reference takes: C's fmod (the sign of the dividend).  The Python twin's np.mod takes the sign of the divisor
+// (dpe_nav_dev.h); with kPi rounded as the ICD rounds it the two differ by more than a period's rounding for a negative angle.
+struct ModTrunc {
+    DPE_HD double operator()(double a, double m) const { return std::fmod(a, m); }
+};
+
+template <class Mod>
+DPE_HD static inline bool solve_kepler_t(double M, double e, double &E, const Mod &mod)  // :97-107
 {
     E = M;
     double dE = 1.0;
@@ -35,13 +42,15 @@ DPE_HD static inline bool solve_kepler(double M, double e, double &E)  // :97-10
         double sE, cE;
         sincos(E, &sE, &cE);   // glibc: bit-identical to sin() and cos(), one argument reduction
         dE = (M - E + e * sE) / (1.0 - e * cE);
-        E = std::fmod(E + dE, k2Pi);
+        E = mod(E + dE, k2Pi);
     }
     return std::fabs(dE) <= 1e-12;
 }
+DPE_HD static inline bool solve_kepler(double M, double e, double &E) { return solve_kepler_t(M, e, E, ModTrunc()); }
 
 // CHM_Get_Sat_Pos :85-210 -> state {x,y,z,clk bias, vx,vy,vz, clk drift}
-DPE_HD static inline int sat_state(const Eph &p, double tx, double out[8])
+template <class Mod>
+DPE_HD static inline int sat_state_t(const Eph &p, double tx, double out[8], const Mod &mod)
 {
     const double A = p.sqrtA * p.sqrtA;
     const double n = std::sqrt(kMu / (A * A * A)) + p.deln;
@@ -49,24 +58,24 @@ DPE_HD static inline int sat_state(const Eph &p, double tx, double out[8])
     double clkb = p.f2 * tc * tc + p.f1 * tc + p.f0 - p.tgd;
     double tk = half_week(tx - clkb - p.toes);
     double E;
-    if (!solve_kepler(std::fmod(p.M0 + n * tk, k2Pi), p.e, E)) return -1;
+    if (!solve_kepler_t(mod(p.M0 + n * tk, k2Pi), p.e, E, mod)) return -1;
     const double dtr = kRelF * p.e * p.sqrtA * std::sin(E);
     tc = tx - (clkb + dtr) - p.tocs;
     clkb = p.f2 * tc * tc + p.f1 * tc + p.f0 + dtr - p.tgd;
     const double clkd = p.f1 + 2.0 * p.f2 * tc;
     tk = half_week(tx - clkb - p.toes);
-    if (!solve_kepler(std::fmod(p.M0 + n * tk, k2Pi), p.e, E)) return -1;
+    if (!solve_kepler_t(mod(p.M0 + n * tk, k2Pi), p.e, E, mod)) return -1;
     double sE, cE;
     sincos(E, &sE, &cE);
     const double den = 1.0 - p.e * cE;
     const double nu = std::atan2(std::sqrt(1.0 - p.e * p.e) * sE / den, (cE - p.e) / den);
-    double u = std::fmod(nu + p.omg, k2Pi);
+    double u = mod(nu + p.omg, k2Pi);
     double c2, s2;
     sincos(2.0 * u, &s2, &c2);
     u += p.cuc * c2 + p.cus * s2;
     const double r = A * den + p.crc * c2 + p.crs * s2;
     const double inc = p.i0 + p.idot * tk + p.cic * c2 + p.cis * s2;
-    const double Om = std::fmod(p.OMG0 + (p.OMGd - kOEDot) * tk - kOEDot * p.toes, k2Pi);
+    const double Om = mod(p.OMG0 + (p.OMGd - kOEDot) * tk - kOEDot * p.toes, k2Pi);
     double su, cu, sO, cO, si, ci;
     sincos(u, &su, &cu);
     sincos(Om, &sO, &cO);
@@ -93,6 +102,7 @@ DPE_HD static inline int sat_state(const Eph &p, double tx, double out[8])
     out[7] = clkd;
     return 0;
 }
+DPE_HD static inline int sat_state(const Eph &p, double tx, double out[8]) { return sat_state_t(p, tx, out, ModTrunc()); }
 
 struct Chan {
     int prn, cpElaStart, cpElaEnd, cpRef, cpRefTOW;
@@ -239,7 +249,7 @@ DPE_HD static inline void enu2ecef_matrix(const double *xkk1, double Rm[9])
 
 }  // namespace dpe
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__) && !defined(DPE_CHM_ARITH_ONLY)   // (dpe_nav.hip takes the arithmetic above alone)
 namespace dpe {
 
 struct ChmDevState {

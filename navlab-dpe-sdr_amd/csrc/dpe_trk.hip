@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "dpe_common.h"
+#include "dpe_trk_log.h"
 
 namespace dpe {
 
@@ -415,6 +416,25 @@ struct dpe_trk {
     double *corrParams_d = nullptr, *corrOut_d = nullptr;
     long long corrCap = 0;
 };
+
+namespace dpe {
+int trk_log_view(dpe_trk *h, TrkLogView *out)   // dpe_trk_log.h
+{
+    DPE_REQUIRE(h && out, "[ScalarTracker] log view: null argument");
+    *out = TrkLogView{h->log_d, h->logCap, h->nWindows, h->K, h->cfg.prn};
+    return 0;
+}
+int trk_log_load(dpe_trk *h, int nWindows, const double *rows, hipStream_t st)
+{
+    DPE_REQUIRE(h && rows, "[ScalarTracker] load_log: null argument");
+    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->logCap, "[ScalarTracker] load_log: %d windows do not fit the log (capacity %lld)", nWindows, h->logCap);
+    DPE_CHECK_HIP(hipStreamSynchronize(st));
+    DPE_CHECK_HIP(hipMemcpy(h->log_d, rows, (size_t)nWindows * h->K * kTrkLogDoubles * sizeof(double), hipMemcpyHostToDevice));
+    h->nWindows = nWindows;
+    h->haveParams = false;   // the loop state is not part of a log: tracking starts again from dpe_trk_set_params
+    return 0;
+}
+}  // namespace dpe
 
 extern "C" {
 

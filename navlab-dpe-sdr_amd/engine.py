@@ -37,6 +37,7 @@ EXPORTS = [
     "dpe_pipe_commit", "dpe_pipe_lane", "dpe_pipe_set_in_flight", "dpe_pipe_lane_at", "dpe_pipe_results", "dpe_pipe_samples_consumed", "dpe_pipe_join", "dpe_pipe_synchronize",
     "dpe_trk_create", "dpe_trk_destroy", "dpe_trk_set_params", "dpe_trk_track", "dpe_trk_correlate", "dpe_trk_read_log",
     "dpe_trk_read_cp_signs", "dpe_trk_state", "dpe_trk_dev_status",
+    "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
 ]
 
 
@@ -1065,6 +1066,16 @@ class ScalarTracker:
         _check(lib().dpe_trk_read_log(self._h, C.c_int64(first), C.c_int32(n), out.ctypes.data_as(C.POINTER(C.c_double)), _stream(stream)))
         return {name: out[:, :, j].copy() for j, name in enumerate(self.LOG_NAMES)}
 
+    def load_log(self, rows, stream=None):
+        """A saved log back onto the device (Receiver.load_measurement_logs, the log alone): rows {name: [n, K]} with any of
+        LOG_NAMES (the others NaN) become windows [0, n).  Tracking continues only after set_params."""
+        n = len(next(iter(rows.values())))
+        a = np.full((n, len(self.prns), len(self.LOG_NAMES)), np.nan)
+        for name, v in rows.items():
+            a[:, :, self.LOG_NAMES.index(name)] = v
+        _check(lib().dpe_nav_load_log(self._h, C.c_int32(n), a.ctypes.data_as(C.POINTER(C.c_double)), _stream(stream)))
+        self.n_windows = n
+
     def state(self, stream=None):
         st = (TrkChanState * len(self.prns))()
         _check(lib().dpe_trk_state(self._h, st, _stream(stream)))
@@ -1087,6 +1098,142 @@ class ScalarTracker:
     def close(self):
         if self._h:
             lib().dpe_trk_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:            # at interpreter shutdown module globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+class NavDecoded(C.Structure):      # dpe_nav_decoded
+    _fields_ = [("eph", C.c_double * 21), ("week", C.c_int32), ("accuracy", C.c_int32), ("health", C.c_int32), ("iode", C.c_int32),
+                ("iodc", C.c_int32), ("tow", C.c_int32), ("cp", C.c_int64), ("status", C.c_int32), ("nPreambleHits", C.c_int32),
+                ("subframeId", C.c_int32 * 5), ("polarity", C.c_int32 * 5), ("parity", C.c_int32 * 50), ("subframeCp", C.c_int64 * 5)]
+
+
+class NavFix(C.Structure):          # dpe_nav_fix
+    _fields_ = [("X_ECEF", C.c_double * 8), ("rxTime", C.c_double), ("rxTime_a", C.c_double), ("lastUpdate", C.c_double),
+                ("iterations", C.c_int32), ("status", C.c_int32)]
+
+
+NAV_FIX_DTYPE = np.dtype([("X_ECEF", "<f8", (8,)), ("rxTime", "<f8"), ("rxTime_a", "<f8"), ("lastUpdate", "<f8"),
+                          ("iterations", "<i4"), ("status", "<i4")])
+assert NAV_FIX_DTYPE.itemsize == C.sizeof(NavFix)
+
+
+class ScalarNavigator:
+    """The twin's scalar navigation stage for `prns` (dpe_nav_*): nav-message decode of a channel's cp_sign stream
+    (dataparser.py:10-70, ephemeris.py:16-297), the per-epoch fix (naveng.py:10-224) on the host or, for every logged epoch
+    of a ScalarTracker, in one device launch, and the handoff dict the DPE loop starts from (receiver.py:804-875)."""
+    FULL, ASSISTED = 0, 1
+    DEC_FEW_PREAMBLES, DEC_PARITY, DEC_IODE, DEC_POLARITY_FLIP, DEC_CP_SLIP, DEC_NO_HISTORY, DEC_POLARITY_D30, DEC_INCOMPLETE = \
+        1, 2, 4, 8, 16, 32, 64, 128
+    SOL_RANK_POS, SOL_NOT_CONVERGED, SOL_KEPLER, SOL_RANK_VEL = 1, 2, 4, 8
+
+    def __init__(self, prns, ds=1.0):
+        self.prns = [int(p) for p in prns]
+        self._h = C.c_void_p(None)
+        _check(lib().dpe_nav_create(C.c_int32(len(self.prns)), C.c_double(ds), C.byref(self._h)))
+        K = len(self.prns)
+        self.eph = np.full((K, 21), np.nan)
+        self.tow = np.full(K, -1, dtype=np.int32)
+        self.cp_timestamp = np.full(K, -1, dtype=np.int64)
+
+    def decode(self, chan, signs, cp_first=0, mode="full", cp_log=None):
+        """signs: channel `chan`'s cp_sign entries (ScalarTracker.read_cp_signs), the first one of code period cp_first.
+        Returns the decode as a dict; what it found (ephemerides in full mode, the timestamp in both) stays in the navigator."""
+        from .handoff import EPH_FIELDS
+        s = np.ascontiguousarray(signs, dtype=np.int8)
+        out = NavDecoded()
+        cl, ncl = None, 0
+        if cp_log is not None:
+            cl = np.ascontiguousarray(cp_log, dtype=np.float64)
+            ncl = cl.size
+        _check(lib().dpe_nav_decode(self._h, C.c_int32(chan), s.ctypes.data_as(C.POINTER(C.c_int8)), C.c_int64(s.size), C.c_int64(int(cp_first)),
+                                    C.c_int32(self.ASSISTED if mode in ("assisted", self.ASSISTED) else self.FULL),
+                                    cl.ctypes.data_as(C.POINTER(C.c_double)) if cl is not None else None, C.c_int64(ncl), C.byref(out)))
+        eph = np.array(out.eph)
+        d = {name: float(eph[j]) for j, name in enumerate(EPH_FIELDS)}
+        d.update(weeknumber=out.week, accuracy=out.accuracy, health=out.health, IODE=out.iode, IODC=out.iodc,
+                 timestamp=dict(TOW=out.tow, cp=out.cp) if out.cp >= 0 else None, status=out.status, n_preamble_hits=out.nPreambleHits,
+                 subframe_id=np.array(out.subframeId), polarity=np.array(out.polarity), parity=np.array(out.parity).reshape(5, 10),
+                 subframe_cp=np.array(out.subframeCp), eph=eph)
+        complete = mode in ("full", self.FULL) and not out.status & (self.DEC_INCOMPLETE | self.DEC_FEW_PREAMBLES | self.DEC_NO_HISTORY)
+        if complete:
+            self.eph[chan] = eph
+        if out.cp >= 0:
+            self.tow[chan], self.cp_timestamp[chan] = out.tow, out.cp
+        return d
+
+    def set_ephemerides(self, eph=None, tow=None, cp=None):
+        """Caller-supplied ephemerides [K, 21] in handoff.EPH_FIELDS order and / or timestamps (tow [K], cp [K])."""
+        K = len(self.prns)
+        e = t = c = None
+        if eph is not None:
+            e = np.ascontiguousarray(eph, dtype=np.float64)
+            assert e.shape == (K, 21)
+            self.eph[:] = e
+        if tow is not None:
+            t, c = np.ascontiguousarray(tow, dtype=np.int32), np.ascontiguousarray(cp, dtype=np.int64)
+            assert t.shape == (K,) and c.shape == (K,)
+            self.tow[:], self.cp_timestamp[:] = t, c
+        _check(lib().dpe_nav_set_ephemerides(self._h, e.ctypes.data_as(C.POINTER(C.c_double)) if e is not None else None,
+                                             t.ctypes.data_as(C.POINTER(C.c_int32)) if t is not None else None,
+                                             c.ctypes.data_as(C.POINTER(C.c_int64)) if c is not None else None))
+
+    @staticmethod
+    def _mask(chans):
+        m = 0
+        for k in chans or ():
+            m |= 1 << int(k)
+        return C.c_uint64(m)
+
+    @staticmethod
+    def _fix(r):
+        return dict(X_ECEF=np.array(r["X_ECEF"], dtype=np.float64), rxTime=float(r["rxTime"]), rxTime_a=float(r["rxTime_a"]),
+                    last_update=float(r["lastUpdate"]), iterations=int(r["iterations"]), status=int(r["status"]))
+
+    def solve(self, cp, rc, fi, chans=None, rx_time0=None):
+        """One epoch on the host: cp, rc, fi [K] (a row of the tracker's log); chans: the channels to use (None: all)."""
+        dp = C.POINTER(C.c_double)
+        a = [np.ascontiguousarray(v, dtype=np.float64) for v in (cp, rc, fi)]
+        assert all(v.shape == (len(self.prns),) for v in a)
+        out = np.zeros(1, dtype=NAV_FIX_DTYPE)
+        _check(lib().dpe_nav_solve(self._h, a[0].ctypes.data_as(dp), a[1].ctypes.data_as(dp), a[2].ctypes.data_as(dp), self._mask(chans),
+                                   C.c_double(np.nan if rx_time0 is None else rx_time0), out.ctypes.data_as(C.c_void_p)))
+        return self._fix(out[0])
+
+    def solve_log(self, tracker, first=0, n_epochs=None, stride=1, chans=None, rx_time0=None, rx_time_step=0.0, stream=None):
+        """Every epoch first + i * stride, i < n_epochs, of `tracker`'s device-resident log in one launch.  Returns the
+        dpe_nav_fix records as a structured array (NAV_FIX_DTYPE)."""
+        if n_epochs is None:
+            n_epochs = (tracker.n_windows - first + stride - 1) // stride
+        out = np.zeros(int(n_epochs), dtype=NAV_FIX_DTYPE)
+        _check(lib().dpe_nav_solve_log(self._h, tracker._h, C.c_int64(first), C.c_int32(int(n_epochs)), C.c_int32(stride), self._mask(chans),
+                                       C.c_double(np.nan if rx_time0 is None else rx_time0), C.c_double(rx_time_step),
+                                       out.ctypes.data_as(C.c_void_p), _stream(stream)))
+        return out
+
+    def status(self):
+        st = C.c_int32()
+        _check(lib().dpe_nav_status(self._h, C.byref(st)))
+        return st.value
+
+    def handoff(self, fix, rc, ri, fc, fi, cp, bytes_read=0):
+        """The handoff dict (handoff.read_handoff's form) at one epoch: `fix` from solve / one record of solve_log, the
+        channels' rc, ri, fc, fi, cp there (a row of the tracker's log, or its state), the file offset of that window."""
+        f = self._fix(fix) if not isinstance(fix, dict) else fix
+        assert np.all(self.cp_timestamp >= 0) and not np.isnan(self.eph).any(), "a channel has no timestamp or no ephemerides"
+        return dict(rxTime=f["rxTime"], rxTime_a=f["rxTime_a"], X_ECEF=np.array(f["X_ECEF"], dtype=np.float64), bytes_read=int(bytes_read),
+                    prn_list=np.array(self.prns, dtype=np.int32), rc=np.array(rc, dtype=np.float64), ri=np.array(ri, dtype=np.float64),
+                    fc=np.array(fc, dtype=np.float64), fi=np.array(fi, dtype=np.float64), cp=np.array(cp).astype(np.int32),
+                    cp_timestamp=self.cp_timestamp.astype(np.int32), TOW=self.tow.astype(np.int32), eph=self.eph.copy())
+
+    def close(self):
+        if self._h:
+            lib().dpe_nav_destroy(self._h)
             self._h = C.c_void_p(None)
 
     def __del__(self):

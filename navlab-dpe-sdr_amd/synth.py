@@ -119,6 +119,33 @@ def gen_iq_record(seed, fs, n_samples, ch, amp=48.0, sigma=300.0, nav_bits=None)
     return iq, bits_out
 
 
+def gen_iq_record_chunks(seed, fs, n_samples, ch, nav_bits, amp=48.0, sigma=300.0, chunk=1 << 20):
+    """gen_iq_record's record in pieces, so that a record of many seconds needs memory for one piece: yields int16 arrays of
+    up to 2 * chunk interleaved I/Q values, in order.  Signal model, `ch` and the nav-bit convention are gen_iq_record's (sample n
+    at t = n / fs whatever piece it falls in; nav_bits[k][j] as there, and required: the caller knows how many bits its record
+    spans).  The noise of piece i is drawn from PCG64((seed, i)), so the samples depend on `chunk` and are not gen_iq_record's."""
+    K = len(ch["prn"])
+    amp = np.broadcast_to(np.asarray(amp, dtype=np.float64), (K,))
+    chips = [ca_code(int(p)).astype(np.float64) for p in ch["prn"]]
+    bits = [np.asarray(b, dtype=np.int8) for b in nav_bits]
+    for i, n0 in enumerate(range(0, n_samples, chunk)):
+        m = min(chunk, n_samples - n0)
+        rng = np.random.Generator(np.random.PCG64([seed, i]))
+        t = np.arange(n0, n0 + m, dtype=np.float64) / fs
+        x = sigma * (rng.standard_normal(m) + 1j * rng.standard_normal(m))
+        for k in range(K):
+            ci = np.floor(t * ch["fc"][k] + ch["rc"][k]).astype(np.int64)
+            first_edge = int(ch["cp_ref"][k]) % 20 if "cp_ref" in ch else 0
+            bit_idx = (ci // L_CA - first_edge + 20) // 20
+            assert bit_idx[-1] < bits[k].size, "channel %d needs %d nav bits" % (k, int(bit_idx[-1]) + 1)
+            ph = ch["fi"][k] * t + ch["ri"][k]
+            x += amp[k] * bits[k][bit_idx] * chips[k][np.mod(ci, L_CA)] * np.exp(2j * np.pi * (ph - np.floor(ph)))
+        iq = np.empty(2 * m, dtype=np.int16)
+        iq[0::2] = np.clip(np.rint(x.real), -32768, 32767).astype(np.int16)
+        iq[1::2] = np.clip(np.rint(x.imag), -32768, 32767).astype(np.int16)
+        yield iq
+
+
 def rand_grid(seed, G, half=(110.0, 110.0, 110.0, 132.0)):
     """rngrid3-format random ENU-dt grid (SURVEY.md 8d iii): columns x,y,z,delta_t (m)."""
     rng = np.random.Generator(np.random.PCG64(seed))
