@@ -325,6 +325,59 @@ typedef struct dpe_grid_axes {
 } dpe_grid_axes;
 int dpe_bcm_create_axes(const dpe_bcm_config *cfg, const dpe_grid_axes *pos, const dpe_grid_axes *vel, dpe_bcm **out);
 
+/* Several receivers over ONE pair of grids -- PyGNSS' multi receiver mode (Receiver.dp_measurement_estimation[_unfolded](gXk_grid=...),
+ * receiver.py:266-274,337-345,385-388: every receiver scores a caller-supplied grid of full states and the caller sums the rows and takes
+ * one arg-max).  Model: nRx receivers form a rigid set on one oscillator (or have calibrated clock offsets); receiver r has its own centre
+ * state, receive time, tracked SVs and banks (its own dpe_bcs handle); baseline and clock offset live in the centres.  The position and
+ * velocity grids of ENU-dt offsets are shared: grid point j means "every receiver at its centre moved by offset j".  The joint score of a
+ * point is the sum over receivers of the score dpe_bcm_update would give that receiver there; its first maximum is the joint ML offset and
+ * receiver r's measurement is its centre moved by that offset.  One launch scores every (receiver, SV) pair per grid point from LDS --
+ * each grid is read once and one score row is written -- and also yields every receiver's OWN arg-max (a receiver that disagrees with the
+ * joint fix is the multipath flag) and its out-of-window count.
+ * Limits: maxRx <= 8, maxChannelsTotal <= 64 (receiver, SV) pairs per window, cfg->maxChannels (<= 37, <= maxChannelsTotal) bounds one receiver;
+ * maxChannelsTotal * ((2 max(L,B) + 1) * 16 + 32) <= 150 KB (the LDS budget of dpe_bcm_config, applied to the total).  Point-list grids
+ * only; weightedMean, referencePair and grid index offsets must be 0.
+ * On such a handle dpe_bcm_scores / dpe_bcm_scores_pitch / dpe_bcm_keys / dpe_bcm_export_scores_f64 / dpe_bcm_profile work unchanged and
+ * return the JOINT rows and keys (same key format).  Refused, each with a message: dpe_bcm_update / _update_dev / _update_prepared,
+ * dpe_bcm_results, dpe_bcm_results_from_keys and dpe_bcm_exchange_keys (sharding), dpe_bcm_set_graph, dpe_chm_dev_attach (the
+ * device-resident loop). */
+typedef struct dpe_bcm_joint_rx {
+    const float *codeBank_dev;      /* DEVICE: this receiver's code bank rows of this window, float2 [nChan][2L+1] (its dpe_bcs_outputs
+                                     * pointer advanced to the window) */
+    const float *carrBank_dev;      /* DEVICE: float2 [nChan][2B+1] */
+    const dpe_chan_end *chan_host;  /* HOST [nChan], consumed before the call returns */
+    dpe_bcm_window win;             /* its centre, receive time and DopplerSign; enu2ecef bit-equal for all receivers of a window */
+    int32_t nChan;                  /* 1 .. cfg->maxChannels; the sum over a window's receivers <= maxChannelsTotal */
+    int32_t reserved;
+} dpe_bcm_joint_rx;
+typedef struct dpe_bcm_joint_result {
+    int64_t posIndex;               /* first maximum of the joint position / velocity row */
+    int64_t velIndex;
+    float posScore;
+    float velScore;
+    double offset[8];               /* the grid rows at the two maxima: ENU-dt position offset, ENU-dt_dot velocity offset */
+    int64_t posOutOfWindow;         /* (point, receiver, SV) triples whose index left a bank */
+    int64_t velOutOfWindow;
+} dpe_bcm_joint_result;
+typedef struct dpe_bcm_joint_rx_result {
+    double zVal[8];                 /* this receiver's centre moved by the joint offset (BCM_MakePosMeas / MakeVelMeas) */
+    int64_t posIndex;               /* first maximum of this receiver's OWN row: what dpe_bcm_update gives it alone, bit for bit */
+    int64_t velIndex;               /* (-1 / score 0 when the own keys are switched off) */
+    float posScore;
+    float velScore;
+    int64_t posOutOfWindow;         /* its (point, SV) pairs outside its banks */
+    int64_t velOutOfWindow;
+} dpe_bcm_joint_rx_result;
+int dpe_bcm_create_joint(const dpe_bcm_config *cfg, int32_t maxRx, int32_t maxChannelsTotal, dpe_bcm **out);
+/* rx: HOST [nWindows][nRx].  Asynchronous on `stream`.  Every expansion is formed in fp64 about its own receiver's centre with that
+ * receiver's receive time.  An error (differing enu2ecef, too many pairs, ...) is found before anything is launched. */
+int dpe_bcm_update_joint(dpe_bcm *h, int32_t nWindows, int32_t nRx, const dpe_bcm_joint_rx *rx, dpe_stream_t stream);
+/* Waits for the last joint Update.  joint: [nWindows]; perRx: [nWindows][nRx]. */
+int dpe_bcm_results_joint(dpe_bcm *h, dpe_bcm_joint_result *joint, dpe_bcm_joint_rx_result *perRx, dpe_stream_t stream);
+/* Own keys on (default) / off for the following joint Updates: off drops the per-receiver running maxima from the kernel; the joint
+ * rows and keys are the same bits either way, the per-receiver out-of-window counts are kept. */
+int dpe_bcm_joint_set_own_keys(dpe_bcm *h, int32_t enable);
+
 /* ------------------------------------------------------------------ batches in flight ------ */
 /* Several batches of the path on the device at once -- what the reference gets from SampleBlock's 32-slot ring and reader thread
  * (sampleblock.cu:327-447) and from the side streams of BatchCorrScores / BatchCorrManifold (batchcorrscores.h:60-64,

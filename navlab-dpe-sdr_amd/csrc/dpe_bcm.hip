@@ -424,6 +424,7 @@ __global__ __launch_bounds__(256) void bcm_scan_kernel(BcmParamBlock pb, int inl
 }  // namespace dpe
 
 #include "dpe_bcm_axes.h"
+#include "dpe_bcm_joint.h"
 
 namespace dpe {
 
@@ -660,6 +661,15 @@ struct dpe_bcm {
     int axOff[2][4] = {};           // float offsets of the x, y, z, t axes of each manifold in axes_d
     bool axesBorrowed = false;      // axes_d belongs to another lane of the same dpe_pipe
     double *posAx64_d = nullptr, *velAx64_d = nullptr;   // fp64 global axes for a measurement formed on the device (dpe_bcm_hook_get)
+    // several receivers over one pair of grids (dpe_bcm_create_joint): cfg.maxChannels is then the per-receiver bound
+    bool joint = false;
+    int jointMaxRx = 0, jointMaxK = 0;      // receivers and (receiver, SV) pairs per window
+    dpe::JointRxDev *jrx_d = nullptr, *jrxBase_h = nullptr;   // [W][maxRx] per-receiver bank pointers and row ranges; pinned staging ring
+    unsigned long long *own_d = nullptr;    // {own keys [W][2][maxRx], own out-of-window counts [W][2][maxRx]}
+    std::vector<unsigned long long> own_h;
+    std::vector<dpe_bcm_window> jwin_h;     // [W][maxRx] window frames of the last joint Update
+    int lastRx = 0;
+    bool ownKeys = true, lastOwn = false;   // dpe_bcm_joint_set_own_keys; what the last joint Update ran with
     dpe::KernelProfiler prof;  // slot 0: the fused position + velocity scan
     dpe::GraphCache graphs;
 };
@@ -826,6 +836,53 @@ static void allow_big_lds()
     }
 }
 
+// Several receivers over one pair of grids (dpe_bcm_update_joint)
+struct JointLaunch {
+    dpe::ScanSide sp, sv;
+    const dpe::JointRxDev *rx;
+    int nRx, maxRx, maxKT, lp;
+    unsigned long long *keys, *oob, *ownKeys, *ownOob, *clr;
+    int clrN;
+    unsigned int *done;
+    unsigned long long *hostKeys, *hostOob, seq;
+    dim3 grid;
+    size_t lds;
+    hipStream_t st;
+};
+
+template <int LP, bool CP, bool CV, bool OWN>
+static void launch_joint4(const JointLaunch &a)
+{
+    hipLaunchKernelGGL((dpe::bcm_scan_joint_kernel<LP, CP, CV, OWN>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.rx, a.nRx, a.maxRx, a.maxKT, a.lp,
+                       a.keys, a.oob, a.ownKeys, a.ownOob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+}
+
+template <bool CP, bool CV, bool OWN>
+static void launch_joint3(const JointLaunch &a)
+{
+    if (a.lp == 1) launch_joint4<1, CP, CV, OWN>(a);
+    else if (a.lp == 2) launch_joint4<2, CP, CV, OWN>(a);
+    else launch_joint4<0, CP, CV, OWN>(a);
+}
+
+static void launch_joint(bool clampP, bool clampV, bool own, const JointLaunch &a)
+{
+#define DPE_JOINT_PICK(CP, CV) do { if (own) launch_joint3<CP, CV, true>(a); else launch_joint3<CP, CV, false>(a); } while (0)
+    if (clampP) { if (clampV) DPE_JOINT_PICK(true, true); else DPE_JOINT_PICK(true, false); }
+    else { if (clampV) DPE_JOINT_PICK(false, true); else DPE_JOINT_PICK(false, false); }
+#undef DPE_JOINT_PICK
+}
+
+template <int LP>
+static void allow_big_lds_joint()
+{
+#define DPE_JOINT_LDS(CP, CV, OWN) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_joint_kernel<LP, CP, CV, OWN>, \
+                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
+    DPE_JOINT_LDS(true, true, false); DPE_JOINT_LDS(true, false, false); DPE_JOINT_LDS(false, true, false); DPE_JOINT_LDS(false, false, false);
+    DPE_JOINT_LDS(true, true, true); DPE_JOINT_LDS(true, false, true); DPE_JOINT_LDS(false, true, true); DPE_JOINT_LDS(false, false, true);
+#undef DPE_JOINT_LDS
+}
+
 // ---- referencePair mode ---------------------------------------------------------------------
 // The reference forms the neighbour pair as floor(idx) and floor(idx + 1) on idx = base + S k (batchcorrmanifold.cu:1797-1799).
 // For k = 0 and S / 2 = 2^m an index one fp64 step below 2^m has idx + 1 rounding UP to 2^m + 1: the neighbours are two apart and
@@ -973,7 +1030,7 @@ static int ref_pair_fixup(dpe_bcm *h, const float *codeBank_dev, int nWindows, i
 static int bcm_finish_create(dpe_bcm *h, const dpe_bcm_config *cfg, dpe_bcm **out)
 {
     using namespace dpe;
-    const size_t W = cfg->maxWindows, K = cfg->maxChannels;
+    const size_t W = cfg->maxWindows, K = h->joint ? h->jointMaxK : cfg->maxChannels;
     // score rows start on 128-byte lines: a wave's 64 consecutive scores are then two whole lines instead of one whole and two
     // partial ones (config R, 390 625-point rows: 0.779 -> 0.755 ms per step, the write-back of a step's 0.8 GB drains faster)
     h->posPitch = (cfg->posGridSize + 31) / 32 * 32;
@@ -1032,19 +1089,14 @@ static int bcm_finish_create(dpe_bcm *h, const dpe_bcm_config *cfg, dpe_bcm **ou
     return 0;
 }
 
-extern "C" {
-
-int dpe_bcm_create(const dpe_bcm_config *cfg, dpe_bcm **out)
-{
-    return dpe_bcm_create_sharing(cfg, nullptr, out);
-}
-
-// donor != nullptr: a handle for the same configuration and grids as `donor` (a further lane of a dpe_pipe) that uses donor's device
-// copy of the fp32 grids; donor must outlive it.
-int dpe_bcm_create_sharing(const dpe_bcm_config *cfg, dpe_bcm *donor, dpe_bcm **out)
+// Point-list grids.  maxRx > 0: a handle that scans several receivers per window (dpe_bcm_create_joint) -- cfg->maxChannels is
+// then the bound per receiver, maxKTotal the bound on the (receiver, SV) pairs of a window, which is what the LDS holds.
+static int bcm_create_points(const dpe_bcm_config *cfg, dpe_bcm *donor, int maxRx, int maxKTotal, dpe_bcm **out)
 {
     using namespace dpe;
     DPE_REQUIRE(cfg && out, "[BatchCorrManifold] create: null argument");
+    const bool joint = maxRx > 0;
+    const int ldsChannels = joint ? maxKTotal : cfg->maxChannels;
     DPE_REQUIRE(!donor || ((int64_t)donor->posGrid_h.size() == 4 * cfg->posGridSize && (int64_t)donor->velGrid_h.size() == 4 * cfg->velGridSize &&
                            !donor->gridsBorrowed), "[BatchCorrManifold] create: the grids to share are not these grids");
     DPE_REQUIRE(cfg->samplesPerWindow > 0 && (cfg->samplesPerWindow % 2) == 0,
@@ -1059,8 +1111,10 @@ int dpe_bcm_create_sharing(const dpe_bcm_config *cfg, dpe_bcm *donor, dpe_bcm **
                 cfg->velGridSize + cfg->velGridIndexOffset < 0xFFFFFFFFll,
                 "[BatchCorrManifold] create: global grid index exceeds 32 bits");
     const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
-    const size_t ldsNeed = (size_t)cfg->maxChannels * (nEntMax * 16 + 32);
+    const size_t ldsNeed = (size_t)ldsChannels * (nEntMax * 16 + 32);
     const bool compact = ldsNeed > 150 * 1024;   // 12-byte entries (slower scan variant) when the 16-byte ones do not fit
+    DPE_REQUIRE(!joint || !compact, "[BatchCorrManifold] create_joint: the score banks of %d (receiver, SV) pairs x %zu entries (%zu B) exceed the "
+                                    "150 KB the joint scan keeps in LDS", ldsChannels, nEntMax, ldsNeed);
     DPE_REQUIRE(!compact || (size_t)cfg->maxChannels * nEntMax * 12 <= 152 * 1024,
                 "[BatchCorrManifold] create: score banks (%zu B even as 12-byte entries) exceed the 160 KB LDS",
                 (size_t)cfg->maxChannels * nEntMax * 12);
@@ -1083,6 +1137,7 @@ int dpe_bcm_create_sharing(const dpe_bcm_config *cfg, dpe_bcm *donor, dpe_bcm **
     h->cfg = *cfg;
     h->cfg.posGrid = h->cfg.velGrid = nullptr;
     h->compact = compact;
+    h->joint = joint; h->jointMaxRx = maxRx; h->jointMaxK = maxKTotal;
     {
         const int half = cfg->samplesPerWindow / 2;
         h->refPair = cfg->referencePair != 0 && (half & (half - 1)) == 0;   // only then can floor(idx + 1) - floor(idx) be 2
@@ -1104,6 +1159,54 @@ int dpe_bcm_create_sharing(const dpe_bcm_config *cfg, dpe_bcm *donor, dpe_bcm **
         return -1;
     }
     return bcm_finish_create(h, cfg, out);
+}
+
+extern "C" {
+
+int dpe_bcm_create(const dpe_bcm_config *cfg, dpe_bcm **out)
+{
+    return bcm_create_points(cfg, nullptr, 0, 0, out);
+}
+
+// donor != nullptr: a handle for the same configuration and grids as `donor` (a further lane of a dpe_pipe) that uses donor's device
+// copy of the fp32 grids; donor must outlive it.
+int dpe_bcm_create_sharing(const dpe_bcm_config *cfg, dpe_bcm *donor, dpe_bcm **out)
+{
+    return bcm_create_points(cfg, donor, 0, 0, out);
+}
+
+int dpe_bcm_create_joint(const dpe_bcm_config *cfg, int32_t maxRx, int32_t maxChannelsTotal, dpe_bcm **out)
+{
+    using namespace dpe;
+    DPE_REQUIRE(cfg && out, "[BatchCorrManifold] create_joint: null argument");
+    DPE_REQUIRE(maxRx >= 1 && maxRx <= kJointMaxRx, "[BatchCorrManifold] create_joint: maxRx %d out of range (1 .. %d receivers)", maxRx, kJointMaxRx);
+    DPE_REQUIRE(maxChannelsTotal >= 1 && maxChannelsTotal <= kJointMaxK,
+                "[BatchCorrManifold] create_joint: maxChannelsTotal %d out of range (1 .. %d (receiver, SV) pairs)", maxChannelsTotal, kJointMaxK);
+    DPE_REQUIRE(cfg->maxChannels <= maxChannelsTotal, "[BatchCorrManifold] create_joint: maxChannels %d (the bound per receiver) exceeds maxChannelsTotal %d",
+                cfg->maxChannels, maxChannelsTotal);
+    DPE_REQUIRE(!cfg->weightedMean, "[BatchCorrManifold] create_joint: the weighted-mean estimator is not formed for several receivers (weightedMean must be 0)");
+    DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_joint: referencePair is a single-receiver mode (it re-evaluates one receiver's first channel)");
+    DPE_REQUIRE(cfg->posGridIndexOffset == 0 && cfg->velGridIndexOffset == 0,
+                "[BatchCorrManifold] create_joint: grid shards are not supported (the index offsets must be 0)");
+    dpe_bcm *h = nullptr;
+    if (bcm_create_points(cfg, nullptr, maxRx, maxChannelsTotal, &h)) return -1;
+    const size_t W = cfg->maxWindows, n = W * (size_t)maxRx;
+    const auto finish = [&]() -> int {
+        h->jrx_d = dev_alloc<JointRxDev>(n);
+        h->own_d = dev_alloc<unsigned long long>(4 * n);
+        DPE_REQUIRE(h->jrx_d && h->own_d, "[BatchCorrManifold] create_joint: device allocation failed");
+        DPE_CHECK_HIP(hipHostMalloc((void **)&h->jrxBase_h, dpe_bcm::kStaging * n * sizeof(JointRxDev), hipHostMallocDefault));
+        return 0;
+    };
+    if (finish()) {
+        dpe_bcm_destroy(h);
+        return -1;
+    }
+    h->own_h.assign(4 * n, 0ull);
+    h->jwin_h.resize(n);
+    allow_big_lds_joint<0>(); allow_big_lds_joint<1>(); allow_big_lds_joint<2>();
+    *out = h;
+    return 0;
 }
 
 // Grids given by their axes.  donor != nullptr: a further lane of a dpe_pipe, which uses donor's device copy of the axes.
@@ -1210,12 +1313,63 @@ int dpe_bcm_destroy(dpe_bcm *h)
     if (h->keys_h) (void)hipHostFree(h->keys_h);
     if (h->devWin_h) (void)hipHostFree(h->devWin_h);
     if (h->refBank_h) (void)hipHostFree(h->refBank_h);
+    if (h->jrxBase_h) (void)hipHostFree(h->jrxBase_h);
+    (void)hipFree(h->jrx_d); (void)hipFree(h->own_d);
     (void)hipFree(h->refCand_d); (void)hipFree(h->refWhere_d); (void)hipFree(h->refValue_d); (void)hipFree(h->refOld_d);
     for (hipEvent_t e : h->stagingFree)
         if (e) (void)hipEventDestroy(e);
     h->graphs.clear();
     delete h;
     return 0;
+}
+
+// The expansion of one (window, SV) pair about the window's centre, in fp64 (file header): the coefficient blocks of the two
+// manifolds, and whether every index of the pair provably stays inside the banks (cleared, never set).
+static void bcm_expand(const dpe_bcm *h, const dpe_bcm_window &win, const dpe_chan_end &ch, dpe::BcmSvDev &p, dpe::BcmSvDev &v,
+                       bool &posInside, bool &velInside)
+{
+    using namespace dpe;
+    const int S = h->cfg.samplesPerWindow, L = h->cfg.lagHalfWidth, B = h->cfg.binHalfWidth;
+    const double fs = h->cfg.samplingFrequency, Cf = (double)h->cfg.numFFTPoints;
+    const double *c = win.xCurrkk1, *R = win.enu2ecef;
+    const double *s = ch.satState;
+    const double dx = s[0] - c[0], dy = s[1] - c[1], dz = s[2] - c[2];       // :1779-1781
+    const double range = std::sqrt(dx * dx + dy * dy + dz * dz);               // :1782
+    const double ux = dx / range, uy = dy / range, uz = dz / range;
+    const double ue = R[0] * ux + R[3] * uy + R[6] * uz;                        // R^T u
+    const double un = R[1] * ux + R[4] * uy + R[7] * uz;
+    const double uu = R[2] * ux + R[5] * uy + R[8] * uz;
+    // position manifold, centre index (:1783-1791).  Carried in long double: the reference's
+    // fp64 "rxTime - pr/C" (rxTime ~4e5 s) rounds at 5.8e-11 s = 1.4e-4 samples PER POINT; the
+    // expansion below is exact about the centre, so the centre itself is kept exact too.
+    const long double pr = (long double)range - (long double)kC * s[3] + c[3];
+    const long double txT = (long double)win.rxTime - pr / (long double)kC;
+    const long double cfd = txT - ch.cpRefTOW - ((long double)(ch.cpElapsedEnd - ch.cpRef) * (long double)kTCA);
+    const long double rc0 = cfd * (long double)kFCA - ch.codePhaseEnd;
+    const double basePos = (double)(((long double)fs / ch.codeFrequency) * (-rc0) + S / 2.0L);
+    p.ue = (float)ue; p.un = (float)un; p.uu = (float)uu;
+    p.g = (float)(fs * kFCA / (ch.codeFrequency * kC));
+    p.h = (float)(0.5 / range);
+    p.idx0 = (float)(basePos - (double)(S / 2 - L));
+    p.pad0 = p.pad1 = 0.f;
+    {
+        const double reach = std::fabs((double)p.g) * h->posExtent + 1e-3;
+        if (!((double)p.idx0 - reach >= 0.0 && (double)p.idx0 + reach < (double)(2 * L))) posInside = false;
+    }
+    // velocity manifold, centre index (:1917-1936)
+    const double ex = c[4] - kOEDot * c[1], ey = c[5] + kOEDot * c[0], ez = c[6];
+    const double lrr = ux * (ex - s[4]) + uy * (ey - s[5]) + uz * (ez - s[6]);
+    const double fbc = kFL1 * ((lrr - c[7]) / kC + s[7]) / win.dopplerSign;
+    const double baseVel = (Cf / fs) * (fbc - ch.carrierFrequency) + Cf / 2.0;
+    const double gv = (Cf / fs) * kFL1 / (kC * win.dopplerSign);
+    v.ue = (float)ue; v.un = (float)un; v.uu = (float)uu;
+    v.g = (float)(-gv);   // index = idx0 + g (delta_tdot - u . delta_v)
+    v.idx0 = (float)(baseVel - (double)(h->cfg.numFFTPoints / 2 - B));
+    v.h = (float)(-gv * ue); v.pad0 = (float)(-gv * un); v.pad1 = (float)(-gv * uu);   // g u, products formed in fp64
+    {
+        const double reach = std::fabs(gv) * h->velExtent + 1e-3;
+        if (!((double)v.idx0 - reach >= 0.0 && (double)v.idx0 + reach < (double)(2 * B))) velInside = false;
+    }
 }
 
 // win_host == nullptr: one window whose coefficients bcm_prep_kernel has already written to h->sv_d on `stream`
@@ -1226,12 +1380,12 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
     using namespace dpe;
     const bool dev = win_host == nullptr;
     DPE_REQUIRE(h && codeBank_dev && carrBank_dev, "[BatchCorrManifold] Update: null argument");
+    DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");
     DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] Update: nWindows %d out of range", nWindows);
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     hipStream_t stream = (hipStream_t)stream_;
-    const int S = h->cfg.samplesPerWindow, L = h->cfg.lagHalfWidth, B = h->cfg.binHalfWidth;
+    const int L = h->cfg.lagHalfWidth, B = h->cfg.binHalfWidth;
     const int maxK = h->cfg.maxChannels, W = h->cfg.maxWindows;
-    const double fs = h->cfg.samplingFrequency, Cf = (double)h->cfg.numFFTPoints;
     bool posInside = !dev, velInside = !dev;   // every index provably inside the banks?  (device parameters: not known here)
     h->lastDev = dev;
     h->slot = (h->slot + 1) % dpe_bcm::kStaging;          // next staging block; an Update kStaging calls ago may still be copying it
@@ -1241,50 +1395,9 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
         const dpe_bcm_window &win = win_host[w];
         DPE_REQUIRE(win.dopplerSign == 1 || win.dopplerSign == -1, "[BatchCorrManifold] Update: dopplerSign must be +/-1");
         h->win_h[w] = win;
-        const double *c = win.xCurrkk1, *R = win.enu2ecef;
-        for (int k = 0; k < nChan; ++k) {
-            const dpe_chan_end &ch = chan_host[(size_t)w * nChan + k];
-            const double *s = ch.satState;
-            const double dx = s[0] - c[0], dy = s[1] - c[1], dz = s[2] - c[2];       // :1779-1781
-            const double range = std::sqrt(dx * dx + dy * dy + dz * dz);               // :1782
-            const double ux = dx / range, uy = dy / range, uz = dz / range;
-            const double ue = R[0] * ux + R[3] * uy + R[6] * uz;                        // R^T u
-            const double un = R[1] * ux + R[4] * uy + R[7] * uz;
-            const double uu = R[2] * ux + R[5] * uy + R[8] * uz;
-            // position manifold, centre index (:1783-1791).  Carried in long double: the reference's
-            // fp64 "rxTime - pr/C" (rxTime ~4e5 s) rounds at 5.8e-11 s = 1.4e-4 samples PER POINT; the
-            // expansion below is exact about the centre, so the centre itself is kept exact too.
-            const long double pr = (long double)range - (long double)kC * s[3] + c[3];
-            const long double txT = (long double)win.rxTime - pr / (long double)kC;
-            const long double cfd = txT - ch.cpRefTOW - ((long double)(ch.cpElapsedEnd - ch.cpRef) * (long double)kTCA);
-            const long double rc0 = cfd * (long double)kFCA - ch.codePhaseEnd;
-            const double basePos = (double)(((long double)fs / ch.codeFrequency) * (-rc0) + S / 2.0L);
-            BcmSvDev &p = h->sv_h[(size_t)(0 * W + w) * maxK + k];
-            p.ue = (float)ue; p.un = (float)un; p.uu = (float)uu;
-            p.g = (float)(fs * kFCA / (ch.codeFrequency * kC));
-            p.h = (float)(0.5 / range);
-            p.idx0 = (float)(basePos - (double)(S / 2 - L));
-            p.pad0 = p.pad1 = 0.f;
-            {
-                const double reach = std::fabs((double)p.g) * h->posExtent + 1e-3;
-                if (!((double)p.idx0 - reach >= 0.0 && (double)p.idx0 + reach < (double)(2 * L))) posInside = false;
-            }
-            // velocity manifold, centre index (:1917-1936)
-            const double ex = c[4] - kOEDot * c[1], ey = c[5] + kOEDot * c[0], ez = c[6];
-            const double lrr = ux * (ex - s[4]) + uy * (ey - s[5]) + uz * (ez - s[6]);
-            const double fbc = kFL1 * ((lrr - c[7]) / kC + s[7]) / win.dopplerSign;
-            const double baseVel = (Cf / fs) * (fbc - ch.carrierFrequency) + Cf / 2.0;
-            const double gv = (Cf / fs) * kFL1 / (kC * win.dopplerSign);
-            BcmSvDev &v = h->sv_h[(size_t)(1 * W + w) * maxK + k];
-            v.ue = (float)ue; v.un = (float)un; v.uu = (float)uu;
-            v.g = (float)(-gv);   // index = idx0 + g (delta_tdot - u . delta_v)
-            v.idx0 = (float)(baseVel - (double)(h->cfg.numFFTPoints / 2 - B));
-            v.h = (float)(-gv * ue); v.pad0 = (float)(-gv * un); v.pad1 = (float)(-gv * uu);   // g u, products formed in fp64
-            {
-                const double reach = std::fabs(gv) * h->velExtent + 1e-3;
-                if (!((double)v.idx0 - reach >= 0.0 && (double)v.idx0 + reach < (double)(2 * B))) velInside = false;
-            }
-        }
+        for (int k = 0; k < nChan; ++k)
+            bcm_expand(h, win, chan_host[(size_t)w * nChan + k], h->sv_h[(size_t)(0 * W + w) * maxK + k],
+                       h->sv_h[(size_t)(1 * W + w) * maxK + k], posInside, velInside);
     }
     h->lastW = nWindows;
     long long axTiles[2] = {0, 0};
@@ -1415,11 +1528,107 @@ int dpe_bcm_update(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_
     return bcm_update_impl(h, codeBank_dev, carrBank_dev, nWindows, nChan, win_host, chan_host, stream);
 }
 
+// Several receivers over one pair of grids: one launch scores, per grid point, every (receiver, SV) pair of the window.
+int dpe_bcm_update_joint(dpe_bcm *h, int32_t nWindows, int32_t nRx, const dpe_bcm_joint_rx *rx, dpe_stream_t stream_)
+{
+    using namespace dpe;
+    DPE_REQUIRE(h && rx, "[BatchCorrManifold] update_joint: null argument");
+    DPE_REQUIRE(h->joint, "[BatchCorrManifold] update_joint: the handle was not made by dpe_bcm_create_joint");
+    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] update_joint: nWindows %d out of range", nWindows);
+    DPE_REQUIRE(nRx >= 1 && nRx <= h->jointMaxRx, "[BatchCorrManifold] update_joint: nRx %d out of range (the handle holds %d receivers)", nRx, h->jointMaxRx);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int W = h->cfg.maxWindows, maxRx = h->jointMaxRx, maxKT = h->jointMaxK;
+    // everything is checked before anything is staged or launched
+    for (int w = 0; w < nWindows; ++w) {
+        int total = 0;
+        for (int r = 0; r < nRx; ++r) {
+            const dpe_bcm_joint_rx &x = rx[(size_t)w * nRx + r];
+            DPE_REQUIRE(x.codeBank_dev && x.carrBank_dev && x.chan_host, "[BatchCorrManifold] update_joint: window %d receiver %d: null pointer", w, r);
+            DPE_REQUIRE(x.nChan >= 1 && x.nChan <= h->cfg.maxChannels, "[BatchCorrManifold] update_joint: window %d receiver %d: nChan %d out of range (1 .. %d)",
+                        w, r, x.nChan, h->cfg.maxChannels);
+            DPE_REQUIRE(x.win.dopplerSign == 1 || x.win.dopplerSign == -1, "[BatchCorrManifold] update_joint: dopplerSign must be +/-1");
+            DPE_REQUIRE(memcmp(x.win.enu2ecef, rx[(size_t)w * nRx].win.enu2ecef, sizeof(x.win.enu2ecef)) == 0,
+                        "[BatchCorrManifold] update_joint: window %d: receiver %d's enu2ecef differs from receiver 0's (one grid offset must mean one "
+                        "ECEF displacement for every receiver: pass bit-equal matrices)", w, r);
+            total += x.nChan;
+        }
+        DPE_REQUIRE(total <= maxKT, "[BatchCorrManifold] update_joint: window %d has %d (receiver, SV) pairs, the handle holds %d", w, total, maxKT);
+    }
+    bool posInside = true, velInside = true;
+    h->lastDev = false;
+    h->slot = (h->slot + 1) % dpe_bcm::kStaging;
+    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
+    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * W * maxKT;
+    JointRxDev *jrx_h = h->jrxBase_h + (size_t)h->slot * W * maxRx;
+    int ldsRows = 0;
+    for (int w = 0; w < nWindows; ++w) {
+        int kOff = 0;
+        for (int r = 0; r < nRx; ++r) {
+            const dpe_bcm_joint_rx &x = rx[(size_t)w * nRx + r];
+            h->jwin_h[(size_t)w * maxRx + r] = x.win;
+            // each expansion about its own receiver's centre, with that receiver's receive time
+            for (int k = 0; k < x.nChan; ++k)
+                bcm_expand(h, x.win, x.chan_host[k], h->sv_h[(size_t)(0 * W + w) * maxKT + kOff + k], h->sv_h[(size_t)(1 * W + w) * maxKT + kOff + k],
+                           posInside, velInside);
+            jrx_h[(size_t)w * maxRx + r] = JointRxDev{reinterpret_cast<const float2 *>(x.codeBank_dev), reinterpret_cast<const float2 *>(x.carrBank_dev),
+                                                     x.nChan, kOff, 0, 0};
+            kOff += x.nChan;
+        }
+        if (kOff > ldsRows) ldsRows = kOff;
+    }
+    h->lastW = nWindows;
+    h->lastRx = nRx;
+    h->lastOwn = h->ownKeys;
+    h->lastSplit[0] = scan_split(h->cfg.posGridSize, nWindows, h->splitForce);
+    h->lastSplit[1] = scan_split(h->cfg.velGridSize, nWindows, h->splitForce);
+    const int use = h->cur ^ 1;
+    unsigned long long *keys = h->keys_d + (size_t)use * 4 * W, *oob = keys + 2 * W;
+    unsigned long long *other = h->keys_d + (size_t)(use ^ 1) * 4 * W;
+    DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sizeof(BcmSvDev) * 2 * (size_t)W * maxKT, hipMemcpyHostToDevice, stream));
+    DPE_CHECK_HIP(hipMemcpyAsync(h->jrx_d, jrx_h, sizeof(JointRxDev) * (size_t)W * maxRx, hipMemcpyHostToDevice, stream));
+    DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
+    DPE_CHECK_HIP(hipMemsetAsync(h->own_d, 0, sizeof(unsigned long long) * 4 * (size_t)W * maxRx, stream));
+    const int nLag = 2 * h->cfg.lagHalfWidth + 1, nBin = 2 * h->cfg.binHalfWidth + 1;
+    JointLaunch a;
+    a.sp = ScanSide{h->posGrid_d, nullptr, h->sv_d, h->posScores_d, nullptr, h->cfg.posGridSize, 0, h->posPitch, nLag, (int)h->lastSplit[0]};
+    a.sv = ScanSide{h->velGrid_d, nullptr, h->sv_d + (size_t)W * maxKT, h->velScores_d, nullptr, h->cfg.velGridSize, 0, h->velPitch, nBin,
+                    (int)h->lastSplit[1]};
+    a.rx = h->jrx_d; a.nRx = nRx; a.maxRx = maxRx; a.maxKT = maxKT; a.lp = h->cfg.lPower;
+    a.keys = keys; a.oob = oob; a.ownKeys = h->own_d; a.ownOob = h->own_d + 2 * (size_t)W * maxRx; a.clr = other; a.clrN = 4 * W;
+    a.done = h->done_d; a.hostKeys = h->keys_hd; a.hostOob = h->keys_hd + 2 * W;
+    h->lastPublished = true;
+    a.seq = ++h->seq;
+    h->pollable = false;   // (the per-receiver results are fetched behind a stream wait)
+    a.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], nWindows, 2);
+    a.lds = (size_t)ldsRows * (nLag > nBin ? nLag : nBin) * 16;   // <= maxKT rows: inside the budget create checked
+    a.st = stream;
+    h->prof.begin(0, stream);
+    launch_joint(!posInside, !velInside, h->lastOwn, a);
+    h->prof.end(0, stream);
+    {
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) {
+            dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
+            return -1;
+        }
+    }
+    h->cur = use;
+    return 0;
+}
+
+int dpe_bcm_joint_set_own_keys(dpe_bcm *h, int32_t enable)
+{
+    DPE_REQUIRE(h && h->joint, "[BatchCorrManifold] joint_set_own_keys: not a handle of dpe_bcm_create_joint");
+    h->ownKeys = enable != 0;
+    return 0;
+}
+
 int dpe_bcm_update_dev(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, int32_t nChan, const dpe_bcm_ports_dev *ports,
                        double rxTime, dpe_stream_t stream)
 {
     using namespace dpe;
     DPE_REQUIRE(h && ports, "[BatchCorrManifold] Update: null argument");
+    DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");   // (before the prep kernel: a refusal launches nothing)
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     DPE_REQUIRE(!h->refPair || (h->cfg.writeScores && !h->cfg.weightedMean),
                 "[BatchCorrManifold] Update: referencePair with the device ports patches the scores on the device: it needs writeScores and no weightedMean "
@@ -1442,6 +1651,7 @@ int dpe_bcm_update_dev(dpe_bcm *h, const float *codeBank_dev, const float *carrB
 int dpe_bcm_update_prepared(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, int32_t nChan, dpe_stream_t stream)
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] Update: null argument");
+    DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     // referencePair (batchcorrmanifold.cu:1798-1812): the prepared blocks hold expansion coefficients only, so the fp64 re-evaluation
     // reads the port arrays of the channel manager that wrote them (handed over at dpe_chm_dev_attach) -- the same device-side
@@ -1469,6 +1679,7 @@ int dpe_bcm_hook_get(dpe_bcm *h, dpe_bcm_hook *out)
 {
     using namespace dpe;
     DPE_REQUIRE(h && out, "[BatchCorrManifold] hook: null argument");
+    DPE_REQUIRE(!h->joint, "[BatchCorrManifold] hook: a joint handle (dpe_bcm_create_joint) cannot serve the device-resident loop or a dpe_pipe lane");
     const size_t W = h->cfg.maxWindows, maxK = h->cfg.maxChannels;
     if (h->axes && !h->posAx64_d) {   // the global axes in fp64 (a few KB): the measurement kernel decodes its index from them
         dpe_bcm::Axes *ax[2] = {&h->posAx, &h->velAx};
@@ -1529,6 +1740,7 @@ int dpe_bcm_hook_set_publish(dpe_bcm *h, int enable)
 int dpe_bcm_set_graph(dpe_bcm *h, int32_t enable)
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] set_graph: null handle");
+    DPE_REQUIRE(!h->joint || !enable, "[BatchCorrManifold] set_graph: joint Updates (dpe_bcm_update_joint) always launch eagerly");
     h->graphs.enabled = enable != 0;
     if (!enable) h->graphs.clear();
     return 0;
@@ -1589,6 +1801,7 @@ static int fetch_device_frame(dpe_bcm *h)
 int dpe_bcm_results(dpe_bcm *h, dpe_bcm_result *results, dpe_stream_t stream)
 {
     DPE_REQUIRE(h && results && h->lastW > 0, "[BatchCorrManifold] results: no update yet");
+    DPE_REQUIRE(!h->joint, "[BatchCorrManifold] results: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_results_joint");
     // Single-window Updates: the scan's last block writes a sequence word right behind the results in the pinned
     // mirror.  Polling it returns the fix as soon as it lands, without the stream-wait wake-up (a few us of a ~58 us
     // closed-loop window); anything unexpected falls back to the stream wait.
@@ -1644,6 +1857,43 @@ int dpe_bcm_results(dpe_bcm *h, dpe_bcm_result *results, dpe_stream_t stream)
                     "[BatchCorrManifold] results: arg-max index outside the local shard");
         double pt[4], vt[4];
         make_meas(h->win_h[w], grid_point(h, 0, r.posIndex, pt), grid_point(h, 1, r.velIndex, vt), r.zVal);
+    }
+    return 0;
+}
+
+int dpe_bcm_results_joint(dpe_bcm *h, dpe_bcm_joint_result *joint, dpe_bcm_joint_rx_result *perRx, dpe_stream_t stream)
+{
+    DPE_REQUIRE(h && joint && perRx, "[BatchCorrManifold] results_joint: null argument");
+    DPE_REQUIRE(h->joint && h->lastW > 0 && h->lastRx > 0, "[BatchCorrManifold] results_joint: no joint update yet");
+    DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    const int W = h->lastW, nRx = h->lastRx, maxRx = h->jointMaxRx;
+    const size_t Wm = h->cfg.maxWindows, half = 2 * Wm * maxRx;
+    DPE_CHECK_HIP(hipMemcpy(h->own_h.data(), h->own_d, sizeof(unsigned long long) * 2 * half, hipMemcpyDeviceToHost));
+    const unsigned long long *keys = h->keys_h, *oob = h->oob_h;
+    for (int w = 0; w < W; ++w) {
+        dpe_bcm_joint_result &j = joint[w];
+        decode_key(keys[2 * w], &j.posScore, &j.posIndex);
+        decode_key(keys[2 * w + 1], &j.velScore, &j.velIndex);
+        j.posOutOfWindow = (int64_t)oob[2 * w];
+        j.velOutOfWindow = (int64_t)oob[2 * w + 1];
+        DPE_REQUIRE(j.posIndex >= 0 && j.posIndex < h->cfg.posGridSize && j.velIndex >= 0 && j.velIndex < h->cfg.velGridSize,
+                    "[BatchCorrManifold] results_joint: arg-max index outside the grids");
+        const double *pp = h->posGrid_h.data() + 4 * j.posIndex, *vp = h->velGrid_h.data() + 4 * j.velIndex;
+        for (int c = 0; c < 4; ++c) { j.offset[c] = pp[c]; j.offset[4 + c] = vp[c]; }
+        for (int r = 0; r < nRx; ++r) {
+            dpe_bcm_joint_rx_result &o = perRx[(size_t)w * nRx + r];
+            make_meas(h->jwin_h[(size_t)w * maxRx + r], pp, vp, o.zVal);   // this receiver's centre moved by the joint offset
+            const size_t ps = ((size_t)w * 2 + 0) * maxRx + r, vs = ((size_t)w * 2 + 1) * maxRx + r;
+            if (h->lastOwn) {
+                decode_key(h->own_h[ps], &o.posScore, &o.posIndex);
+                decode_key(h->own_h[vs], &o.velScore, &o.velIndex);
+            } else {
+                o.posIndex = o.velIndex = -1;
+                o.posScore = o.velScore = 0.f;
+            }
+            o.posOutOfWindow = (int64_t)h->own_h[half + ps];
+            o.velOutOfWindow = (int64_t)h->own_h[half + vs];
+        }
     }
     return 0;
 }
@@ -1704,6 +1954,7 @@ int dpe_bcm_keys(dpe_bcm *h, const uint64_t **keys_dev)
 int dpe_bcm_exchange_keys(dpe_bcm *h, dpe_comm *c, uint64_t *keys_host, dpe_stream_t stream)
 {
     DPE_REQUIRE(h && c && h->lastW > 0, "[BatchCorrManifold] exchange_keys: no update yet / null communicator");
+    DPE_REQUIRE(!h->joint, "[BatchCorrManifold] exchange_keys: a joint handle (dpe_bcm_create_joint) scans whole grids: sharding is not supported");
     unsigned long long *keys = h->keys_d + (size_t)h->cur * 4 * h->cfg.maxWindows;
     if (dpe_comm_allreduce_max_u64(c, reinterpret_cast<uint64_t *>(keys), 2 * (int64_t)h->lastW, stream)) return -1;
     if (keys_host) {
@@ -1720,6 +1971,7 @@ int dpe_bcm_results_from_keys(dpe_bcm *h, const uint64_t *keys_host, int32_t nWi
 {
     DPE_REQUIRE(h && keys_host && results && (posGridGlobal != nullptr) == (velGridGlobal != nullptr) && (posGridGlobal || h->axes),
                 "[BatchCorrManifold] results_from_keys: null argument (both global grids, or neither for a handle with grid axes)");
+    DPE_REQUIRE(!h->joint, "[BatchCorrManifold] results_from_keys: a joint handle (dpe_bcm_create_joint) scans whole grids: use dpe_bcm_results_joint");
     if (!posGridGlobal) {   // an axes handle decodes from its axes, which are the global ones
         posGridGlobalSize = axes_size(h->posAx);
         velGridGlobalSize = axes_size(h->velAx);

@@ -37,6 +37,7 @@ EXPORTS = [
     "dpe_pipe_commit", "dpe_pipe_lane", "dpe_pipe_set_in_flight", "dpe_pipe_lane_at", "dpe_pipe_results", "dpe_pipe_samples_consumed", "dpe_pipe_join", "dpe_pipe_synchronize",
     "dpe_trk_create", "dpe_trk_destroy", "dpe_trk_set_params", "dpe_trk_track", "dpe_trk_correlate", "dpe_trk_read_log",
     "dpe_trk_read_cp_signs", "dpe_trk_state", "dpe_trk_dev_status",
+    "dpe_bcm_create_joint", "dpe_bcm_update_joint", "dpe_bcm_results_joint", "dpe_bcm_joint_set_own_keys",
     "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
 ]
 
@@ -93,6 +94,21 @@ class BcmResult(C.Structure):
     _fields_ = [("zVal", C.c_double * 8), ("posIndex", C.c_int64), ("velIndex", C.c_int64),
                 ("posScore", C.c_float), ("velScore", C.c_float), ("posOutOfWindow", C.c_int64),
                 ("velOutOfWindow", C.c_int64), ("zValMean", C.c_double * 8), ("weightedSums", (C.c_double * 5) * 2)]
+
+
+class BcmJointRx(C.Structure):      # dpe_bcm_joint_rx
+    _fields_ = [("codeBank_dev", C.c_void_p), ("carrBank_dev", C.c_void_p), ("chan_host", C.POINTER(ChanEnd)), ("win", BcmWindow),
+                ("nChan", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BcmJointResult(C.Structure):  # dpe_bcm_joint_result
+    _fields_ = [("posIndex", C.c_int64), ("velIndex", C.c_int64), ("posScore", C.c_float), ("velScore", C.c_float),
+                ("offset", C.c_double * 8), ("posOutOfWindow", C.c_int64), ("velOutOfWindow", C.c_int64)]
+
+
+class BcmJointRxResult(C.Structure):  # dpe_bcm_joint_rx_result
+    _fields_ = [("zVal", C.c_double * 8), ("posIndex", C.c_int64), ("velIndex", C.c_int64), ("posScore", C.c_float),
+                ("velScore", C.c_float), ("posOutOfWindow", C.c_int64), ("velOutOfWindow", C.c_int64)]
 
 
 CHAN_START_DTYPE = np.dtype([("codePhaseStart", "<f8"), ("carrierPhaseStart", "<f8"), ("codeFrequency", "<f8"),
@@ -589,6 +605,103 @@ class BatchCorrManifold:
             self.Stop()
         except Exception:
             pass
+
+
+class JointManifold(BatchCorrManifold):
+    """Several receivers over one pair of grids (dpe_bcm_create_joint): PyGNSS' multi receiver mode
+    (receiver.py:266-274,337-345,385-388) as one launch.  max_channels bounds one receiver, max_channels_total the
+    (receiver, SV) pairs of a window.  PosScores / VelScores / Keys are the JOINT rows and keys."""
+
+    def __init__(self, SamplingFrequency, samples_per_window, NumFFTPoints, pos_grid, vel_grid, max_rx, max_channels_total, LPower=1,
+                 lag_half_width=8, bin_half_width=48, max_windows=1, max_channels=8, write_scores=True, own_keys=True):
+        super().__init__(SamplingFrequency, samples_per_window, NumFFTPoints, pos_grid, vel_grid, LPower=LPower,
+                         lag_half_width=lag_half_width, bin_half_width=bin_half_width, max_windows=max_windows,
+                         max_channels=max_channels, write_scores=write_scores)
+        if self.axes:
+            raise DpeError("[BatchCorrManifold] create_joint: point-list grids only (GridAxes are not supported)")
+        self.max_rx, self.max_channels_total, self.own_keys = int(max_rx), int(max_channels_total), bool(own_keys)
+        self._nRx = 0
+
+    def Start(self):
+        if self.Started:
+            return 0
+        cfg = _bcm_config(self.S, self.L, self.B, self.LPower, self.max_windows, self.max_channels, self.C, self.fs, self.pos_grid,
+                          self.vel_grid, 0, 0, False, self.write_scores, False, False)
+        _check(lib().dpe_bcm_create_joint(C.byref(cfg), C.c_int32(self.max_rx), C.c_int32(self.max_channels_total), C.byref(self._h)))
+        self._bind_outputs()
+        self.set_own_keys(self.own_keys)
+        return 0
+
+    def set_own_keys(self, enable=True):
+        """Keep (default) or drop the per-receiver arg-max of the following Updates; the joint bits are the same either way."""
+        _check(lib().dpe_bcm_joint_set_own_keys(self._h, C.c_int32(1 if enable else 0)))
+        self.own_keys = bool(enable)
+
+    @staticmethod
+    def pack(rx):
+        """rx: [W][nRx] (or [nRx] for one window) of dicts {code, carr: device pointers to that receiver's bank rows of the
+        window, win: BCM_WINDOW_DTYPE scalar / [1], chan: CHAN_END_DTYPE [K_r]} -> the dpe_bcm_joint_rx array Update takes
+        (a caller that repeats an Update packs once)."""
+        if rx and isinstance(rx[0], dict):
+            rx = [rx]
+        W, nRx = len(rx), len(rx[0])
+        arr = (BcmJointRx * (W * nRx))()
+        keep = []
+        for w, row in enumerate(rx):
+            if len(row) != nRx:
+                raise DpeError("[BatchCorrManifold] update_joint: every window needs the same number of receivers")
+            for r, d in enumerate(row):
+                chan = np.ascontiguousarray(d["chan"], dtype=CHAN_END_DTYPE).reshape(-1)
+                win = np.ascontiguousarray(np.atleast_1d(d["win"]), dtype=BCM_WINDOW_DTYPE)
+                keep += [chan, win]
+                a = arr[w * nRx + r]
+                a.codeBank_dev, a.carrBank_dev = _ptr(d["code"]).value, _ptr(d["carr"]).value
+                a.chan_host = chan.ctypes.data_as(C.POINTER(ChanEnd))
+                C.memmove(C.byref(a.win), win.ctypes.data, C.sizeof(BcmWindow))
+                a.nChan, a.reserved = chan.shape[0], 0
+        return (arr, keep, W, nRx)
+
+    def Update(self, rx, stream=None):
+        """rx: what pack() takes, or its result."""
+        if not self.Started:
+            raise DpeError("[BatchCorrManifold] Error: Update() Failed due to module not initialized")
+        arr, _keep, W, nRx = rx if isinstance(rx, tuple) else self.pack(rx)
+        _check(lib().dpe_bcm_update_joint(self._h, C.c_int32(W), C.c_int32(nRx), arr, _stream(stream)))
+        self._W, self._nRx = W, nRx
+        keys = C.c_void_p()
+        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
+        self.Keys = keys.value
+        return 0
+
+    def results(self, stream=None):
+        """-> per window a dict: the joint arg-max (posIndex, velIndex, posScore, velScore, offset[8], out-of-window counts) and
+        rx = [per receiver: zVal (its centre moved by the joint offset), its own arg-max and out-of-window counts]."""
+        jr = (BcmJointResult * self._W)()
+        pr = (BcmJointRxResult * (self._W * self._nRx))()
+        _check(lib().dpe_bcm_results_joint(self._h, jr, pr, _stream(stream)))
+        out = []
+        for w, j in enumerate(jr):
+            rxs = [dict(zVal=np.array(o.zVal), RVal=np.eye(8), posIndex=o.posIndex, velIndex=o.velIndex, posScore=o.posScore,
+                        velScore=o.velScore, posOutOfWindow=o.posOutOfWindow, velOutOfWindow=o.velOutOfWindow)
+                   for o in pr[w * self._nRx:(w + 1) * self._nRx]]
+            out.append(dict(posIndex=j.posIndex, velIndex=j.velIndex, posScore=j.posScore, velScore=j.velScore,
+                            offset=np.array(j.offset), posOutOfWindow=j.posOutOfWindow, velOutOfWindow=j.velOutOfWindow, rx=rxs))
+        return out
+
+    def read_keys(self, stream=None):
+        """The joint packed keys of the last Update, uint64 [W, 2] (dpe_bcm_keys)."""
+        return d2h(self.Keys, self._W * 2 * 8, np.uint64, stream).reshape(self._W, 2)
+
+    def UpdateDev(self, *a, **k):
+        raise DpeError("[BatchCorrManifold] a joint handle takes its inputs through Update(rx) only")
+
+    UpdatePrepared = exchange_keys = results_from_keys = UpdateDev
+
+
+def bank_rows(bcs, window=0):
+    """Device pointers to window `window` of a BatchCorrScores' code and carrier banks (JointManifold.Update's code / carr)."""
+    return (bcs.CodeScores + window * bcs.max_channels * (2 * bcs.L + 1) * 8,
+            bcs.CarrScores + window * bcs.max_channels * (2 * bcs.B + 1) * 8)
 
 
 class Pipe:

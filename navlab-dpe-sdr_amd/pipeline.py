@@ -119,3 +119,66 @@ def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
     bcm.Stop()
     bcs.Stop()
     return fixes, results, status
+
+
+def run_joint_closed_loop(iq_windows_per_rx, handoffs, fs, pos_grid, vel_grid, time_grid=(0.0,), init_delta=(0, 0, 0, 0), lpower=1,
+                          lag_half_width=None, bin_half_width=None, own_keys=True, keep_scores=False):
+    """The closed loop for a rigid set of receivers (engine.JointManifold): iq_windows_per_rx[r] = int16 [W, 2S] of receiver r,
+    handoffs[r] its handoff state (its own SVs and X_ECEF: baseline and clock offset live there).  One host ChanMgr and one
+    BatchCorrScores per receiver, ONE joint scan per window over the shared grids; every receiver's state is then updated with
+    its own zVal (its centre moved by the joint ML offset; pass-through filter).  All receivers of a window are given receiver
+    0's ENU->ECEF matrix, so that one grid offset is one ECEF displacement for the whole set.  init_delta: a common ECEF / clock
+    offset added to every receiver's initial state.  Returns fixes [W, N, 8] and the per-window joint result dicts."""
+    import torch
+    N = len(handoffs)
+    iqs = [np.ascontiguousarray(q) for q in iq_windows_per_rx]
+    W, S2 = iqs[0].shape
+    S = S2 // 2
+    Ks = [len(ho["prn_list"]) for ho in handoffs]
+    nfft = engine.carr_fft_len(S)
+    L, B = bank_half_widths(pos_grid, vel_grid, fs, nfft)
+    L = L if lag_half_width is None else int(lag_half_width)
+    B = B if bin_half_width is None else int(bin_half_width)
+    bcss = [engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_channels=K) for K in Ks]
+    bcm = engine.JointManifold(fs, S, nfft, pos_grid, vel_grid, N, sum(Ks), LPower=lpower, lag_half_width=L,
+                               bin_half_width=B, max_channels=max(Ks), own_keys=own_keys)
+    cms = []
+    try:
+        for b in bcss:
+            b.Start()
+        bcm.Start()
+        cms = [engine.ChanMgr.from_handoff(ho, S / fs, K) for ho, K in zip(handoffs, Ks)]
+        xs = []
+        for ho in handoffs:
+            x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
+            x[:4] += np.asarray(init_delta, dtype=np.float64)
+            xs.append(x)
+        iq_d = [torch.from_numpy(q).to("cuda:0") for q in iqs]
+        fixes, results = np.zeros((W, N, 8)), []
+        for w in range(W):
+            rx = []
+            for r in range(N):
+                (cms[r].Start if w == 0 else cms[r].Update)(xs[r], xs[r], time_grid)
+                cs, ce, bw = cms[r].outputs()
+                bw = bw.copy()
+                if r:
+                    bw["enu2ecef"] = rx[0]["win"]["enu2ecef"]
+                bcss[r].Update(iq_d[r][w], cs)
+                code, carr = engine.bank_rows(bcss[r])
+                rx.append(dict(code=code, carr=carr, win=bw, chan=ce))
+            bcm.Update(rx)
+            res = bcm.results()[0]
+            if keep_scores:
+                ps, vs = bcm.read_scores()
+                res["posScores"], res["velScores"] = ps[0].copy(), vs[0].copy()
+            for r in range(N):
+                xs[r] = res["rx"][r]["zVal"].copy()
+                fixes[w, r] = xs[r]
+            results.append(res)
+    finally:      # an error in the middle of the loop must not leave N + 1 device handles behind
+        for c in cms:
+            c.Stop()
+        bcm.Stop()
+        for b in bcss:
+            b.Stop()
+    return fixes, results
