@@ -378,6 +378,51 @@ int dpe_bcm_results_joint(dpe_bcm *h, dpe_bcm_joint_result *joint, dpe_bcm_joint
  * rows and keys are the same bits either way, the per-receiver out-of-window counts are kept. */
 int dpe_bcm_joint_set_own_keys(dpe_bcm *h, int32_t enable);
 
+/* N consecutive windows (epochs) of ONE receiver summed into one score row and one arg-max -- non-coherent accumulation over epochs, the
+ * reason to choose Direct Position Estimation for weak and partly blocked signals: at ~30 dB-Hz the manifold maximum of a single window is a
+ * noise peak, the maximum of the sum over the predicted trajectory is not.  This is the joint model with epochs in place of receivers.  A launch
+ * carries nGroups groups of nEpochs consecutive windows (nGroups * nEpochs <= cfg->maxWindows); window e of a group has its own dpe_bcm_window
+ * (centre, enu2ecef, rxTime, dopplerSign), its own dpe_chan_end[nChan] and its own bank rows, exactly as it would be handed to dpe_bcm_update,
+ * and is expanded in fp64 about its own centre with its own matrix and receive time (the matrices need not be equal).  Grid point j means "the
+ * whole predicted trajectory moved by offset j"; the group's score at j, per manifold, is the sum over its windows of the score dpe_bcm_update
+ * gives that window at j (each window summed over its SVs from 0 in SV order, the windows added in window order); the key is the first maximum
+ * of that sum in the packed key format; zVal is the LAST window's centre moved by the ML offset through that window's matrix
+ * (BCM_MakePosMeas / MakeVelMeas); the out-of-window count is the sum of the windows' counts.  A group of one window gives the rows, keys,
+ * fix and counts of dpe_bcm_update bit for bit.
+ * Passes: the (window, SV) coefficients are read by scalar loads from a device array, so only the LDS bounds the pairs scored together:
+ * a group is scanned in passes of whole windows, each within pairs * ((2 max(L,B) + 1) * 16 + 32) <= 150 KB (the LDS budget of dpe_bcm_config);
+ * the running sum lives in the group's fp32 score row between passes (writeScores is forced on: the row is the accumulator), which every
+ * lane reads back where it stored it.  A group's bits do not depend on how its windows are cut into passes, and a launch of G groups gives
+ * the bits of G launches of one group.  A sum is not carried across launches: a group lies within one launch.
+ * Limits: point-list grids only; weightedMean, referencePair and the grid index offsets must be 0; 1 <= maxEpochs <= cfg->maxWindows;
+ * pairsPerPass = 0: as many whole windows per pass as the budget holds, > 0: a cap on the pairs of a pass (rounded down to whole windows; for
+ * tests and for measuring the price of a pass), refused below cfg->maxChannels; bank sets that would need the 12-byte LDS entries for even
+ * one window are refused.
+ * On such a handle dpe_bcm_scores / dpe_bcm_scores_pitch / dpe_bcm_keys / dpe_bcm_export_scores_f64 / dpe_bcm_profile work unchanged on the
+ * GROUP rows and keys (one row and one key pair per group, same key format).  Refused, each with a message: dpe_bcm_update / _update_dev /
+ * _update_prepared, dpe_bcm_results, dpe_bcm_results_from_keys and dpe_bcm_exchange_keys (sharding), dpe_bcm_set_graph, dpe_chm_dev_attach
+ * (the device-resident loop) and the joint calls; the calls below are refused on every other kind of handle. */
+typedef struct dpe_bcm_epochs_result {
+    double zVal[8];                 /* the group's LAST window's centre moved by the ML offset (BCM_MakePosMeas / MakeVelMeas) */
+    double offset[8];               /* the grid rows at the two maxima: ENU-dt position offset, ENU-dt_dot velocity offset */
+    int64_t posIndex;               /* first maximum of the group's position / velocity row */
+    int64_t velIndex;
+    float posScore;
+    float velScore;
+    int64_t posOutOfWindow;         /* (point, window, SV) triples whose index left a bank */
+    int64_t velOutOfWindow;
+    int32_t nPasses;                /* passes the group was scanned in */
+    int32_t reserved;
+} dpe_bcm_epochs_result;
+int dpe_bcm_create_epochs(const dpe_bcm_config *cfg, int32_t maxEpochs, int32_t pairsPerPass, dpe_bcm **out);
+/* Arrays as for dpe_bcm_update over nGroups * nEpochs windows, group-major: win_host [nGroups * nEpochs], chan_host [nGroups * nEpochs][nChan],
+ * banks = the dpe_bcs_outputs pointers of a stage-1 call over the same windows.  Asynchronous on `stream`; the host arrays are consumed before
+ * the call returns.  A bad nGroups * nEpochs, nEpochs > maxEpochs or nChan is found before anything is launched. */
+int dpe_bcm_update_epochs(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, int32_t nGroups, int32_t nEpochs, int32_t nChan,
+                          const dpe_bcm_window *win_host, const dpe_chan_end *chan_host, dpe_stream_t stream);
+/* Waits for the last epochs Update.  results: [nGroups]. */
+int dpe_bcm_results_epochs(dpe_bcm *h, dpe_bcm_epochs_result *results, dpe_stream_t stream);
+
 /* ------------------------------------------------------------------ batches in flight ------ */
 /* Several batches of the path on the device at once -- what the reference gets from SampleBlock's 32-slot ring and reader thread
  * (sampleblock.cu:327-447) and from the side streams of BatchCorrScores / BatchCorrManifold (batchcorrscores.h:60-64,

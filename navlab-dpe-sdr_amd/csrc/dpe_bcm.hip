@@ -425,6 +425,7 @@ __global__ __launch_bounds__(256) void bcm_scan_kernel(BcmParamBlock pb, int inl
 
 #include "dpe_bcm_axes.h"
 #include "dpe_bcm_joint.h"
+#include "dpe_bcm_epochs.h"
 
 namespace dpe {
 
@@ -670,6 +671,10 @@ struct dpe_bcm {
     std::vector<dpe_bcm_window> jwin_h;     // [W][maxRx] window frames of the last joint Update
     int lastRx = 0;
     bool ownKeys = true, lastOwn = false;   // dpe_bcm_joint_set_own_keys; what the last joint Update ran with
+    // N consecutive windows summed into one row and one arg-max (dpe_bcm_create_epochs): lastW then counts GROUPS
+    bool epochs = false;
+    int epMaxEpochs = 0, epPairsPerPass = 0;   // windows per group; (window, SV) pairs whose banks share the LDS in one pass
+    int lastEpochs = 0, lastPasses = 0;     // what the last epochs Update ran with
     dpe::KernelProfiler prof;  // slot 0: the fused position + velocity scan
     dpe::GraphCache graphs;
 };
@@ -881,6 +886,44 @@ static void allow_big_lds_joint()
     DPE_JOINT_LDS(true, true, false); DPE_JOINT_LDS(true, false, false); DPE_JOINT_LDS(false, true, false); DPE_JOINT_LDS(false, false, false);
     DPE_JOINT_LDS(true, true, true); DPE_JOINT_LDS(true, false, true); DPE_JOINT_LDS(false, true, true); DPE_JOINT_LDS(false, false, true);
 #undef DPE_JOINT_LDS
+}
+
+// N consecutive windows per score row (dpe_bcm_update_epochs)
+struct EpochsLaunch {
+    dpe::ScanSide sp, sv;
+    int nEpochs, winPerPass, K, maxK, lp;
+    unsigned long long *keys, *oob, *clr;
+    int clrN;
+    unsigned int *done;
+    unsigned long long *hostKeys, *hostOob, seq;
+    dim3 grid;
+    size_t lds;
+    hipStream_t st;
+};
+
+template <int LP, bool CP, bool CV>
+static void launch_epochs3(const EpochsLaunch &a)
+{
+    hipLaunchKernelGGL((dpe::bcm_scan_epochs_kernel<LP, CP, CV>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.nEpochs, a.winPerPass, a.K, a.maxK, a.lp,
+                       a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+}
+
+static void launch_epochs(bool clampP, bool clampV, const EpochsLaunch &a)
+{
+#define DPE_EPOCHS_PICK(CP, CV) do { if (a.lp == 1) launch_epochs3<1, CP, CV>(a); else if (a.lp == 2) launch_epochs3<2, CP, CV>(a); \
+                                     else launch_epochs3<0, CP, CV>(a); } while (0)
+    if (clampP) { if (clampV) DPE_EPOCHS_PICK(true, true); else DPE_EPOCHS_PICK(true, false); }
+    else { if (clampV) DPE_EPOCHS_PICK(false, true); else DPE_EPOCHS_PICK(false, false); }
+#undef DPE_EPOCHS_PICK
+}
+
+template <int LP>
+static void allow_big_lds_epochs()
+{
+#define DPE_EPOCHS_LDS(CP, CV) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_epochs_kernel<LP, CP, CV>, \
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
+    DPE_EPOCHS_LDS(true, true); DPE_EPOCHS_LDS(true, false); DPE_EPOCHS_LDS(false, true); DPE_EPOCHS_LDS(false, false);
+#undef DPE_EPOCHS_LDS
 }
 
 // ---- referencePair mode ---------------------------------------------------------------------
@@ -1209,6 +1252,41 @@ int dpe_bcm_create_joint(const dpe_bcm_config *cfg, int32_t maxRx, int32_t maxCh
     return 0;
 }
 
+// N consecutive windows per score row and arg-max (dpe_bcm_epochs.h).  The LDS budget rule of dpe_bcm_config bounds the (window, SV)
+// pairs of ONE PASS; a group of any length up to maxEpochs is scanned in as many passes as that takes.
+int dpe_bcm_create_epochs(const dpe_bcm_config *cfg, int32_t maxEpochs, int32_t pairsPerPass, dpe_bcm **out)
+{
+    using namespace dpe;
+    DPE_REQUIRE(cfg && out, "[BatchCorrManifold] create_epochs: null argument");
+    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
+                "[BatchCorrManifold] create_epochs: maxWindows/maxChannels out of range");
+    DPE_REQUIRE(maxEpochs >= 1 && maxEpochs <= cfg->maxWindows, "[BatchCorrManifold] create_epochs: maxEpochs %d out of range (1 .. maxWindows = %d)",
+                maxEpochs, cfg->maxWindows);
+    DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1, "[BatchCorrManifold] create_epochs: bad L/B");
+    DPE_REQUIRE(!cfg->weightedMean, "[BatchCorrManifold] create_epochs: the weighted-mean estimator is not formed for summed windows (weightedMean must be 0)");
+    DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_epochs: referencePair is a single-window mode (it re-evaluates one window's first channel)");
+    DPE_REQUIRE(cfg->posGridIndexOffset == 0 && cfg->velGridIndexOffset == 0,
+                "[BatchCorrManifold] create_epochs: grid shards are not supported (the index offsets must be 0)");
+    const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
+    const size_t budget = (size_t)150 * 1024 / (nEntMax * 16 + 32);   // pairs * ((2 max(L, B) + 1) * 16 + 32) <= 150 KB
+    DPE_REQUIRE(budget >= (size_t)cfg->maxChannels, "[BatchCorrManifold] create_epochs: the score banks of one window (%d channels x %zu entries, %zu B) exceed "
+                                                    "the 150 KB the epochs scan keeps in LDS (no 12-byte bank entries here)",
+                cfg->maxChannels, nEntMax, (size_t)cfg->maxChannels * (nEntMax * 16 + 32));
+    DPE_REQUIRE(pairsPerPass == 0 || pairsPerPass >= cfg->maxChannels,
+                "[BatchCorrManifold] create_epochs: pairsPerPass %d is below maxChannels %d (a pass holds whole windows; 0 = as many as the LDS holds)",
+                pairsPerPass, cfg->maxChannels);
+    dpe_bcm_config c = *cfg;
+    c.writeScores = 1;   // the score row is the accumulator
+    dpe_bcm *h = nullptr;
+    if (bcm_create_points(&c, nullptr, 0, 0, &h)) return -1;
+    h->epochs = true;
+    h->epMaxEpochs = maxEpochs;
+    h->epPairsPerPass = (pairsPerPass > 0 && (size_t)pairsPerPass < budget) ? pairsPerPass : (int)budget;
+    allow_big_lds_epochs<0>(); allow_big_lds_epochs<1>(); allow_big_lds_epochs<2>();
+    *out = h;
+    return 0;
+}
+
 // Grids given by their axes.  donor != nullptr: a further lane of a dpe_pipe, which uses donor's device copy of the axes.
 int dpe_bcm_create_axes_sharing(const dpe_bcm_config *cfg, const dpe_grid_axes *pos, const dpe_grid_axes *vel, dpe_bcm *donor,
                                 dpe_bcm **out)
@@ -1381,6 +1459,7 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
     const bool dev = win_host == nullptr;
     DPE_REQUIRE(h && codeBank_dev && carrBank_dev, "[BatchCorrManifold] Update: null argument");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");
+    DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] Update: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_update_epochs");
     DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] Update: nWindows %d out of range", nWindows);
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     hipStream_t stream = (hipStream_t)stream_;
@@ -1616,6 +1695,77 @@ int dpe_bcm_update_joint(dpe_bcm *h, int32_t nWindows, int32_t nRx, const dpe_bc
     return 0;
 }
 
+// N consecutive windows per group: one launch scores, per grid point, every (window, SV) pair of the group, in passes of whole
+// windows whose banks fit the LDS together (dpe_bcm_epochs.h).
+int dpe_bcm_update_epochs(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, int32_t nGroups, int32_t nEpochs, int32_t nChan,
+                          const dpe_bcm_window *win_host, const dpe_chan_end *chan_host, dpe_stream_t stream_)
+{
+    using namespace dpe;
+    DPE_REQUIRE(h && codeBank_dev && carrBank_dev && win_host && chan_host, "[BatchCorrManifold] update_epochs: null argument");
+    DPE_REQUIRE(h->epochs, "[BatchCorrManifold] update_epochs: the handle was not made by dpe_bcm_create_epochs");
+    // everything is checked before anything is staged or launched
+    DPE_REQUIRE(nEpochs >= 1 && nEpochs <= h->epMaxEpochs, "[BatchCorrManifold] update_epochs: nEpochs %d out of range (the handle holds %d windows per group)",
+                nEpochs, h->epMaxEpochs);
+    DPE_REQUIRE(nGroups >= 1 && (long long)nGroups * nEpochs <= h->cfg.maxWindows,
+                "[BatchCorrManifold] update_epochs: %d groups of %d windows out of range (maxWindows %d)", nGroups, nEpochs, h->cfg.maxWindows);
+    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] update_epochs: nChan %d out of range", nChan);
+    const int nWin = nGroups * nEpochs;
+    for (int w = 0; w < nWin; ++w)
+        DPE_REQUIRE(win_host[w].dopplerSign == 1 || win_host[w].dopplerSign == -1, "[BatchCorrManifold] update_epochs: dopplerSign must be +/-1");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int maxK = h->cfg.maxChannels, W = h->cfg.maxWindows;
+    bool posInside = true, velInside = true;
+    h->lastDev = false;
+    h->slot = (h->slot + 1) % dpe_bcm::kStaging;
+    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
+    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * W * maxK;
+    for (int w = 0; w < nWin; ++w) {
+        h->win_h[w] = win_host[w];
+        // each expansion about its own window's centre, with that window's matrix and receive time
+        for (int k = 0; k < nChan; ++k)
+            bcm_expand(h, win_host[w], chan_host[(size_t)w * nChan + k], h->sv_h[(size_t)(0 * W + w) * maxK + k], h->sv_h[(size_t)(1 * W + w) * maxK + k],
+                       posInside, velInside);
+    }
+    const int winPerPass = std::min(h->epPairsPerPass / nChan, (int)nEpochs);   // >= 1: epPairsPerPass >= maxChannels >= nChan
+    h->lastW = nGroups;
+    h->lastEpochs = nEpochs;
+    h->lastPasses = (nEpochs + winPerPass - 1) / winPerPass;
+    h->lastSplit[0] = scan_split(h->cfg.posGridSize, nGroups, h->splitForce);
+    h->lastSplit[1] = scan_split(h->cfg.velGridSize, nGroups, h->splitForce);
+    const int use = h->cur ^ 1;
+    unsigned long long *keys = h->keys_d + (size_t)use * 4 * W, *oob = keys + 2 * W;
+    unsigned long long *other = h->keys_d + (size_t)(use ^ 1) * 4 * W;
+    DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sizeof(BcmSvDev) * 2 * (size_t)W * maxK, hipMemcpyHostToDevice, stream));
+    DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
+    const int nLag = 2 * h->cfg.lagHalfWidth + 1, nBin = 2 * h->cfg.binHalfWidth + 1;
+    EpochsLaunch a;
+    a.sp = ScanSide{h->posGrid_d, reinterpret_cast<const float2 *>(codeBank_dev), h->sv_d, h->posScores_d, nullptr, h->cfg.posGridSize, 0, h->posPitch, nLag,
+                    (int)h->lastSplit[0]};
+    a.sv = ScanSide{h->velGrid_d, reinterpret_cast<const float2 *>(carrBank_dev), h->sv_d + (size_t)W * maxK, h->velScores_d, nullptr, h->cfg.velGridSize, 0,
+                    h->velPitch, nBin, (int)h->lastSplit[1]};
+    a.nEpochs = nEpochs; a.winPerPass = winPerPass; a.K = nChan; a.maxK = maxK; a.lp = h->cfg.lPower;
+    a.keys = keys; a.oob = oob; a.clr = other; a.clrN = 4 * W;
+    a.done = h->done_d; a.hostKeys = h->keys_hd; a.hostOob = h->keys_hd + 2 * W;
+    h->lastPublished = true;
+    a.seq = ++h->seq;
+    h->pollable = false;
+    a.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], nGroups, 2);
+    a.lds = (size_t)winPerPass * nChan * (nLag > nBin ? nLag : nBin) * 16;   // <= epPairsPerPass pairs: inside the budget create checked
+    a.st = stream;
+    h->prof.begin(0, stream);
+    launch_epochs(!posInside, !velInside, a);
+    h->prof.end(0, stream);
+    {
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) {
+            dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
+            return -1;
+        }
+    }
+    h->cur = use;
+    return 0;
+}
+
 int dpe_bcm_joint_set_own_keys(dpe_bcm *h, int32_t enable)
 {
     DPE_REQUIRE(h && h->joint, "[BatchCorrManifold] joint_set_own_keys: not a handle of dpe_bcm_create_joint");
@@ -1629,6 +1779,7 @@ int dpe_bcm_update_dev(dpe_bcm *h, const float *codeBank_dev, const float *carrB
     using namespace dpe;
     DPE_REQUIRE(h && ports, "[BatchCorrManifold] Update: null argument");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");   // (before the prep kernel: a refusal launches nothing)
+    DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] Update: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_update_epochs");
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     DPE_REQUIRE(!h->refPair || (h->cfg.writeScores && !h->cfg.weightedMean),
                 "[BatchCorrManifold] Update: referencePair with the device ports patches the scores on the device: it needs writeScores and no weightedMean "
@@ -1680,6 +1831,7 @@ int dpe_bcm_hook_get(dpe_bcm *h, dpe_bcm_hook *out)
     using namespace dpe;
     DPE_REQUIRE(h && out, "[BatchCorrManifold] hook: null argument");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] hook: a joint handle (dpe_bcm_create_joint) cannot serve the device-resident loop or a dpe_pipe lane");
+    DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] hook: an epochs handle (dpe_bcm_create_epochs) cannot serve the device-resident loop or a dpe_pipe lane");
     const size_t W = h->cfg.maxWindows, maxK = h->cfg.maxChannels;
     if (h->axes && !h->posAx64_d) {   // the global axes in fp64 (a few KB): the measurement kernel decodes its index from them
         dpe_bcm::Axes *ax[2] = {&h->posAx, &h->velAx};
@@ -1741,6 +1893,7 @@ int dpe_bcm_set_graph(dpe_bcm *h, int32_t enable)
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] set_graph: null handle");
     DPE_REQUIRE(!h->joint || !enable, "[BatchCorrManifold] set_graph: joint Updates (dpe_bcm_update_joint) always launch eagerly");
+    DPE_REQUIRE(!h->epochs || !enable, "[BatchCorrManifold] set_graph: epochs Updates (dpe_bcm_update_epochs) always launch eagerly");
     h->graphs.enabled = enable != 0;
     if (!enable) h->graphs.clear();
     return 0;
@@ -1802,6 +1955,7 @@ int dpe_bcm_results(dpe_bcm *h, dpe_bcm_result *results, dpe_stream_t stream)
 {
     DPE_REQUIRE(h && results && h->lastW > 0, "[BatchCorrManifold] results: no update yet");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] results: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_results_joint");
+    DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] results: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_results_epochs");
     // Single-window Updates: the scan's last block writes a sequence word right behind the results in the pinned
     // mirror.  Polling it returns the fix as soon as it lands, without the stream-wait wake-up (a few us of a ~58 us
     // closed-loop window); anything unexpected falls back to the stream wait.
@@ -1898,6 +2052,30 @@ int dpe_bcm_results_joint(dpe_bcm *h, dpe_bcm_joint_result *joint, dpe_bcm_joint
     return 0;
 }
 
+int dpe_bcm_results_epochs(dpe_bcm *h, dpe_bcm_epochs_result *results, dpe_stream_t stream)
+{
+    DPE_REQUIRE(h && results, "[BatchCorrManifold] results_epochs: null argument");
+    DPE_REQUIRE(h->epochs, "[BatchCorrManifold] results_epochs: the handle was not made by dpe_bcm_create_epochs");
+    DPE_REQUIRE(h->lastW > 0 && h->lastEpochs > 0, "[BatchCorrManifold] results_epochs: no epochs update yet");
+    DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    const unsigned long long *keys = h->keys_h, *oob = h->oob_h;
+    for (int g = 0; g < h->lastW; ++g) {
+        dpe_bcm_epochs_result &r = results[g];
+        decode_key(keys[2 * g], &r.posScore, &r.posIndex);
+        decode_key(keys[2 * g + 1], &r.velScore, &r.velIndex);
+        r.posOutOfWindow = (int64_t)oob[2 * g];
+        r.velOutOfWindow = (int64_t)oob[2 * g + 1];
+        r.nPasses = h->lastPasses;
+        r.reserved = 0;
+        DPE_REQUIRE(r.posIndex >= 0 && r.posIndex < h->cfg.posGridSize && r.velIndex >= 0 && r.velIndex < h->cfg.velGridSize,
+                    "[BatchCorrManifold] results_epochs: arg-max index outside the grids");
+        const double *pp = h->posGrid_h.data() + 4 * r.posIndex, *vp = h->velGrid_h.data() + 4 * r.velIndex;
+        for (int c = 0; c < 4; ++c) { r.offset[c] = pp[c]; r.offset[4 + c] = vp[c]; }
+        make_meas(h->win_h[(size_t)g * h->lastEpochs + h->lastEpochs - 1], pp, vp, r.zVal);   // the LAST window's centre moved by the ML offset
+    }
+    return 0;
+}
+
 int dpe_bcm_profile(dpe_bcm *h, int32_t enable, float *ms, int32_t *count)
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] profile: null handle");
@@ -1955,6 +2133,7 @@ int dpe_bcm_exchange_keys(dpe_bcm *h, dpe_comm *c, uint64_t *keys_host, dpe_stre
 {
     DPE_REQUIRE(h && c && h->lastW > 0, "[BatchCorrManifold] exchange_keys: no update yet / null communicator");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] exchange_keys: a joint handle (dpe_bcm_create_joint) scans whole grids: sharding is not supported");
+    DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] exchange_keys: an epochs handle (dpe_bcm_create_epochs) scans whole grids: sharding is not supported");
     unsigned long long *keys = h->keys_d + (size_t)h->cur * 4 * h->cfg.maxWindows;
     if (dpe_comm_allreduce_max_u64(c, reinterpret_cast<uint64_t *>(keys), 2 * (int64_t)h->lastW, stream)) return -1;
     if (keys_host) {
@@ -1972,6 +2151,7 @@ int dpe_bcm_results_from_keys(dpe_bcm *h, const uint64_t *keys_host, int32_t nWi
     DPE_REQUIRE(h && keys_host && results && (posGridGlobal != nullptr) == (velGridGlobal != nullptr) && (posGridGlobal || h->axes),
                 "[BatchCorrManifold] results_from_keys: null argument (both global grids, or neither for a handle with grid axes)");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] results_from_keys: a joint handle (dpe_bcm_create_joint) scans whole grids: use dpe_bcm_results_joint");
+    DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] results_from_keys: an epochs handle (dpe_bcm_create_epochs) scans whole grids: use dpe_bcm_results_epochs");
     if (!posGridGlobal) {   // an axes handle decodes from its axes, which are the global ones
         posGridGlobalSize = axes_size(h->posAx);
         velGridGlobalSize = axes_size(h->velAx);

@@ -38,6 +38,7 @@ EXPORTS = [
     "dpe_trk_create", "dpe_trk_destroy", "dpe_trk_set_params", "dpe_trk_track", "dpe_trk_correlate", "dpe_trk_read_log",
     "dpe_trk_read_cp_signs", "dpe_trk_state", "dpe_trk_dev_status",
     "dpe_bcm_create_joint", "dpe_bcm_update_joint", "dpe_bcm_results_joint", "dpe_bcm_joint_set_own_keys",
+    "dpe_bcm_create_epochs", "dpe_bcm_update_epochs", "dpe_bcm_results_epochs",
     "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
 ]
 
@@ -109,6 +110,12 @@ class BcmJointResult(C.Structure):  # dpe_bcm_joint_result
 class BcmJointRxResult(C.Structure):  # dpe_bcm_joint_rx_result
     _fields_ = [("zVal", C.c_double * 8), ("posIndex", C.c_int64), ("velIndex", C.c_int64), ("posScore", C.c_float),
                 ("velScore", C.c_float), ("posOutOfWindow", C.c_int64), ("velOutOfWindow", C.c_int64)]
+
+
+class BcmEpochsResult(C.Structure):  # dpe_bcm_epochs_result
+    _fields_ = [("zVal", C.c_double * 8), ("offset", C.c_double * 8), ("posIndex", C.c_int64), ("velIndex", C.c_int64),
+                ("posScore", C.c_float), ("velScore", C.c_float), ("posOutOfWindow", C.c_int64), ("velOutOfWindow", C.c_int64),
+                ("nPasses", C.c_int32), ("reserved", C.c_int32)]
 
 
 CHAN_START_DTYPE = np.dtype([("codePhaseStart", "<f8"), ("carrierPhaseStart", "<f8"), ("codeFrequency", "<f8"),
@@ -694,6 +701,72 @@ class JointManifold(BatchCorrManifold):
 
     def UpdateDev(self, *a, **k):
         raise DpeError("[BatchCorrManifold] a joint handle takes its inputs through Update(rx) only")
+
+    UpdatePrepared = exchange_keys = results_from_keys = UpdateDev
+
+
+class EpochManifold(BatchCorrManifold):
+    """N consecutive windows summed into one score row and one arg-max (dpe_bcm_create_epochs): non-coherent accumulation
+    over epochs along the predicted trajectory.  max_windows bounds the windows of a launch (groups x epochs), max_epochs the
+    windows of a group; pairs_per_pass = 0 lets a pass hold as many whole windows as the LDS budget allows, a positive value caps
+    the (window, SV) pairs of a pass.  PosScores / VelScores / Keys are the GROUP rows and keys."""
+
+    def __init__(self, SamplingFrequency, samples_per_window, NumFFTPoints, pos_grid, vel_grid, max_epochs, pairs_per_pass=0, LPower=1,
+                 lag_half_width=8, bin_half_width=48, max_windows=None, max_channels=8):
+        super().__init__(SamplingFrequency, samples_per_window, NumFFTPoints, pos_grid, vel_grid, LPower=LPower,
+                         lag_half_width=lag_half_width, bin_half_width=bin_half_width,
+                         max_windows=max_epochs if max_windows is None else max_windows, max_channels=max_channels, write_scores=True)
+        if self.axes:
+            raise DpeError("[BatchCorrManifold] create_epochs: point-list grids only (GridAxes are not supported)")
+        self.max_epochs, self.pairs_per_pass = int(max_epochs), int(pairs_per_pass)
+        self.n_epochs = 0
+
+    def Start(self):
+        if self.Started:
+            return 0
+        cfg = _bcm_config(self.S, self.L, self.B, self.LPower, self.max_windows, self.max_channels, self.C, self.fs, self.pos_grid,
+                          self.vel_grid, 0, 0, False, True, False, False)
+        _check(lib().dpe_bcm_create_epochs(C.byref(cfg), C.c_int32(self.max_epochs), C.c_int32(self.pairs_per_pass), C.byref(self._h)))
+        self._bind_outputs()
+        return 0
+
+    def Update(self, CodeScores, CarrScores, win, chan, n_epochs, stream=None):
+        """win: BCM_WINDOW_DTYPE [G * n_epochs]; chan: CHAN_END_DTYPE [G * n_epochs, K], group-major; banks: the device pointers
+        of a BatchCorrScores updated with the same windows."""
+        if not self.Started:
+            raise DpeError("[BatchCorrManifold] Error: Update() Failed due to module not initialized")
+        win = np.ascontiguousarray(np.atleast_1d(win))
+        chan = np.ascontiguousarray(chan)
+        if chan.ndim == 1:
+            chan = chan[None, :]
+        W, K = chan.shape
+        n_epochs = int(n_epochs)
+        if win.shape[0] != W or n_epochs < 1 or W % n_epochs:
+            raise DpeError("[BatchCorrManifold] update_epochs: %d windows are not whole groups of %d" % (W, n_epochs))
+        _check(lib().dpe_bcm_update_epochs(self._h, _ptr(CodeScores), _ptr(CarrScores), C.c_int32(W // n_epochs), C.c_int32(n_epochs),
+                                           C.c_int32(K), win.ctypes.data_as(C.POINTER(BcmWindow)),
+                                           chan.ctypes.data_as(C.POINTER(ChanEnd)), _stream(stream)))
+        self._W, self.n_epochs = W // n_epochs, n_epochs          # rows, keys and results are per GROUP
+        keys = C.c_void_p()
+        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
+        self.Keys = keys.value
+        return 0
+
+    def results(self, stream=None):
+        """-> per group a dict: zVal (the last window's centre moved by the ML offset), the arg-max of the summed rows, offset[8],
+        the summed out-of-window counts and nPasses."""
+        res = (BcmEpochsResult * self._W)()
+        _check(lib().dpe_bcm_results_epochs(self._h, res, _stream(stream)))
+        return [dict(zVal=np.array(r.zVal), RVal=np.eye(8), offset=np.array(r.offset), posIndex=r.posIndex, velIndex=r.velIndex,
+                     posScore=r.posScore, velScore=r.velScore, posOutOfWindow=r.posOutOfWindow, velOutOfWindow=r.velOutOfWindow,
+                     nPasses=r.nPasses) for r in res]
+
+    def read_keys(self, stream=None):
+        """The groups' packed keys of the last Update, uint64 [G, 2] (dpe_bcm_keys)."""
+        return d2h(self.Keys, self._W * 2 * 8, np.uint64, stream).reshape(self._W, 2)
+
+    def UpdateDev(self, *a, **k):
+        raise DpeError("[BatchCorrManifold] an epochs handle takes its inputs through Update(..., n_epochs) only")
 
     UpdatePrepared = exchange_keys = results_from_keys = UpdateDev
 

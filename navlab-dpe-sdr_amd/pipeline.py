@@ -182,3 +182,69 @@ def run_joint_closed_loop(iq_windows_per_rx, handoffs, fs, pos_grid, vel_grid, t
         for b in bcss:
             b.Stop()
     return fixes, results
+
+
+def predict_state(x, T, couple_velocity=True):
+    """The time update x_k+1|k = F x_k|k of the DPE random-walk model (EKF_MakeDPERandomWalkFMatrix, cuekf.cu:133-139), by the
+    library's own cuEKF StepPredict."""
+    ekf = engine.cuEKF(x, SampleLength=T, EnableEKF=True, couple_velocity=couple_velocity)
+    try:
+        ekf.step_predict()
+        return ekf.state()["xkk1"].copy()
+    finally:
+        ekf.Stop()
+
+
+def run_epoch_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, n_epochs, time_grid=(0.0,), init_delta=(0, 0, 0, 0), K=None, lpower=1,
+                          lag_half_width=None, bin_half_width=None, pairs_per_pass=0, keep_scores=False):
+    """The closed loop with ONE fix per group of n_epochs consecutive windows (engine.EpochManifold): inside a group the channel
+    manager is stepped window by window with the PREDICTED state (predict_state: the filter's time update, no measurement),
+    one BatchCorrScores call covers the group's windows, one EpochManifold.Update sums their manifold scores and takes one
+    arg-max.  The group's zVal -- its last window's centre moved by the ML offset -- is the state the next group starts from
+    (pass-through filter).  A trailing group may be shorter.  n_epochs = 1 is run_closed_loop, bit for bit.
+    Returns fixes [ceil(W / n_epochs), 8] and the per-group result dicts."""
+    import torch
+    iq_windows = np.ascontiguousarray(iq_windows)
+    W, S2 = iq_windows.shape
+    S, n = S2 // 2, int(n_epochs)
+    K = len(ho["prn_list"]) if K is None else K
+    nfft = engine.carr_fft_len(S)
+    L, B = bank_half_widths(pos_grid, vel_grid, fs, nfft)
+    L = L if lag_half_width is None else int(lag_half_width)
+    B = B if bin_half_width is None else int(bin_half_width)
+    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_windows=n, max_channels=K)
+    bcm = engine.EpochManifold(fs, S, nfft, pos_grid, vel_grid, n, pairs_per_pass, LPower=lpower, lag_half_width=L, bin_half_width=B,
+                               max_channels=K)
+    cm = None
+    try:
+        bcs.Start()
+        bcm.Start()
+        cm = engine.ChanMgr.from_handoff(ho, S / fs, K)
+        x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
+        x[:4] += np.asarray(init_delta, dtype=np.float64)
+        iq_d = torch.from_numpy(iq_windows).to("cuda:0")
+        fixes, results = [], []
+        for g0 in range(0, W, n):
+            m = min(n, W - g0)
+            cs, ce, bw = [], [], []
+            for e in range(m):
+                if e:
+                    x = predict_state(x, S / fs)
+                (cm.Start if g0 + e == 0 else cm.Update)(x, x, time_grid)
+                s_, e_, w_ = cm.outputs()
+                cs.append(s_); ce.append(e_); bw.append(w_)
+            bcs.Update(iq_d[g0:g0 + m], np.stack(cs))
+            bcm.Update(bcs.CodeScores, bcs.CarrScores, np.concatenate(bw), np.stack(ce), m)
+            r = bcm.results()[0]
+            if keep_scores:
+                ps, vs = bcm.read_scores()
+                r["posScores"], r["velScores"] = ps[0].copy(), vs[0].copy()
+            x = r["zVal"].copy()
+            fixes.append(x)
+            results.append(r)
+    finally:
+        if cm is not None:
+            cm.Stop()
+        bcm.Stop()
+        bcs.Stop()
+    return np.stack(fixes), results
