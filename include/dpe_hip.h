@@ -300,6 +300,10 @@ int dpe_bcm_export_scores_f64(dpe_bcm *h, int32_t window, double *posScores_dev,
  * (score bits << 32) | (0xFFFFFFFF - globalIndex): an integer max over shards reproduces
  * the "first maximum" tie-break of thrust::max_element (:2589-2590).  For RCCL all-reduce. */
 int dpe_bcm_keys(dpe_bcm *h, const uint64_t **keys_dev);
+/* Blocks along x per window (or group) that the LAST Update of any kind gave the position (split[0]) and the velocity
+ * (split[1]) manifold; a block walks ceil(tiles / split) or one fewer 1024-point tiles.  Read-only, host state; refused before
+ * the first Update.  (For tests and measurements that depend on a block walking several tiles.) */
+int dpe_bcm_last_split(dpe_bcm *h, int32_t split[2]);
 /* Measurement from externally reduced keys (multi-GPU): host keys [nWindows][2]; the GLOBAL grids with their sizes (a
  * decoded index outside them, or a key of 0 = "no valid score" -- every score NaN, or a key set that was never reduced --
  * is an error, not a wild read). */

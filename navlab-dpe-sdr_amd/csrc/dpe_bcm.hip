@@ -2129,6 +2129,15 @@ int dpe_bcm_keys(dpe_bcm *h, const uint64_t **keys_dev)
     return 0;
 }
 
+int dpe_bcm_last_split(dpe_bcm *h, int32_t split[2])
+{
+    DPE_REQUIRE(h && split, "[BatchCorrManifold] last_split: null argument");
+    DPE_REQUIRE(h->lastSplit[0] > 0 && h->lastSplit[1] > 0, "[BatchCorrManifold] last_split: no Update yet");
+    split[0] = (int32_t)h->lastSplit[0];
+    split[1] = (int32_t)h->lastSplit[1];
+    return 0;
+}
+
 int dpe_bcm_exchange_keys(dpe_bcm *h, dpe_comm *c, uint64_t *keys_host, dpe_stream_t stream)
 {
     DPE_REQUIRE(h && c && h->lastW > 0, "[BatchCorrManifold] exchange_keys: no update yet / null communicator");

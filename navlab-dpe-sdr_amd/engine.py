@@ -38,7 +38,7 @@ EXPORTS = [
     "dpe_trk_create", "dpe_trk_destroy", "dpe_trk_set_params", "dpe_trk_track", "dpe_trk_correlate", "dpe_trk_read_log",
     "dpe_trk_read_cp_signs", "dpe_trk_state", "dpe_trk_dev_status",
     "dpe_bcm_create_joint", "dpe_bcm_update_joint", "dpe_bcm_results_joint", "dpe_bcm_joint_set_own_keys",
-    "dpe_bcm_create_epochs", "dpe_bcm_update_epochs", "dpe_bcm_results_epochs",
+    "dpe_bcm_create_epochs", "dpe_bcm_update_epochs", "dpe_bcm_results_epochs", "dpe_bcm_last_split",
     "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
 ]
 
@@ -555,6 +555,13 @@ class BatchCorrManifold:
         _check(lib().dpe_bcm_results_from_keys(self._h, keys_host.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_int32(W), *args, res))
         return [dict(zVal=np.array(r.zVal), posIndex=r.posIndex, velIndex=r.velIndex, posScore=r.posScore,
                      velScore=r.velScore) for r in res]
+
+    def last_split(self):
+        """(position, velocity) blocks per window or group of the last Update (dpe_bcm_last_split): with fewer blocks than
+        1024-point tiles a block walks several tiles."""
+        split = (C.c_int32 * 2)()
+        _check(lib().dpe_bcm_last_split(self._h, split))
+        return (int(split[0]), int(split[1]))
 
     def read_scores(self, stream=None):
         Gp, Gv = self.pos_grid.shape[0], self.vel_grid.shape[0]

@@ -1,5 +1,6 @@
 """A synthetic world for the multi-epoch manifold scan (dpe_bcm_create_epochs): ONE receiver on the handoff geometry at
-2.5 Msps, N consecutive short windows (S = 5000, 2 ms), 7^4-point grids with the joint world's 40 m and 12 m/s steps.
+2.5 Msps, N consecutive short windows (S = 5000, 2 ms), 7^4-point grids with the joint world's 40 m and 12 m/s steps (or
+larger grids of the same extent, pos_dim / vel_dim: the worlds of tests/test_gpu_epochs_walk.py).
 
 The truth moves with constant velocity (and constant clock drift).  Every window's centre is the truth AT THAT EPOCH moved
 back by ONE common grid offset that is not the grids' centre point, so each window alone, and the sum over windows, peak on
@@ -28,20 +29,32 @@ def _o():
     return o
 
 
+def build(N=5, K=8, seed=0, amp=AMP, widen=True, bin_half_width=None, shift=0.0, pos_dim=7, vel_dim=7, pos_step=None,
+          vel_step=None):
+    """One world per set of arguments, however they are passed (see _build)."""
+    return _build(N, K, seed, amp, widen, bin_half_width, shift, pos_dim, vel_dim, pos_step, vel_step)
+
+
 @functools.lru_cache(maxsize=None)
-def build(N=5, K=8, seed=0, amp=AMP, widen=True, bin_half_width=None, shift=0.0):
+def _build(N, K, seed, amp, widen, bin_half_width, shift, pos_dim, vel_dim, pos_step, vel_step):
     """-> world dict: fs, S, C, N, K, pos, vel, L, B, pos_at / vel_at (the expected arg-max indices), offset[8] (ENU-dt),
     truth[N, 8], wins[N] (the window records of joint_world.build, each with its own centre).
     widen: bank half-widths from pipeline.bank_half_widths, enlarged until the oracle reports no pair outside the banks;
     False: deliberately narrow banks (the clamp path).  bin_half_width: B forced (with L as widened).
-    shift: windows 1 and 3 have their centres moved by `shift` metres in the clock term (pairs leave the banks there)."""
+    shift: windows 1 and 3 have their centres moved by `shift` metres in the clock term (pairs leave the banks there).
+    widen "L" / "B": only the lag (bin) banks narrow, the other side as widened -- one manifold clamps, the other is clean.
+    pos_dim / vel_dim, pos_step / vel_step: as joint_world.build (the walk worlds of tests/test_gpu_epochs_walk.py)."""
+    if widen in ("L", "B"):
+        world = dict(build(N, K, seed, amp, True, bin_half_width, shift, pos_dim, vel_dim, pos_step, vel_step))
+        world["L" if widen == "L" else "B"] = 1 if widen == "L" else 2
+        return world
     o = _o()
     ho = jw._extended()
     X = np.array(ho["X_ECEF"], dtype=np.float64)
     R = o.enu2ecef(o.ecef2ll(X))
     R3 = R.reshape(3, 3)
-    pos, vel = jw.grids(POS_STEP)
-    ip, iv = jw.grid_index(POS_AT), jw.grid_index(VEL_AT)
+    pos, vel = jw.grids(pos_step, pos_dim, vel_dim, vel_step)
+    ip, iv = jw.grid_index(jw.scaled_at(POS_AT, pos_dim), pos_dim), jw.grid_index(jw.scaled_at(VEL_AT, vel_dim), vel_dim)
     dp, dv = pos[ip], vel[iv]
     C = dpe.engine.carr_fft_len(S)
     T = S / FS
@@ -75,7 +88,7 @@ def build(N=5, K=8, seed=0, amp=AMP, widen=True, bin_half_width=None, shift=0.0)
         truths.append(truth)
     L, B = dpe.pipeline.bank_half_widths(pos, vel, FS, C)
     world = dict(fs=FS, S=S, C=C, N=N, K=K, pos=pos, vel=vel, R=R, wins=wins, truth=np.stack(truths), ho=hr, pos_at=ip, vel_at=iv,
-                 offset=np.concatenate([dp, dv]), prn=np.asarray(cm.prns))
+                 offset=np.concatenate([dp, dv]), prn=np.asarray(cm.prns), dims=(pos_dim, vel_dim))
     if widen:
         while True:
             world["L"], world["B"] = L, B

@@ -9,7 +9,9 @@ offset is one ECEF displacement for all of them.
 
 Spacings: at 2.5 Msps a sample is 120 m and a 2 ms window resolves Doppler to ~95 m/s per main lobe; with amp 200 against
 sigma 300 over 5000 samples a single SV's peak is known to ~1/33 of that.  The grids step by 40 m / 12 m/s so that the
-expected point wins for every receiver alone (tests/test_joint_world_cpu.py proves it with the oracle)."""
+expected point wins for every receiver alone (tests/test_joint_world_cpu.py proves it with the oracle).  Larger grids
+(pos_dim / vel_dim of build) keep that extent with finer steps (17.1 m and 5.1 m/s at 15^4), on which the point still wins for
+every receiver alone, by the same proof."""
 import functools
 
 import numpy as np
@@ -25,6 +27,20 @@ BASELINES = np.array([[0.0, 0.0, 0.0], [1.2, -0.5, 0.0], [-0.4, 2.9, 0.3], [2.1,
                       [0.3, -2.2, 1.0], [1.0, 1.0, 1.0]])
 CLOCKS = np.array([0.0, 7.5, -3.25, 12.0, 1.0, -8.0, 4.0, 2.0])     # calibrated clock offsets (m)
 POS_AT, VEL_AT = (4, 2, 5, 1), (2, 4, 1, 5)                         # the common offset as grid coordinates (centre: 3, 3, 3, 3)
+
+
+def scaled_at(at, dim):
+    """POS_AT / VEL_AT of the 7^4 grid as coordinates of a dim^4 grid: the same direction from the centre point, scaled with
+    the grid's half width ((dim - 1) // 2 entries, synth.uniform_grid's centre).  dim = 7 gives `at` itself.  For the walk
+    worlds (dim 13, 14, 15, 20) the point lies far beyond the first 1024-point tile: its x coordinate alone puts it past
+    4 * 13^3 points."""
+    half = (dim - 1) // 2
+    return tuple(half + int(np.rint((a - 3) * half / 3.0)) for a in at)
+
+
+def scaled_step(step, dim):
+    """The spacing that keeps a dim^4 grid at the 7^4 grid's extent (3 steps to its far edge): step for dim = 7."""
+    return step * 3 / (dim // 2)
 
 
 def _o():
@@ -76,24 +92,40 @@ def handoff_at(sel, Xr):
 SAMPLE = _C / FS     # one sample of code delay, in metres
 
 
-def grids(pos_step=POS_STEP):
-    return dpe.synth.uniform_grid(7, pos_step), dpe.synth.uniform_grid(7, VEL_STEP)
+def grids(pos_step=None, pos_dim=7, vel_dim=7, vel_step=None):
+    """Position and velocity grids of pos_dim^4 / vel_dim^4 points; a step left out keeps the 7^4 grid's extent."""
+    pos_step = scaled_step(POS_STEP, pos_dim) if pos_step is None else pos_step
+    vel_step = scaled_step(VEL_STEP, vel_dim) if vel_step is None else vel_step
+    return dpe.synth.uniform_grid(pos_dim, pos_step), dpe.synth.uniform_grid(vel_dim, vel_step)
+
+
+def build(n_sv=(5, 8, 4), seed=0, W=1, widen=True, pos_step=None, pos_dim=7, vel_dim=7, vel_step=None):
+    """One world per set of arguments, however they are passed (see _build)."""
+    return _build(tuple(n_sv), seed, W, widen, pos_step, pos_dim, vel_dim, vel_step)
 
 
 @functools.lru_cache(maxsize=None)
-def build(n_sv=(5, 8, 4), seed=0, W=1, widen=True, pos_step=POS_STEP):
+def _build(n_sv, seed, W, widen, pos_step, pos_dim, vel_dim, vel_step):
     """-> world dict: fs, S, C, pos, vel, R, L, B, pos_at / vel_at (expected arg-max indices), offset[8] (ENU-dt), and per
     receiver rx[r] = dict(K, ho, truth, centre, wins[W]) with the window records of helpers.make_case.
     widen: bank half-widths from pipeline.bank_half_widths, enlarged until the oracle reports no pair outside the banks;
-    False: deliberately narrow banks (the clamp path).  pos_step: spacing of the position grid (the closed-loop world uses
-    SAMPLE, see oracle_loop)."""
+    False: deliberately narrow banks (the clamp path); "L": only the lag banks narrow, B as widened (the position manifold
+    clamps, the velocity manifold is clean); "B": its mirror.  pos_step: spacing of the position grid (the closed-loop world
+    uses SAMPLE, see oracle_loop).  pos_dim / vel_dim: points per axis of each grid (7: three tiles; 15, 14, 20, 13: the
+    walk worlds of tests/test_gpu_joint_walk.py), with POS_AT / VEL_AT and, unless given, the steps scaled to the 7^4 grid's
+    extent (scaled_at, scaled_step)."""
+    if widen in ("L", "B"):
+        base = build(n_sv, seed, W, True, pos_step, pos_dim, vel_dim, vel_step)
+        world = dict(base)
+        world["L" if widen == "L" else "B"] = 1 if widen == "L" else 2
+        return world
     o = _o()
     ho = _extended()
     X = np.array(ho["X_ECEF"], dtype=np.float64)
     R = o.enu2ecef(o.ecef2ll(X))
     R3 = R.reshape(3, 3)
-    pos, vel = grids(pos_step)
-    ip, iv = grid_index(POS_AT), grid_index(VEL_AT)
+    pos, vel = grids(pos_step, pos_dim, vel_dim, vel_step)
+    ip, iv = grid_index(scaled_at(POS_AT, pos_dim), pos_dim), grid_index(scaled_at(VEL_AT, vel_dim), vel_dim)
     dp, dv = pos[ip], vel[iv]
     C = dpe.engine.carr_fft_len(S)
     T = S / FS
@@ -123,7 +155,8 @@ def build(n_sv=(5, 8, 4), seed=0, W=1, widen=True, pos_step=POS_STEP):
                              fi=cm.fi.copy(), centre=centre.copy()))
         rxs.append(dict(K=K, ho=hr, truth=truth, centre=centre, wins=wins, prn=np.asarray(cm.prns)))
     L, B = dpe.pipeline.bank_half_widths(pos, vel, FS, C)
-    world = dict(fs=FS, S=S, C=C, W=W, pos=pos, vel=vel, R=R, rx=rxs, pos_at=ip, vel_at=iv, offset=np.concatenate([dp, dv]))
+    world = dict(fs=FS, S=S, C=C, W=W, pos=pos, vel=vel, R=R, rx=rxs, pos_at=ip, vel_at=iv, offset=np.concatenate([dp, dv]),
+                 dims=(pos_dim, vel_dim))
     if widen:
         while True:
             world["L"], world["B"] = L, B

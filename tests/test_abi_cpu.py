@@ -28,6 +28,20 @@ def test_header_symbols_exported(built):
     assert built.dpe_abi_version() == 4
 
 
+def test_last_split_accessor(built):
+    """dpe_bcm_last_split (additive, the ABI version stays): declared, exported, wrapped, and refused with a message where
+    there is nothing to report."""
+    import ctypes as C
+    hdr = open(os.path.join(ROOT, "include", "dpe_hip.h")).read()
+    assert re.search(r"\bint dpe_bcm_last_split\(dpe_bcm \*h, int32_t split\[2\]\);", hdr)
+    assert "dpe_bcm_last_split" in dpe.engine.EXPORTS and callable(dpe.BatchCorrManifold.last_split)
+    assert dpe.JointManifold.last_split is dpe.BatchCorrManifold.last_split is dpe.EpochManifold.last_split
+    split = (C.c_int32 * 2)(-1, -1)
+    with pytest.raises(dpe.DpeError, match="last_split: null argument"):
+        dpe.engine._check(built.dpe_bcm_last_split(None, split))
+    assert list(split) == [-1, -1] and built.dpe_abi_version() == 4
+
+
 def test_integration_md_has_a_row_for_every_exported_symbol():
     """INTEGRATION.md section 1b names, for every function include/dpe_hip.h declares, the reference interface it replaces (file:line)
     or says why there is none -- one row per symbol, none missing, none stale."""

@@ -83,3 +83,88 @@ def test_oracle_closed_loop_returns_to_the_truth(built, oracle, start):
     for r, rx in enumerate(world["rx"]):
         assert np.abs(ref["fixes"][0, r] - rx["truth"]).max() > 100.0
         assert np.abs(ref["fixes"][3, r] - rx["truth"]).max() < bound
+
+
+# the worlds of tests/test_gpu_joint_walk.py: (arguments of joint_world.build, tiles of the position and velocity grids)
+WALK_WORLDS = {
+    "J1": (dict(n_sv=(5, 8, 4), seed=3, W=2, pos_dim=15, vel_dim=14), (50, 38)),
+    "J1-swapped": (dict(n_sv=(5, 8, 4), seed=3, W=2, pos_dim=14, vel_dim=15), (38, 50)),
+    "J2": (dict(n_sv=(5, 8, 4), seed=7, W=4), (3, 3)),
+    "J3": (dict(n_sv=(8,) * 8, seed=6, W=1, pos_dim=15, vel_dim=14), (50, 38)),
+    "J6": (dict(n_sv=(5, 8, 4), seed=5, W=1, pos_dim=13, vel_dim=13), (28, 28)),
+    "J7": (dict(n_sv=(5, 8, 4), seed=4, W=2, pos_dim=20, vel_dim=7), (157, 3)),
+}
+
+
+def test_defaults_keep_their_bits():
+    """The grid dimension arguments leave the 7^4 worlds what they were."""
+    import navlab_dpe_sdr_amd as dpe
+    pos, vel = jw.grids()
+    assert np.array_equal(pos, dpe.synth.uniform_grid(7, 40.0)) and np.array_equal(vel, dpe.synth.uniform_grid(7, 12.0))
+    assert jw.scaled_at(jw.POS_AT, 7) == jw.POS_AT and jw.scaled_at(jw.VEL_AT, 7) == jw.VEL_AT
+    assert jw.scaled_step(jw.POS_STEP, 7) == 40.0 and jw.scaled_step(jw.VEL_STEP, 7) == 12.0
+    assert np.array_equal(jw.grids(jw.SAMPLE)[0], dpe.synth.uniform_grid(7, jw.SAMPLE))
+    for dim in (13, 14, 15, 20):      # the larger grids keep the 7^4 grid's extent and the point leaves the first tile
+        p, v = jw.grids(pos_dim=dim, vel_dim=dim)
+        assert p.shape == (dim ** 4, 4) and np.abs(p).max() == pytest.approx(120.0) and np.abs(v).max() == pytest.approx(36.0)
+        for at in (jw.POS_AT, jw.VEL_AT):
+            s = jw.scaled_at(at, dim)
+            assert all(0 <= c < dim for c in s) and jw.grid_index(s, dim) >= 1024 and s != ((dim - 1) // 2,) * 4
+
+
+@pytest.mark.parametrize("name", sorted(WALK_WORLDS))
+def test_walk_worlds_peak_on_the_scaled_offset_in_every_window(built, oracle, name):
+    """Every receiver alone in every distinct window, and the sum, peak on the expected point of the larger grids, which is
+    neither the centre nor in the first tile; no pair leaves the widened banks; the grids have the tile counts the GPU tests
+    reason with."""
+    kw, want_tiles = WALK_WORLDS[name]
+    world = jw.build(**kw)
+    ref = jw.oracle_rows(world)
+    pd, vd = world["dims"]
+    assert (-(-world["pos"].shape[0] // 1024), -(-world["vel"].shape[0] // 1024)) == want_tiles
+    assert world["pos_at"] == jw.grid_index(jw.scaled_at(jw.POS_AT, pd), pd) and world["vel_at"] == jw.grid_index(jw.scaled_at(jw.VEL_AT, vd), vd)
+    assert world["pos_at"] != jw.grid_index(((pd - 1) // 2,) * 4, pd) and world["vel_at"] != jw.grid_index(((vd - 1) // 2,) * 4, vd)
+    if pd != 7:
+        assert world["pos_at"] >= 1024
+    if vd != 7:
+        assert world["vel_at"] >= 1024
+    assert len(ref["rx"]) == world["W"]
+    for w in range(world["W"]):
+        for r, x in enumerate(ref["rx"][w]):
+            assert x["oob_pos"] == 0 and x["oob_pos_x"] == 0 and x["oob_vel"] == 0, (w, r)
+            assert oracle.argmax_first(x["pos"]) == world["pos_at"], (w, r)
+            assert oracle.argmax_first(x["pos_x"]) == world["pos_at"], (w, r)
+            assert oracle.argmax_first(x["vel"]) == world["vel_at"], (w, r)
+        for rname, at in (("pos", world["pos_at"]), ("pos_x", world["pos_at"]), ("vel", world["vel_at"])):
+            assert oracle.argmax_first(ref[rname][w]) == at, (w, rname)
+    if world["W"] > 1:
+        assert not np.array_equal(world["rx"][0]["wins"][0]["iq"], world["rx"][0]["wins"][1]["iq"])
+    if name == "J6":      # the tie test's point list: the first 24 tiles of the grids hold both expected points
+        assert 1024 <= world["pos_at"] < 24 * 1024 and 1024 <= world["vel_at"] < 24 * 1024
+
+
+@pytest.mark.parametrize("name,side", [("J1", "L"), ("J1", "B"), ("J1-swapped", "L"), ("J1-swapped", "B"), ("J2", False), ("J6", False)])
+def test_walk_worlds_with_narrow_banks(built, oracle, name, side):
+    """The clamp-path variants: with only the lag (bin) banks narrow, pairs of every receiver leave the position (velocity)
+    banks in every window and none the other side's, which keeps the widened world's rows; the faithful position row stays
+    inside helpers.assert_parity's cap on edge flips per receiver."""
+    world = jw.build(**dict(WALK_WORLDS[name][0], widen=side))
+    ref = jw.oracle_rows(world)
+    if side:
+        base = jw.build(**WALK_WORLDS[name][0])
+        assert (world["L"], world["B"]) == ((1, base["B"]) if side == "L" else (base["L"], 2))
+        clean = jw.oracle_rows(base)
+    for w in range(world["W"]):
+        for r, x in enumerate(ref["rx"][w]):
+            assert (x["oob_pos_x"] > 0) == (side != "B") and (x["oob_vel"] > 0) == (side != "L"), (w, r)
+            assert x["pos_x"].max() > 0 and x["vel"].max() > 0
+            flips = np.abs(x["pos"] - x["pos_x"]) > 10 * helpers.POS_REF_NOISE * x["pos"].max()
+            flips[x["quirks"]] = False
+            allowed = 16 + x["pos"].size * world["rx"][r]["K"] // 2000
+            print("%s narrow %s, window %d receiver %d: %d edge flips (cap %d), oob pos %d / %d, vel %d"
+                  % (name, side, w, r, flips.sum(), allowed, x["oob_pos"], x["oob_pos_x"], x["oob_vel"]))
+            assert flips.sum() <= allowed
+        if side:
+            same = "vel" if side == "L" else "pos_x"
+            assert np.array_equal(ref[same][w], clean[same][w])
+            assert oracle.argmax_first(ref[same][w]) == (world["vel_at"] if side == "L" else world["pos_at"])
