@@ -800,6 +800,80 @@ int dpe_nav_solve_log(dpe_nav *h, dpe_trk *trk, int64_t firstWindow, int32_t nEp
 int dpe_nav_load_log(dpe_trk *trk, int32_t nWindows, const double *rows, dpe_stream_t stream);
 int dpe_nav_status(dpe_nav *h, int32_t *status);   /* OR of the solve status bits since create */
 
+/* ---- Vector tracking: every channel steered by one 8-state navigation filter (the twin's vt_init / vt_track / vt_measurement_update /
+ * vt_time_update, receiver.py:545-720, which names the structure but does not run; the algorithm is stated in DESIGN.md 7e).  One
+ * epoch = N consecutive windows of T seconds during which the NCOs run open loop: window j of channel k is correlated with
+ * rc_j = mod(rc + j fc T, 1023), ri_j = mod(ri + j fi T, 1) and the epoch's fc, fi (vt_correlate_kernel, one block per window and
+ * channel); vt_filter_kernel (one wave) turns the N x K early / prompt / late sums into a code and a frequency residual per channel,
+ * gates each channel on a lock metric, updates X and Sigma through the Cholesky factor of S = H Sigma H^T + W, predicts over N T and
+ * back-computes every channel's fi and fc from the predicted state (csrc/dpe_vt.hip, csrc/dpe_vt_dev.h). */
+typedef struct dpe_vt dpe_vt;
+#define DPE_VT_MAX_CHAN 16
+#define DPE_VT_MAX_WINDOWS 20
+#define DPE_VT_MAX_PREV 32
+typedef struct dpe_vt_config {
+    double samplingFrequency;
+    double T;                     /* window length in s, at most 1.5 ms; round(T fs) must be even */
+    int32_t N;                    /* windows per epoch: even, 2 .. 20 (0 -> 20) */
+    int32_t nChan;                /* 1 .. 16 (an update needs four included channels) */
+    int32_t prn[DPE_VT_MAX_CHAN];
+    double dopplerSign;           /* rawfile.ds, 0 -> +1 */
+    int32_t numPrev;              /* residuals the measurement variance is taken over, 2 .. 32 (0 -> 20) */
+    int32_t reserved;
+    double initVarRange, initVarRate;   /* variances used until numPrev residuals exist: m^2, (m/s)^2 (0 -> 225, 1) */
+    double minVarRange, minVarRate;     /* floors of the measured variances (0 -> 1, 0.01; negative: no floor) */
+    double qDiag[8];              /* process noise added per epoch, diagonal (all 0 -> ekf.py:58-70 at v clamped to 50: 0 0 0 0 6 6 6 (2.5e-10 c)^2) */
+    double initSigmaDiag[8];      /* dpe_vt_init_from_trk's Sigma (0 -> 100^2 for position and clock, 1 for their rates) */
+    double lockThreshold;         /* a channel is included when mean |P_j| / std |P_j| over the epoch's windows exceeds it (0 -> 4) */
+    int64_t logCapacityEpochs;    /* the log is a ring of this many epochs */
+} dpe_vt_config;
+/* status bits, per epoch in the log and ORed in the device status word */
+#define DPE_VT_BAD_WINDOW 1       /* a window's boundary case was -1, or a sum was not finite: the channel is excluded from that epoch */
+#define DPE_VT_NO_UPDATE 2        /* fewer than four channels included: predict only */
+#define DPE_VT_PIVOT 4            /* a pivot of S was not positive: predict only */
+typedef struct dpe_vt_chan {
+    double rc, ri, fc, fi, cp;    /* parameters of the next epoch's first window; cp counts completed code periods */
+    double sat[8];                /* satellite state at the transmit time those parameters stand for (valid when satValid) */
+    double histRange[DPE_VT_MAX_PREV], histRate[DPE_VT_MAX_PREV];   /* ring of the last included residuals */
+    int32_t histN, histPos;
+} dpe_vt_chan;
+typedef struct dpe_vt_state_rec {
+    double X[8], Sigma[64];       /* ECEF position, c dt, ECEF velocity, c dt'; row-major covariance */
+    double rxTime0, rxBase;       /* receive time of the next epoch's first sample = rxBase + epochs N T */
+    int64_t epochs;
+    int32_t status, satValid;
+    dpe_vt_chan chan[DPE_VT_MAX_CHAN];
+} dpe_vt_state_rec;
+/* One log record per epoch: X [8], diag Sigma [8], rxTime0 (all after the epoch's predict step), included mask, status, number of
+ * included channels; then per channel 12 doubles: rc ri fc fi cp (the next epoch's), range residual (m), rate residual (m/s), the
+ * two W entries used, lock metric, dpc (chips), dfi (Hz). */
+#define DPE_VT_LOG_HEAD 20
+#define DPE_VT_LOG_CHAN 12
+#define DPE_VT_LOG_DOUBLES (DPE_VT_LOG_HEAD + DPE_VT_MAX_CHAN * DPE_VT_LOG_CHAN)
+#define DPE_VT_CORR_DOUBLES 8     /* per window and channel: iE qE iP qP iL qL, boundary case, completed code periods */
+int dpe_vt_create(const dpe_vt_config *cfg, dpe_vt **out);
+int dpe_vt_destroy(dpe_vt *h);
+/* As dpe_nav_set_ephemerides: eph [nChan][DPE_NAV_EPH_DOUBLES], timestamps tow / cp [nChan] (all required here). */
+int dpe_vt_set_ephemerides(dpe_vt *h, const double *eph, const int32_t *tow, const int64_t *cp);
+/* chan [nChan][5] = rc ri fc fi cp at the sample rxTime0 belongs to; Sigma row-major [64].  Resets log, histories and status. Synchronises. */
+int dpe_vt_init(dpe_vt *h, const double *X, const double *Sigma, double rxTime0, const double *chan, dpe_stream_t stream);
+/* The vt_init hand-over: the channels' rc ri fc fi cp are copied on the device from the tracker's loop state -- its parameters of the
+ * next window; no host round trip of them.  fix: the solution of the tracker's LAST TRACKED window (dpe_nav_solve_log at window
+ * nWindows - 1); X and rxTime0 are that fix advanced by the tracker's one window to the sample the channel parameters stand for.
+ * Sigma from initSigmaDiag.  Synchronises before it uploads those; the copy of the channels is enqueued. */
+int dpe_vt_init_from_trk(dpe_vt *h, dpe_trk *trk, const dpe_nav_fix *fix, dpe_stream_t stream);
+/* nEpochs epochs of N windows each on consecutive samples: two launches per epoch, no host synchronisation.  Asynchronous. */
+int dpe_vt_track(dpe_vt *h, const int16_t *samples_dev, int32_t nEpochs, dpe_stream_t stream);
+int dpe_vt_read_log(dpe_vt *h, int64_t firstEpoch, int32_t nEpochs, double *out /* [nEpochs][DPE_VT_LOG_DOUBLES] */, dpe_stream_t stream);
+/* The last tracked epoch's correlations: out[N][nChan][DPE_VT_CORR_DOUBLES]. Synchronises. */
+int dpe_vt_read_corr(dpe_vt *h, double *out, dpe_stream_t stream);
+int dpe_vt_state(dpe_vt *h, dpe_vt_state_rec *out, dpe_stream_t stream);      /* synchronises */
+int dpe_vt_dev_status(dpe_vt *h, int32_t *status, dpe_stream_t stream);       /* OR of the epochs' status bits; synchronises */
+/* One epoch's discriminators, gate, W, update, predict and steering on the host (the same source as vt_filter_kernel): sums
+ * [N][nChan][DPE_VT_CORR_DOUBLES], st in / out, rec [DPE_VT_LOG_DOUBLES] out.  Needs no device. */
+int dpe_vt_filter_step_host(const dpe_vt_config *cfg, const double *eph, const int32_t *tow, const int64_t *cp, dpe_vt_state_rec *st,
+                            const double *sums, double *rec);
+
 /* Per-kernel timing (HIP events recorded on the launch stream around each kernel).  Returns and
  * resets the totals accumulated since the previous call, then sets the enable flag.
  * BCS slots: 0 DC-sum (not launched for single windows, where the bank kernel carries the sums), 1 bank (one launch per

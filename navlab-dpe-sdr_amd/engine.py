@@ -40,6 +40,8 @@ EXPORTS = [
     "dpe_bcm_create_joint", "dpe_bcm_update_joint", "dpe_bcm_results_joint", "dpe_bcm_joint_set_own_keys",
     "dpe_bcm_create_epochs", "dpe_bcm_update_epochs", "dpe_bcm_results_epochs", "dpe_bcm_last_split",
     "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
+    "dpe_vt_create", "dpe_vt_destroy", "dpe_vt_set_ephemerides", "dpe_vt_init", "dpe_vt_init_from_trk", "dpe_vt_track", "dpe_vt_read_log",
+    "dpe_vt_read_corr", "dpe_vt_state", "dpe_vt_dev_status", "dpe_vt_filter_step_host",
 ]
 
 
@@ -1427,6 +1429,154 @@ class ScalarNavigator:
     def close(self):
         if self._h:
             lib().dpe_nav_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:            # at interpreter shutdown module globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+class VtConfig(C.Structure):        # dpe_vt_config
+    _fields_ = [("samplingFrequency", C.c_double), ("T", C.c_double), ("N", C.c_int32), ("nChan", C.c_int32), ("prn", C.c_int32 * 16),
+                ("dopplerSign", C.c_double), ("numPrev", C.c_int32), ("reserved", C.c_int32), ("initVarRange", C.c_double),
+                ("initVarRate", C.c_double), ("minVarRange", C.c_double), ("minVarRate", C.c_double), ("qDiag", C.c_double * 8),
+                ("initSigmaDiag", C.c_double * 8), ("lockThreshold", C.c_double), ("logCapacityEpochs", C.c_int64)]
+
+
+class VtChan(C.Structure):          # dpe_vt_chan
+    _fields_ = [("rc", C.c_double), ("ri", C.c_double), ("fc", C.c_double), ("fi", C.c_double), ("cp", C.c_double), ("sat", C.c_double * 8),
+                ("histRange", C.c_double * 32), ("histRate", C.c_double * 32), ("histN", C.c_int32), ("histPos", C.c_int32)]
+
+
+class VtStateRec(C.Structure):      # dpe_vt_state_rec
+    _fields_ = [("X", C.c_double * 8), ("Sigma", C.c_double * 64), ("rxTime0", C.c_double), ("rxBase", C.c_double), ("epochs", C.c_int64),
+                ("status", C.c_int32), ("satValid", C.c_int32), ("chan", VtChan * 16)]
+
+
+class VectorTracker:
+    """Vector tracking for `prns` (dpe_vt_*): no channel has a loop filter of its own; every epoch of N windows the
+    early / prompt / late correlations of all channels become range and range-rate residuals of one 8-state filter, and every
+    channel's code and carrier NCO is back-computed from the filtered state.  Two kernel launches per epoch, no host synchronisation
+    between epochs."""
+    BAD_WINDOW, NO_UPDATE, PIVOT = 1, 2, 4
+    LOG_HEAD, LOG_CHAN, MAX_CHAN = 20, 12, 16
+    CHAN_NAMES = ("rc", "ri", "fc", "fi", "cp", "eR", "eV", "wR", "wV", "lock", "dpc", "dfi")
+
+    @staticmethod
+    def config(SamplingFrequency, prns, T=1e-3, N=20, ds=1.0, num_prev=20, init_var=(0.0, 0.0), min_var=(0.0, 0.0), q_diag=None,
+               init_sigma_diag=None, lock_threshold=0.0, log_capacity_epochs=4096):
+        prns = [int(p) for p in prns]
+        return VtConfig(float(SamplingFrequency), float(T), int(N), len(prns), (C.c_int32 * 16)(*prns[:16]), float(ds), int(num_prev), 0,
+                        float(init_var[0]), float(init_var[1]), float(min_var[0]), float(min_var[1]),
+                        (C.c_double * 8)(*([0.0] * 8 if q_diag is None else q_diag)),
+                        (C.c_double * 8)(*([0.0] * 8 if init_sigma_diag is None else init_sigma_diag)), float(lock_threshold), int(log_capacity_epochs))
+
+    def __init__(self, SamplingFrequency, prns, **kw):
+        self.prns = [int(p) for p in prns]
+        self.cfg = self.config(SamplingFrequency, prns, **kw)
+        self.fs, self.T, self.N = self.cfg.samplingFrequency, self.cfg.T, self.cfg.N or 20
+        self.S = int(round(self.T * self.fs))
+        self._h = C.c_void_p(None)
+        _check(lib().dpe_vt_create(C.byref(self.cfg), C.byref(self._h)))
+        self.n_epochs = 0
+        self.eph = self.tow = self.cp_timestamp = None
+
+    def set_ephemerides(self, eph, tow, cp):
+        """eph [K, 21] in handoff.EPH_FIELDS order with their timestamps (TOW [K] at code-period count cp [K])."""
+        K = len(self.prns)
+        e, t, c = np.ascontiguousarray(eph, dtype=np.float64), np.ascontiguousarray(tow, dtype=np.int32), np.ascontiguousarray(cp, dtype=np.int64)
+        assert e.shape == (K, 21) and t.shape == (K,) and c.shape == (K,)
+        self.eph, self.tow, self.cp_timestamp = e.copy(), t.copy(), c.copy()
+        _check(lib().dpe_vt_set_ephemerides(self._h, e.ctypes.data_as(C.POINTER(C.c_double)), t.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            c.ctypes.data_as(C.POINTER(C.c_int64))))
+
+    def init(self, X, Sigma, rx_time0, chan, stream=None):
+        """X [8], Sigma [8, 8], the receive time of the first sample and chan [K, 5] = rc ri fc fi cp there."""
+        dp = C.POINTER(C.c_double)
+        x, s, c = (np.ascontiguousarray(v, dtype=np.float64) for v in (X, Sigma, chan))
+        assert x.shape == (8,) and s.size == 64 and c.shape == (len(self.prns), 5)
+        _check(lib().dpe_vt_init(self._h, x.ctypes.data_as(dp), s.ctypes.data_as(dp), C.c_double(rx_time0), c.ctypes.data_as(dp), _stream(stream)))
+        self.n_epochs = 0
+
+    def init_from_tracker(self, tracker, fix, stream=None):
+        """The vt_init hand-over: channel states from `tracker`'s device state (after its last window), X and rxTime0 from `fix`,
+        the solution of the tracker's last tracked window (ScalarNavigator.solve_log(tracker, first=n_windows - 1, n_epochs=1)[0]),
+        advanced by that one window."""
+        f = NavFix((C.c_double * 8)(*np.asarray(fix["X_ECEF"], dtype=np.float64)), float(fix["rxTime"]), float(fix["rxTime_a"]), 0.0, 0, 0)
+        _check(lib().dpe_vt_init_from_trk(self._h, tracker._h, C.byref(f), _stream(stream)))
+        self.n_epochs = 0
+
+    def track(self, Samples, n_epochs, stream=None):
+        """Samples: device int16, n_epochs * N consecutive windows of 2 * S values.  Asynchronous; successive calls continue."""
+        _check(lib().dpe_vt_track(self._h, _ptr(Samples), C.c_int32(n_epochs), _stream(stream)))
+        self.n_epochs += int(n_epochs)
+
+    def read_log(self, first=0, n=None, stream=None):
+        """{X [n, 8], diag [n, 8], rxTime0, mask, status, n_incl [n], and per channel CHAN_NAMES [n, K]} for epochs [first, first + n)."""
+        n = self.n_epochs - first if n is None else int(n)
+        K = len(self.prns)
+        out = np.empty((n, self.LOG_HEAD + self.MAX_CHAN * self.LOG_CHAN), dtype=np.float64)
+        _check(lib().dpe_vt_read_log(self._h, C.c_int64(first), C.c_int32(n), out.ctypes.data_as(C.POINTER(C.c_double)), _stream(stream)))
+        return self.unpack_log(out, K)
+
+    @classmethod
+    def unpack_log(cls, out, K):
+        d = dict(X=out[:, 0:8].copy(), diag=out[:, 8:16].copy(), rxTime0=out[:, 16].copy(), mask=out[:, 17].astype(np.int64),
+                 status=out[:, 18].astype(np.int64), n_incl=out[:, 19].astype(np.int64))
+        ch = out[:, cls.LOG_HEAD:].reshape(out.shape[0], cls.MAX_CHAN, cls.LOG_CHAN)
+        for j, name in enumerate(cls.CHAN_NAMES):
+            d[name] = ch[:, :K, j].copy()
+        return d
+
+    def read_corr(self, stream=None):
+        """The last epoch's correlations [N, K, 8]: iE qE iP qP iL qL, boundary case, completed code periods."""
+        out = np.empty((self.N, len(self.prns), 8), dtype=np.float64)
+        _check(lib().dpe_vt_read_corr(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), _stream(stream)))
+        return out
+
+    def state(self, stream=None):
+        st = VtStateRec()
+        _check(lib().dpe_vt_state(self._h, C.byref(st), _stream(stream)))
+        return self.unpack_state(st, len(self.prns))
+
+    @staticmethod
+    def unpack_state(st, K):
+        d = dict(X=np.array(st.X), Sigma=np.array(st.Sigma).reshape(8, 8), rxTime0=st.rxTime0, epochs=st.epochs, status=st.status)
+        for n in ("rc", "ri", "fc", "fi", "cp"):
+            d[n] = np.array([getattr(st.chan[k], n) for k in range(K)])
+        return d
+
+    def dev_status(self, stream=None):
+        st = C.c_int32()
+        _check(lib().dpe_vt_dev_status(self._h, C.byref(st), _stream(stream)))
+        return st.value
+
+    def handoff(self, bytes_read=0, stream=None):
+        """The state after the last epoch as a handoff dict (handoff.read_handoff's form): what ChanMgr.from_handoff and
+        pipeline.run_closed_loop start from, as ScalarNavigator.handoff's."""
+        s = self.state(stream)
+        return dict(rxTime=s["rxTime0"], rxTime_a=s["rxTime0"] - s["X"][3] / 299792458.0, X_ECEF=s["X"].copy(), bytes_read=int(bytes_read),
+                    prn_list=np.array(self.prns, dtype=np.int32), rc=s["rc"], ri=s["ri"], fc=s["fc"], fi=s["fi"], cp=s["cp"].astype(np.int32),
+                    cp_timestamp=self.cp_timestamp.astype(np.int32), TOW=self.tow.astype(np.int32), eph=self.eph.copy())
+
+    @classmethod
+    def filter_step_host(cls, cfg, eph, tow, cp, st, sums):
+        """dpe_vt_filter_step_host: one epoch's discriminators, gate, W, update, predict and steering on the host.  cfg: config(...);
+        st: a VtStateRec (updated in place); sums [N, K, 8].  Returns the epoch's log record, unpacked."""
+        e, t, c = np.ascontiguousarray(eph, dtype=np.float64), np.ascontiguousarray(tow, dtype=np.int32), np.ascontiguousarray(cp, dtype=np.int64)
+        s = np.ascontiguousarray(sums, dtype=np.float64)
+        assert s.shape == ((cfg.N or 20), cfg.nChan, 8)
+        rec = np.zeros((1, cls.LOG_HEAD + cls.MAX_CHAN * cls.LOG_CHAN))
+        dp = C.POINTER(C.c_double)
+        _check(lib().dpe_vt_filter_step_host(C.byref(cfg), e.ctypes.data_as(dp), t.ctypes.data_as(C.POINTER(C.c_int32)), c.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             C.byref(st), s.ctypes.data_as(dp), rec.ctypes.data_as(dp)))
+        return {k: v[0] for k, v in cls.unpack_log(rec, cfg.nChan).items()}
+
+    def close(self):
+        if self._h:
+            lib().dpe_vt_destroy(self._h)
             self._h = C.c_void_p(None)
 
     def __del__(self):

@@ -248,3 +248,40 @@ def run_epoch_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, n_epochs, time
         bcm.Stop()
         bcs.Stop()
     return np.stack(fixes), results
+
+
+def run_vector_tracking(samples, start, fs, n_epochs=None, T=1e-3, N=20, fix=None, Sigma=None, stream=None, **cfg):
+    """The vector-tracking loop (engine.VectorTracker, DESIGN.md 7e) over `samples` (int16 interleaved I/Q, numpy or a device tensor;
+    n_epochs * N windows of round(T fs) samples from the sample `start` refers to).
+    start: a handoff dict (handoff.read_handoff's / ScalarNavigator.handoff's form: the state and the channels' rc ri fc fi cp at
+    the first sample), or a (ScalarTracker, ScalarNavigator) pair -- then the channels are taken from the tracker's device state and
+    `fix` (default: the navigator's solve_log at the tracker's last window) gives X and rxTime.
+    Returns (log = VectorTracker.read_log's per-epoch states, handoff = the end state as a handoff dict, which ChanMgr.from_handoff
+    and run_closed_loop accept as they accept ScalarNavigator.handoff's, device status)."""
+    import torch
+    from . import engine
+    S = int(round(T * fs))
+    x = samples if hasattr(samples, "data_ptr") else torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int16)).to("cuda:0")
+    if n_epochs is None:
+        n_epochs = int(x.numel() // (2 * S * N))
+    assert x.numel() >= 2 * S * N * n_epochs, "the record is shorter than n_epochs epochs"
+    if isinstance(start, dict):
+        prns = [int(p) for p in start["prn_list"]]
+        vt = engine.VectorTracker(fs, prns, T=T, N=N, log_capacity_epochs=max(int(n_epochs), 1), **cfg)
+        vt.set_ephemerides(start["eph"], start["TOW"], start["cp_timestamp"])
+        chan = np.stack([np.asarray(start[n], dtype=np.float64) for n in ("rc", "ri", "fc", "fi", "cp")], axis=1)
+        Sg = np.diag([1.0e4, 1.0e4, 1.0e4, 1.0e4, 1.0, 1.0, 1.0, 1.0]) if Sigma is None else Sigma
+        vt.init(start["X_ECEF"], Sg, start["rxTime"], chan, stream)
+    else:
+        trk, nav = start
+        vt = engine.VectorTracker(fs, trk.prns, T=T, N=N, log_capacity_epochs=max(int(n_epochs), 1), **cfg)
+        vt.set_ephemerides(nav.eph, nav.tow, nav.cp_timestamp)
+        if fix is None:
+            fix = nav.solve_log(trk, first=trk.n_windows - 1, n_epochs=1, stream=stream)[0]
+        vt.init_from_tracker(trk, fix, stream)
+    vt.track(x, n_epochs, stream)
+    log = vt.read_log(stream=stream)
+    ho = vt.handoff(bytes_read=4 * S * N * n_epochs, stream=stream)
+    status = vt.dev_status(stream)
+    vt.close()
+    return log, ho, status
