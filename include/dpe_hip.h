@@ -427,6 +427,45 @@ int dpe_bcm_update_epochs(dpe_bcm *h, const float *codeBank_dev, const float *ca
 /* Waits for the last epochs Update.  results: [nGroups]. */
 int dpe_bcm_results_epochs(dpe_bcm *h, dpe_bcm_epochs_result *results, dpe_stream_t stream);
 
+/* Every SV subset's fix from ONE scan -- solution separation / fault exclusion for a single receiver.  One satellite with a biased code
+ * phase (a strong reflection, a spoofed PRN) pulls the maximum-likelihood point; the classical answer is to fix with every SV, fix again
+ * with each SV left out, and compare.  The per-(point, SV) term does not depend on which other SVs it is summed with, so one launch
+ * evaluates it once and yields the first maximum of the full set and of up to 16 subsets per window.  Subset m of window w is a 64-bit
+ * mask over the window's channels (bit k = channel k of chan_host); its score at a point is the sum of its SVs' terms from 0 in SV order,
+ * so its key, index, score, zVal and out-of-window count are, bit for bit, what dpe_bcm_update gives when it is handed only those
+ * channels.  An excluded SV's term is skipped, never multiplied by 0: a NaN of an excluded SV does not reach the subset's sum.  The full
+ * set's score row, key and counts are those of dpe_bcm_update on all channels; subset rows are not written.  Out-of-window pairs are
+ * counted per SV and per manifold; a subset's count is the sum of its SVs' counts.  nSubsets = 0 is the plain scan.  A set none of whose
+ * points has a score (a channel with NaN banks in it) reports index -1, score 0 and NaN offset / zVal for that manifold; the window's
+ * other sets stand.  This is the one case outside the bit contract above: dpe_bcm_update followed by dpe_bcm_results fails on such
+ * channels ("arg-max index outside the local shard"), so there is nothing to equal.
+ * Limits, each refused with a message before anything is launched: 1 <= maxSubsets <= 16; maxChannels * ((2 max(L,B) + 1) * 16 + 32)
+ * <= 150 KB (the LDS budget of dpe_bcm_config; no 12-byte bank entries here); point-list grids only; weightedMean, referencePair and the
+ * grid index offsets must be 0; an empty mask; a mask bit at or above nChan; nSubsets > maxSubsets.
+ * On such a handle dpe_bcm_scores / dpe_bcm_scores_pitch / dpe_bcm_keys / dpe_bcm_export_scores_f64 / dpe_bcm_profile / dpe_bcm_last_split
+ * work unchanged on the FULL set's rows and keys.  Refused, each with a message: dpe_bcm_update / _update_dev / _update_prepared,
+ * dpe_bcm_results, dpe_bcm_results_from_keys and dpe_bcm_exchange_keys (sharding), dpe_bcm_set_graph, dpe_chm_dev_attach (the
+ * device-resident loop) and the joint and epochs calls; the calls below are refused on every other kind of handle. */
+typedef struct dpe_bcm_subset_result {
+    double zVal[8];                 /* the window's centre moved by this subset's ML offsets (BCM_MakePosMeas / MakeVelMeas) */
+    double offset[8];               /* the grid rows at the two maxima: ENU-dt position offset, ENU-dt_dot velocity offset */
+    int64_t posIndex;               /* first maximum of the subset's position / velocity score */
+    int64_t velIndex;
+    float posScore;
+    float velScore;
+    int64_t posOutOfWindow;         /* (point, SV) pairs of the subset's SVs whose index left a bank */
+    int64_t velOutOfWindow;
+} dpe_bcm_subset_result;
+int dpe_bcm_create_subsets(const dpe_bcm_config *cfg, int32_t maxSubsets, dpe_bcm **out);
+/* Arrays as for dpe_bcm_update; masks_host: HOST [nWindows][nSubsets] (may be NULL when nSubsets = 0).  Asynchronous on `stream`; the host
+ * arrays are consumed before the call returns. */
+int dpe_bcm_update_subsets(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, int32_t nWindows, int32_t nChan,
+                           const dpe_bcm_window *win_host, const dpe_chan_end *chan_host, int32_t nSubsets, const uint64_t *masks_host,
+                           dpe_stream_t stream);
+/* Waits for the last subsets Update.  full: [nWindows]; subs: [nWindows][nSubsets] (may be NULL when nSubsets = 0); oobPerSv: NULL or
+ * [nWindows][2][nChan] (manifold 0 position, 1 velocity). */
+int dpe_bcm_results_subsets(dpe_bcm *h, dpe_bcm_subset_result *full, dpe_bcm_subset_result *subs, int64_t *oobPerSv, dpe_stream_t stream);
+
 /* ------------------------------------------------------------------ batches in flight ------ */
 /* Several batches of the path on the device at once -- what the reference gets from SampleBlock's 32-slot ring and reader thread
  * (sampleblock.cu:327-447) and from the side streams of BatchCorrScores / BatchCorrManifold (batchcorrscores.h:60-64,

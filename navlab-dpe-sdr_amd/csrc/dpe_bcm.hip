@@ -426,6 +426,7 @@ __global__ __launch_bounds__(256) void bcm_scan_kernel(BcmParamBlock pb, int inl
 #include "dpe_bcm_axes.h"
 #include "dpe_bcm_joint.h"
 #include "dpe_bcm_epochs.h"
+#include "dpe_bcm_subsets.h"
 
 namespace dpe {
 
@@ -675,6 +676,13 @@ struct dpe_bcm {
     bool epochs = false;
     int epMaxEpochs = 0, epPairsPerPass = 0;   // windows per group; (window, SV) pairs whose banks share the LDS in one pass
     int lastEpochs = 0, lastPasses = 0;     // what the last epochs Update ran with
+    // the arg-max of every SV subset of a window from one scan (dpe_bcm_create_subsets)
+    bool subsets = false;
+    int subMax = 0, lastSubsets = 0, lastChan = 0;   // subsets per window the handle holds; what the last subsets Update ran with
+    bool lastCounted = false;               // the last subsets Update ran a clamped variant (only then are the per-SV counters written)
+    unsigned long long *sub_d = nullptr;    // {masks [W][subMax], subset keys [W][2][subMax], per-SV out-of-window counts [W][2][maxK]}
+    unsigned long long *subMaskBase_h = nullptr;   // pinned staging ring of the masks
+    std::vector<unsigned long long> sub_h, subMask_h;   // host copies: keys and counts of the last Update; its masks
     dpe::KernelProfiler prof;  // slot 0: the fused position + velocity scan
     dpe::GraphCache graphs;
 };
@@ -924,6 +932,53 @@ static void allow_big_lds_epochs()
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
     DPE_EPOCHS_LDS(true, true); DPE_EPOCHS_LDS(true, false); DPE_EPOCHS_LDS(false, true); DPE_EPOCHS_LDS(false, false);
 #undef DPE_EPOCHS_LDS
+}
+
+// Every SV subset's arg-max from one scan (dpe_bcm_update_subsets)
+struct SubsetsLaunch {
+    dpe::ScanSide sp, sv;
+    int K, maxK, lp, nSubsets, maxSubsets;
+    const unsigned long long *masks;
+    unsigned long long *keys, *oob, *subKeys, *svOob, *clr;
+    int clrN;
+    unsigned int *done;
+    unsigned long long *hostKeys, *hostOob, seq;
+    dim3 grid;
+    size_t lds;
+    hipStream_t st;
+};
+
+template <int LP, bool CP, bool CV, bool SUBS>
+static void launch_subsets4(const SubsetsLaunch &a)
+{
+    hipLaunchKernelGGL((dpe::bcm_scan_subsets_kernel<LP, CP, CV, SUBS>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.K, a.maxK, a.lp, a.masks, a.nSubsets,
+                       a.maxSubsets, a.keys, a.oob, a.subKeys, a.svOob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+}
+
+template <bool CP, bool CV, bool SUBS>
+static void launch_subsets3(const SubsetsLaunch &a)
+{
+    if (a.lp == 1) launch_subsets4<1, CP, CV, SUBS>(a);
+    else if (a.lp == 2) launch_subsets4<2, CP, CV, SUBS>(a);
+    else launch_subsets4<0, CP, CV, SUBS>(a);
+}
+
+static void launch_subsets(bool clampP, bool clampV, const SubsetsLaunch &a)
+{
+#define DPE_SUBSETS_PICK(CP, CV) do { if (a.nSubsets > 0) launch_subsets3<CP, CV, true>(a); else launch_subsets3<CP, CV, false>(a); } while (0)
+    if (clampP) { if (clampV) DPE_SUBSETS_PICK(true, true); else DPE_SUBSETS_PICK(true, false); }
+    else { if (clampV) DPE_SUBSETS_PICK(false, true); else DPE_SUBSETS_PICK(false, false); }
+#undef DPE_SUBSETS_PICK
+}
+
+template <int LP>
+static void allow_big_lds_subsets()
+{
+#define DPE_SUBSETS_LDS(CP, CV, SUBS) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_subsets_kernel<LP, CP, CV, SUBS>, \
+                                                                hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
+    DPE_SUBSETS_LDS(true, true, false); DPE_SUBSETS_LDS(true, false, false); DPE_SUBSETS_LDS(false, true, false); DPE_SUBSETS_LDS(false, false, false);
+    DPE_SUBSETS_LDS(true, true, true); DPE_SUBSETS_LDS(true, false, true); DPE_SUBSETS_LDS(false, true, true); DPE_SUBSETS_LDS(false, false, true);
+#undef DPE_SUBSETS_LDS
 }
 
 // ---- referencePair mode ---------------------------------------------------------------------
@@ -1287,6 +1342,47 @@ int dpe_bcm_create_epochs(const dpe_bcm_config *cfg, int32_t maxEpochs, int32_t 
     return 0;
 }
 
+// One scan, the arg-max of every SV subset (dpe_bcm_subsets.h).  The masks, the subset keys and the per-SV out-of-window counts
+// live in one device block beside the handle's ordinary key sets.
+int dpe_bcm_create_subsets(const dpe_bcm_config *cfg, int32_t maxSubsets, dpe_bcm **out)
+{
+    using namespace dpe;
+    DPE_REQUIRE(cfg && out, "[BatchCorrManifold] create_subsets: null argument");
+    DPE_REQUIRE(maxSubsets >= 1 && maxSubsets <= kSubsetMax, "[BatchCorrManifold] create_subsets: maxSubsets %d out of range (1 .. %d subsets per window)",
+                maxSubsets, kSubsetMax);
+    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
+                "[BatchCorrManifold] create_subsets: maxWindows/maxChannels out of range");
+    DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1, "[BatchCorrManifold] create_subsets: bad L/B");
+    DPE_REQUIRE(!cfg->weightedMean, "[BatchCorrManifold] create_subsets: the weighted-mean estimator is not formed per subset (weightedMean must be 0)");
+    DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_subsets: referencePair re-evaluates the full set only (referencePair must be 0)");
+    DPE_REQUIRE(cfg->posGridIndexOffset == 0 && cfg->velGridIndexOffset == 0,
+                "[BatchCorrManifold] create_subsets: grid shards are not supported (the index offsets must be 0)");
+    const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
+    const size_t ldsNeed = (size_t)cfg->maxChannels * (nEntMax * 16 + 32);
+    DPE_REQUIRE(ldsNeed <= 150 * 1024, "[BatchCorrManifold] create_subsets: the score banks of %d channels x %zu entries (%zu B) exceed the 150 KB the "
+                                       "subsets scan keeps in LDS (no 12-byte bank entries here)", cfg->maxChannels, nEntMax, ldsNeed);
+    dpe_bcm *h = nullptr;
+    if (bcm_create_points(cfg, nullptr, 0, 0, &h)) return -1;
+    const size_t W = cfg->maxWindows, n = W * (size_t)maxSubsets + 2 * W * (size_t)maxSubsets + 2 * W * (size_t)cfg->maxChannels;
+    const auto finish = [&]() -> int {
+        h->sub_d = dev_alloc<unsigned long long>(n);
+        DPE_REQUIRE(h->sub_d, "[BatchCorrManifold] create_subsets: device allocation failed");
+        DPE_CHECK_HIP(hipHostMalloc((void **)&h->subMaskBase_h, dpe_bcm::kStaging * W * (size_t)maxSubsets * sizeof(unsigned long long), hipHostMallocDefault));
+        return 0;
+    };
+    if (finish()) {
+        dpe_bcm_destroy(h);
+        return -1;
+    }
+    h->subsets = true;
+    h->subMax = maxSubsets;
+    h->sub_h.assign(n, 0ull);
+    h->subMask_h.assign(W * (size_t)maxSubsets, 0ull);
+    allow_big_lds_subsets<0>(); allow_big_lds_subsets<1>(); allow_big_lds_subsets<2>();
+    *out = h;
+    return 0;
+}
+
 // Grids given by their axes.  donor != nullptr: a further lane of a dpe_pipe, which uses donor's device copy of the axes.
 int dpe_bcm_create_axes_sharing(const dpe_bcm_config *cfg, const dpe_grid_axes *pos, const dpe_grid_axes *vel, dpe_bcm *donor,
                                 dpe_bcm **out)
@@ -1393,6 +1489,8 @@ int dpe_bcm_destroy(dpe_bcm *h)
     if (h->refBank_h) (void)hipHostFree(h->refBank_h);
     if (h->jrxBase_h) (void)hipHostFree(h->jrxBase_h);
     (void)hipFree(h->jrx_d); (void)hipFree(h->own_d);
+    if (h->subMaskBase_h) (void)hipHostFree(h->subMaskBase_h);
+    (void)hipFree(h->sub_d);
     (void)hipFree(h->refCand_d); (void)hipFree(h->refWhere_d); (void)hipFree(h->refValue_d); (void)hipFree(h->refOld_d);
     for (hipEvent_t e : h->stagingFree)
         if (e) (void)hipEventDestroy(e);
@@ -1460,6 +1558,7 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
     DPE_REQUIRE(h && codeBank_dev && carrBank_dev, "[BatchCorrManifold] Update: null argument");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] Update: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_update_epochs");
+    DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] Update: this handle scans SV subsets (dpe_bcm_create_subsets): use dpe_bcm_update_subsets");
     DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] Update: nWindows %d out of range", nWindows);
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     hipStream_t stream = (hipStream_t)stream_;
@@ -1766,6 +1865,93 @@ int dpe_bcm_update_epochs(dpe_bcm *h, const float *codeBank_dev, const float *ca
     return 0;
 }
 
+// One launch scores every (point, SV) pair once and reduces the full set and every subset to its own first maximum
+// (dpe_bcm_subsets.h).
+int dpe_bcm_update_subsets(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, int32_t nWindows, int32_t nChan,
+                           const dpe_bcm_window *win_host, const dpe_chan_end *chan_host, int32_t nSubsets, const uint64_t *masks_host,
+                           dpe_stream_t stream_)
+{
+    using namespace dpe;
+    DPE_REQUIRE(h && codeBank_dev && carrBank_dev && win_host && chan_host, "[BatchCorrManifold] update_subsets: null argument");
+    DPE_REQUIRE(h->subsets, "[BatchCorrManifold] update_subsets: the handle was not made by dpe_bcm_create_subsets");
+    // everything is checked before anything is staged or launched
+    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] update_subsets: nWindows %d out of range", nWindows);
+    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] update_subsets: nChan %d out of range", nChan);
+    DPE_REQUIRE(nSubsets >= 0 && nSubsets <= h->subMax, "[BatchCorrManifold] update_subsets: nSubsets %d out of range (the handle holds %d subsets per window)",
+                nSubsets, h->subMax);
+    DPE_REQUIRE(nSubsets == 0 || masks_host, "[BatchCorrManifold] update_subsets: null masks");
+    for (int w = 0; w < nWindows; ++w) {
+        DPE_REQUIRE(win_host[w].dopplerSign == 1 || win_host[w].dopplerSign == -1, "[BatchCorrManifold] update_subsets: dopplerSign must be +/-1");
+        for (int m = 0; m < nSubsets; ++m) {
+            const uint64_t mask = masks_host[(size_t)w * nSubsets + m];
+            DPE_REQUIRE(mask != 0, "[BatchCorrManifold] update_subsets: window %d subset %d: empty mask", w, m);
+            DPE_REQUIRE(nChan >= 64 || (mask >> nChan) == 0, "[BatchCorrManifold] update_subsets: window %d subset %d: mask 0x%llx has a bit at or above nChan %d",
+                        w, m, (unsigned long long)mask, nChan);
+        }
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int maxK = h->cfg.maxChannels, W = h->cfg.maxWindows, maxS = h->subMax;
+    bool posInside = true, velInside = true;
+    h->lastDev = false;
+    h->slot = (h->slot + 1) % dpe_bcm::kStaging;
+    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
+    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * W * maxK;
+    unsigned long long *mask_h = h->subMaskBase_h + (size_t)h->slot * W * maxS;
+    for (int w = 0; w < nWindows; ++w) {
+        h->win_h[w] = win_host[w];
+        for (int k = 0; k < nChan; ++k)
+            bcm_expand(h, win_host[w], chan_host[(size_t)w * nChan + k], h->sv_h[(size_t)(0 * W + w) * maxK + k], h->sv_h[(size_t)(1 * W + w) * maxK + k],
+                       posInside, velInside);
+        for (int m = 0; m < maxS; ++m)
+            h->subMask_h[(size_t)w * maxS + m] = mask_h[(size_t)w * maxS + m] = m < nSubsets ? masks_host[(size_t)w * nSubsets + m] : 0ull;
+    }
+    h->lastW = nWindows;
+    h->lastSubsets = nSubsets;
+    h->lastChan = nChan;
+    h->lastSplit[0] = scan_split(h->cfg.posGridSize, nWindows, h->splitForce);
+    h->lastSplit[1] = scan_split(h->cfg.velGridSize, nWindows, h->splitForce);
+    const int use = h->cur ^ 1;
+    unsigned long long *keys = h->keys_d + (size_t)use * 4 * W, *oob = keys + 2 * W;
+    unsigned long long *other = h->keys_d + (size_t)(use ^ 1) * 4 * W;
+    unsigned long long *masks_d = h->sub_d, *subKeys_d = masks_d + (size_t)W * maxS, *svOob_d = subKeys_d + 2 * (size_t)W * maxS;
+    DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sizeof(BcmSvDev) * 2 * (size_t)W * maxK, hipMemcpyHostToDevice, stream));
+    // nSubsets = 0 with every index inside the banks is the plain scan on the launch side as well: no mask copy, nothing to clear
+    // (the kernel then touches neither the subset keys nor the per-SV counters, which the results call reports as 0)
+    if (nSubsets > 0) DPE_CHECK_HIP(hipMemcpyAsync(masks_d, mask_h, sizeof(unsigned long long) * (size_t)W * maxS, hipMemcpyHostToDevice, stream));
+    DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
+    h->lastCounted = !posInside || !velInside;
+    if (nSubsets > 0) DPE_CHECK_HIP(hipMemsetAsync(subKeys_d, 0, sizeof(unsigned long long) * (2 * (size_t)W * maxS + 2 * (size_t)W * maxK), stream));
+    else if (h->lastCounted) DPE_CHECK_HIP(hipMemsetAsync(svOob_d, 0, sizeof(unsigned long long) * 2 * (size_t)W * maxK, stream));
+    const int nLag = 2 * h->cfg.lagHalfWidth + 1, nBin = 2 * h->cfg.binHalfWidth + 1;
+    SubsetsLaunch a;
+    a.sp = ScanSide{h->posGrid_d, reinterpret_cast<const float2 *>(codeBank_dev), h->sv_d, h->posScores_d, nullptr, h->cfg.posGridSize, 0, h->posPitch, nLag,
+                    (int)h->lastSplit[0]};
+    a.sv = ScanSide{h->velGrid_d, reinterpret_cast<const float2 *>(carrBank_dev), h->sv_d + (size_t)W * maxK, h->velScores_d, nullptr, h->cfg.velGridSize, 0,
+                    h->velPitch, nBin, (int)h->lastSplit[1]};
+    a.K = nChan; a.maxK = maxK; a.lp = h->cfg.lPower; a.nSubsets = nSubsets; a.maxSubsets = maxS;
+    a.masks = masks_d; a.subKeys = subKeys_d; a.svOob = svOob_d;
+    a.keys = keys; a.oob = oob; a.clr = other; a.clrN = 4 * W;
+    a.done = h->done_d; a.hostKeys = h->keys_hd; a.hostOob = h->keys_hd + 2 * W;
+    h->lastPublished = true;
+    a.seq = ++h->seq;
+    h->pollable = false;   // (the per-subset results are fetched behind a stream wait)
+    a.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], nWindows, 2);
+    a.lds = (size_t)nChan * (nLag > nBin ? nLag : nBin) * 16;   // <= maxChannels rows: inside the budget create checked
+    a.st = stream;
+    h->prof.begin(0, stream);
+    launch_subsets(!posInside, !velInside, a);
+    h->prof.end(0, stream);
+    {
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) {
+            dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
+            return -1;
+        }
+    }
+    h->cur = use;
+    return 0;
+}
+
 int dpe_bcm_joint_set_own_keys(dpe_bcm *h, int32_t enable)
 {
     DPE_REQUIRE(h && h->joint, "[BatchCorrManifold] joint_set_own_keys: not a handle of dpe_bcm_create_joint");
@@ -1780,6 +1966,7 @@ int dpe_bcm_update_dev(dpe_bcm *h, const float *codeBank_dev, const float *carrB
     DPE_REQUIRE(h && ports, "[BatchCorrManifold] Update: null argument");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");   // (before the prep kernel: a refusal launches nothing)
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] Update: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_update_epochs");
+    DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] Update: this handle scans SV subsets (dpe_bcm_create_subsets): use dpe_bcm_update_subsets");
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     DPE_REQUIRE(!h->refPair || (h->cfg.writeScores && !h->cfg.weightedMean),
                 "[BatchCorrManifold] Update: referencePair with the device ports patches the scores on the device: it needs writeScores and no weightedMean "
@@ -1832,6 +2019,7 @@ int dpe_bcm_hook_get(dpe_bcm *h, dpe_bcm_hook *out)
     DPE_REQUIRE(h && out, "[BatchCorrManifold] hook: null argument");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] hook: a joint handle (dpe_bcm_create_joint) cannot serve the device-resident loop or a dpe_pipe lane");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] hook: an epochs handle (dpe_bcm_create_epochs) cannot serve the device-resident loop or a dpe_pipe lane");
+    DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] hook: a subsets handle (dpe_bcm_create_subsets) cannot serve the device-resident loop or a dpe_pipe lane");
     const size_t W = h->cfg.maxWindows, maxK = h->cfg.maxChannels;
     if (h->axes && !h->posAx64_d) {   // the global axes in fp64 (a few KB): the measurement kernel decodes its index from them
         dpe_bcm::Axes *ax[2] = {&h->posAx, &h->velAx};
@@ -1894,6 +2082,7 @@ int dpe_bcm_set_graph(dpe_bcm *h, int32_t enable)
     DPE_REQUIRE(h, "[BatchCorrManifold] set_graph: null handle");
     DPE_REQUIRE(!h->joint || !enable, "[BatchCorrManifold] set_graph: joint Updates (dpe_bcm_update_joint) always launch eagerly");
     DPE_REQUIRE(!h->epochs || !enable, "[BatchCorrManifold] set_graph: epochs Updates (dpe_bcm_update_epochs) always launch eagerly");
+    DPE_REQUIRE(!h->subsets || !enable, "[BatchCorrManifold] set_graph: subsets Updates (dpe_bcm_update_subsets) always launch eagerly");
     h->graphs.enabled = enable != 0;
     if (!enable) h->graphs.clear();
     return 0;
@@ -1956,6 +2145,7 @@ int dpe_bcm_results(dpe_bcm *h, dpe_bcm_result *results, dpe_stream_t stream)
     DPE_REQUIRE(h && results && h->lastW > 0, "[BatchCorrManifold] results: no update yet");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] results: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_results_joint");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] results: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_results_epochs");
+    DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] results: this handle scans SV subsets (dpe_bcm_create_subsets): use dpe_bcm_results_subsets");
     // Single-window Updates: the scan's last block writes a sequence word right behind the results in the pinned
     // mirror.  Polling it returns the fix as soon as it lands, without the stream-wait wake-up (a few us of a ~58 us
     // closed-loop window); anything unexpected falls back to the stream wait.
@@ -2076,6 +2266,59 @@ int dpe_bcm_results_epochs(dpe_bcm *h, dpe_bcm_epochs_result *results, dpe_strea
     return 0;
 }
 
+int dpe_bcm_results_subsets(dpe_bcm *h, dpe_bcm_subset_result *full, dpe_bcm_subset_result *subs, int64_t *oobPerSv, dpe_stream_t stream)
+{
+    DPE_REQUIRE(h && full, "[BatchCorrManifold] results_subsets: null argument");
+    DPE_REQUIRE(h->subsets, "[BatchCorrManifold] results_subsets: the handle was not made by dpe_bcm_create_subsets");
+    DPE_REQUIRE(h->lastW > 0, "[BatchCorrManifold] results_subsets: no subsets update yet");
+    DPE_REQUIRE(subs || h->lastSubsets == 0, "[BatchCorrManifold] results_subsets: null argument (the last Update ran %d subsets)", h->lastSubsets);
+    DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    const int W = h->lastW, M = h->lastSubsets, K = h->lastChan, maxS = h->subMax, maxK = h->cfg.maxChannels;
+    const size_t Wm = h->cfg.maxWindows;
+    // keys and counts only (the masks in front of them are the host's own); nothing was written when no subset was asked for and
+    // no variant clamped
+    if (M > 0 || h->lastCounted)
+        DPE_CHECK_HIP(hipMemcpy(h->sub_h.data() + Wm * maxS, h->sub_d + Wm * maxS, sizeof(unsigned long long) * (h->sub_h.size() - Wm * maxS),
+                                hipMemcpyDeviceToHost));
+    if (!h->lastCounted) std::fill(h->sub_h.begin() + 3 * Wm * maxS, h->sub_h.end(), 0ull);
+    const unsigned long long *subKeys = h->sub_h.data() + Wm * maxS, *svOob = subKeys + 2 * Wm * maxS;
+    const unsigned long long *keys = h->keys_h, *oob = h->oob_h;
+    // A key of 0 means that no point of the row had a score (every sum NaN: a channel with NaN banks in the set): index -1,
+    // score 0 and NaN offsets / zVal for that manifold -- the other subsets of the window, which leave that channel out, stand.
+    const auto fill = [&](dpe_bcm_subset_result &r, int w, unsigned long long pk, unsigned long long vk) -> int {
+        const double nan4[4] = {NAN, NAN, NAN, NAN};
+        decode_key(pk, &r.posScore, &r.posIndex);
+        decode_key(vk, &r.velScore, &r.velIndex);
+        if (!pk) { r.posIndex = -1; r.posScore = 0.f; }
+        if (!vk) { r.velIndex = -1; r.velScore = 0.f; }
+        DPE_REQUIRE((!pk || (r.posIndex >= 0 && r.posIndex < h->cfg.posGridSize)) && (!vk || (r.velIndex >= 0 && r.velIndex < h->cfg.velGridSize)),
+                    "[BatchCorrManifold] results_subsets: arg-max index outside the grids");
+        const double *pp = pk ? h->posGrid_h.data() + 4 * r.posIndex : nan4, *vp = vk ? h->velGrid_h.data() + 4 * r.velIndex : nan4;
+        for (int c = 0; c < 4; ++c) { r.offset[c] = pp[c]; r.offset[4 + c] = vp[c]; }
+        make_meas(h->win_h[w], pp, vp, r.zVal);
+        return 0;
+    };
+    for (int w = 0; w < W; ++w) {
+        if (fill(full[w], w, keys[2 * w], keys[2 * w + 1])) return -1;
+        full[w].posOutOfWindow = (int64_t)oob[2 * w];
+        full[w].velOutOfWindow = (int64_t)oob[2 * w + 1];
+        const unsigned long long *po = svOob + ((size_t)w * 2 + 0) * maxK, *vo = svOob + ((size_t)w * 2 + 1) * maxK;
+        for (int k = 0; oobPerSv && k < K; ++k) {
+            oobPerSv[((size_t)w * 2 + 0) * K + k] = (int64_t)po[k];
+            oobPerSv[((size_t)w * 2 + 1) * K + k] = (int64_t)vo[k];
+        }
+        for (int m = 0; m < M; ++m) {
+            dpe_bcm_subset_result &r = subs[(size_t)w * M + m];
+            if (fill(r, w, subKeys[((size_t)w * 2 + 0) * maxS + m], subKeys[((size_t)w * 2 + 1) * maxS + m])) return -1;
+            const unsigned long long mask = h->subMask_h[(size_t)w * maxS + m];
+            r.posOutOfWindow = r.velOutOfWindow = 0;
+            for (int k = 0; k < K; ++k)
+                if ((mask >> k) & 1ull) { r.posOutOfWindow += (int64_t)po[k]; r.velOutOfWindow += (int64_t)vo[k]; }   // a subset's count: the sum of its SVs'
+        }
+    }
+    return 0;
+}
+
 int dpe_bcm_profile(dpe_bcm *h, int32_t enable, float *ms, int32_t *count)
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] profile: null handle");
@@ -2143,6 +2386,7 @@ int dpe_bcm_exchange_keys(dpe_bcm *h, dpe_comm *c, uint64_t *keys_host, dpe_stre
     DPE_REQUIRE(h && c && h->lastW > 0, "[BatchCorrManifold] exchange_keys: no update yet / null communicator");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] exchange_keys: a joint handle (dpe_bcm_create_joint) scans whole grids: sharding is not supported");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] exchange_keys: an epochs handle (dpe_bcm_create_epochs) scans whole grids: sharding is not supported");
+    DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] exchange_keys: a subsets handle (dpe_bcm_create_subsets) scans whole grids: sharding is not supported");
     unsigned long long *keys = h->keys_d + (size_t)h->cur * 4 * h->cfg.maxWindows;
     if (dpe_comm_allreduce_max_u64(c, reinterpret_cast<uint64_t *>(keys), 2 * (int64_t)h->lastW, stream)) return -1;
     if (keys_host) {
@@ -2161,6 +2405,7 @@ int dpe_bcm_results_from_keys(dpe_bcm *h, const uint64_t *keys_host, int32_t nWi
                 "[BatchCorrManifold] results_from_keys: null argument (both global grids, or neither for a handle with grid axes)");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] results_from_keys: a joint handle (dpe_bcm_create_joint) scans whole grids: use dpe_bcm_results_joint");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] results_from_keys: an epochs handle (dpe_bcm_create_epochs) scans whole grids: use dpe_bcm_results_epochs");
+    DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] results_from_keys: a subsets handle (dpe_bcm_create_subsets) scans whole grids: use dpe_bcm_results_subsets");
     if (!posGridGlobal) {   // an axes handle decodes from its axes, which are the global ones
         posGridGlobalSize = axes_size(h->posAx);
         velGridGlobalSize = axes_size(h->velAx);

@@ -39,6 +39,7 @@ EXPORTS = [
     "dpe_trk_read_cp_signs", "dpe_trk_state", "dpe_trk_dev_status",
     "dpe_bcm_create_joint", "dpe_bcm_update_joint", "dpe_bcm_results_joint", "dpe_bcm_joint_set_own_keys",
     "dpe_bcm_create_epochs", "dpe_bcm_update_epochs", "dpe_bcm_results_epochs", "dpe_bcm_last_split",
+    "dpe_bcm_create_subsets", "dpe_bcm_update_subsets", "dpe_bcm_results_subsets",
     "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
     "dpe_vt_create", "dpe_vt_destroy", "dpe_vt_set_ephemerides", "dpe_vt_init", "dpe_vt_init_from_trk", "dpe_vt_track", "dpe_vt_read_log",
     "dpe_vt_read_corr", "dpe_vt_state", "dpe_vt_dev_status", "dpe_vt_filter_step_host",
@@ -118,6 +119,11 @@ class BcmEpochsResult(C.Structure):  # dpe_bcm_epochs_result
     _fields_ = [("zVal", C.c_double * 8), ("offset", C.c_double * 8), ("posIndex", C.c_int64), ("velIndex", C.c_int64),
                 ("posScore", C.c_float), ("velScore", C.c_float), ("posOutOfWindow", C.c_int64), ("velOutOfWindow", C.c_int64),
                 ("nPasses", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BcmSubsetResult(C.Structure):  # dpe_bcm_subset_result
+    _fields_ = [("zVal", C.c_double * 8), ("offset", C.c_double * 8), ("posIndex", C.c_int64), ("velIndex", C.c_int64),
+                ("posScore", C.c_float), ("velScore", C.c_float), ("posOutOfWindow", C.c_int64), ("velOutOfWindow", C.c_int64)]
 
 
 CHAN_START_DTYPE = np.dtype([("codePhaseStart", "<f8"), ("carrierPhaseStart", "<f8"), ("codeFrequency", "<f8"),
@@ -778,6 +784,95 @@ class EpochManifold(BatchCorrManifold):
         raise DpeError("[BatchCorrManifold] an epochs handle takes its inputs through Update(..., n_epochs) only")
 
     UpdatePrepared = exchange_keys = results_from_keys = UpdateDev
+
+
+SUBSET_MAX = 16      # kSubsetMax: subsets per window of one scan
+
+
+def leave_one_out_masks(K):
+    """The K single-SV exclusions of K channels as uint64 masks [K]: mask j holds every channel but j."""
+    K = int(K)
+    if not 2 <= K <= 64:
+        raise DpeError("[BatchCorrManifold] leave_one_out_masks: K %d out of range (2 .. 64)" % K)
+    full = (1 << K) - 1
+    return np.array([full & ~(1 << j) for j in range(K)], dtype=np.uint64)
+
+
+class SubsetManifold(BatchCorrManifold):
+    """The arg-max of every SV subset of a window from one scan (dpe_bcm_create_subsets): solution separation / fault exclusion.
+    A subset is a uint64 mask over the window's channels; its key, fix and out-of-window count carry the bits of an Update on those
+    channels alone.  PosScores / VelScores / Keys are the FULL set's rows and keys; subset rows are not written."""
+
+    def __init__(self, SamplingFrequency, samples_per_window, NumFFTPoints, pos_grid, vel_grid, max_subsets, LPower=1,
+                 lag_half_width=8, bin_half_width=48, max_windows=1, max_channels=8, write_scores=True):
+        super().__init__(SamplingFrequency, samples_per_window, NumFFTPoints, pos_grid, vel_grid, LPower=LPower,
+                         lag_half_width=lag_half_width, bin_half_width=bin_half_width, max_windows=max_windows,
+                         max_channels=max_channels, write_scores=write_scores)
+        if self.axes:
+            raise DpeError("[BatchCorrManifold] create_subsets: point-list grids only (GridAxes are not supported)")
+        self.max_subsets = int(max_subsets)
+        self._M = self._K = 0
+
+    def Start(self):
+        if self.Started:
+            return 0
+        cfg = _bcm_config(self.S, self.L, self.B, self.LPower, self.max_windows, self.max_channels, self.C, self.fs, self.pos_grid,
+                          self.vel_grid, 0, 0, False, self.write_scores, False, False)
+        _check(lib().dpe_bcm_create_subsets(C.byref(cfg), C.c_int32(self.max_subsets), C.byref(self._h)))
+        self._bind_outputs()
+        return 0
+
+    def Update(self, CodeScores, CarrScores, win, chan, masks=None, stream=None):
+        """win, chan, banks as for BatchCorrManifold.Update; masks: uint64 [M] (the same subsets for every window) or [W, M];
+        None or empty: the plain scan."""
+        if not self.Started:
+            raise DpeError("[BatchCorrManifold] Error: Update() Failed due to module not initialized")
+        win = np.ascontiguousarray(np.atleast_1d(win))
+        chan = np.ascontiguousarray(chan)
+        if chan.ndim == 1:
+            chan = chan[None, :]
+        W, K = chan.shape
+        assert win.shape[0] == W
+        masks = np.zeros((W, 0), dtype=np.uint64) if masks is None else np.asarray(masks, dtype=np.uint64)
+        if masks.ndim == 1:
+            masks = np.broadcast_to(masks, (W, masks.shape[0]))
+        if masks.ndim != 2 or masks.shape[0] != W:
+            raise DpeError("[BatchCorrManifold] update_subsets: masks must be [M] or [%d, M]" % W)
+        masks = np.ascontiguousarray(masks)
+        M = masks.shape[1]
+        _check(lib().dpe_bcm_update_subsets(self._h, _ptr(CodeScores), _ptr(CarrScores), C.c_int32(W), C.c_int32(K),
+                                            win.ctypes.data_as(C.POINTER(BcmWindow)), chan.ctypes.data_as(C.POINTER(ChanEnd)),
+                                            C.c_int32(M), masks.ctypes.data_as(C.POINTER(C.c_uint64)) if M else None, _stream(stream)))
+        self._W, self._M, self._K = W, M, K
+        keys = C.c_void_p()
+        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
+        self.Keys = keys.value
+        return 0
+
+    @staticmethod
+    def _dict(r):
+        return dict(zVal=np.array(r.zVal), RVal=np.eye(8), offset=np.array(r.offset), posIndex=r.posIndex, velIndex=r.velIndex,
+                    posScore=r.posScore, velScore=r.velScore, posOutOfWindow=r.posOutOfWindow, velOutOfWindow=r.velOutOfWindow)
+
+    def results(self, stream=None):
+        """-> per window a dict: the full set's fix (zVal, offset[8], arg-max, counts), subs = [per subset: the same fields] and
+        oobPerSv int64 [2, K] (position, velocity)."""
+        full = (BcmSubsetResult * self._W)()
+        subs = (BcmSubsetResult * max(self._W * self._M, 1))()
+        oob = np.zeros((self._W, 2, self._K), dtype=np.int64)
+        _check(lib().dpe_bcm_results_subsets(self._h, full, subs if self._M else None, oob.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             _stream(stream)))
+        out = []
+        for w, f in enumerate(full):
+            d = self._dict(f)
+            d["subs"] = [self._dict(r) for r in subs[w * self._M:(w + 1) * self._M]] if self._M else []
+            d["oobPerSv"] = oob[w]
+            out.append(d)
+        return out
+
+    def read_keys(self, stream=None):
+        """The full set's packed keys of the last Update, uint64 [W, 2] (dpe_bcm_keys)."""
+        return d2h(self.Keys, self._W * 2 * 8, np.uint64, stream).reshape(self._W, 2)
 
 
 def bank_rows(bcs, window=0):

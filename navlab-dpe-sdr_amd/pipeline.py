@@ -250,6 +250,86 @@ def run_epoch_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, n_epochs, time
     return np.stack(fixes), results
 
 
+def solution_separation(full, subs, masks, threshold_m, n_chan=None):
+    """Solution separation over the subsets of one window (host fp64).  full / subs[m]: result dicts with `offset` (the ENU-dt
+    position offset in offset[:4], as engine.SubsetManifold.results gives them); masks: uint64 [M], subset m's channels;
+    n_chan: the window's channels.  PASS IT whenever the masks are not the complete leave-one-out list: left out, it is taken
+    as the highest bit any mask holds plus one, which is the channel count only if some mask holds the last channel -- a list
+    without it makes every mask look like an exclusion of the wrong set.
+    Per subset the separation is the Euclidean distance (m) between its position ENU-dt offset and the full set's.  The suspect
+    is the SV whose single exclusion (the mask of every channel but that one) separates most, if that distance exceeds
+    threshold_m; otherwise -1.  Returns (suspect, separations float64 [M])."""
+    masks = [int(m) for m in np.asarray(masks, dtype=np.uint64).reshape(-1)]
+    if len(masks) != len(subs):
+        raise ValueError("solution_separation: %d masks for %d subsets" % (len(masks), len(subs)))
+    threshold_m = float(threshold_m)
+    K = max(m.bit_length() for m in masks) if n_chan is None else int(n_chan)
+    all_sv = (1 << K) - 1
+    p0 = np.asarray(full["offset"], dtype=np.float64)[:4]
+    sep = np.array([np.linalg.norm(np.asarray(r["offset"], dtype=np.float64)[:4] - p0) for r in subs], dtype=np.float64)
+    suspect, worst = -1, threshold_m
+    for m, d in zip(masks, sep):
+        out = all_sv & ~m
+        if m & ~all_sv or out == 0 or out & (out - 1):
+            continue                                  # not a single-SV exclusion
+        if d > worst:                                 # (a tie keeps the lower SV: masks are visited in order)
+            suspect, worst = out.bit_length() - 1, d
+    return suspect, sep
+
+
+def run_fde_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, threshold_m, time_grid=(0.0,), init_delta=(0, 0, 0, 0), K=None, lpower=1,
+                        lag_half_width=None, bin_half_width=None, exclude=True, keep_scores=False):
+    """The closed loop with fault detection and exclusion (engine.SubsetManifold): every window is scanned ONCE with the K
+    leave-one-out masks; solution_separation names a suspect SV or none.  With a suspect the window's fix is the zVal of the
+    subset without that SV, else the full set's.  The channel manager keeps all K channels and back-computes them from the
+    chosen fix; nothing is remembered from one window to the next (exclude=False: suspects are logged, the fix stays the full
+    set's).  init_delta: ECEF / clock offset of the initial state, 4 entries, or 8 with the velocity and drift.
+    Returns fixes [W, 8], suspects int [W], separations [W, K] and the per-window result dicts."""
+    import torch
+    iq_windows = np.ascontiguousarray(iq_windows)
+    W, S2 = iq_windows.shape
+    S = S2 // 2
+    K = len(ho["prn_list"]) if K is None else K
+    nfft = engine.carr_fft_len(S)
+    L, B = bank_half_widths(pos_grid, vel_grid, fs, nfft)
+    L = L if lag_half_width is None else int(lag_half_width)
+    B = B if bin_half_width is None else int(bin_half_width)
+    masks = engine.leave_one_out_masks(K)
+    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_channels=K)
+    bcm = engine.SubsetManifold(fs, S, nfft, pos_grid, vel_grid, K, LPower=lpower, lag_half_width=L, bin_half_width=B, max_channels=K)
+    cm = None
+    try:
+        bcs.Start()
+        bcm.Start()
+        cm = engine.ChanMgr.from_handoff(ho, S / fs, K)
+        x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
+        d0 = np.asarray(init_delta, dtype=np.float64)
+        x[:d0.shape[0]] += d0                                  # 4 entries (position, clock) or all 8 of the state
+        iq_d = torch.from_numpy(iq_windows).to("cuda:0")
+        fixes, suspects, seps, results = np.zeros((W, 8)), np.full(W, -1, dtype=np.int64), np.zeros((W, K)), []
+        for w in range(W):
+            (cm.Start if w == 0 else cm.Update)(x, x, time_grid)
+            cs, ce, bw = cm.outputs()
+            bcs.Update(iq_d[w], cs)
+            bcm.Update(bcs.CodeScores, bcs.CarrScores, bw, ce, masks)
+            r = bcm.results()[0]
+            if keep_scores:
+                ps, vs = bcm.read_scores()
+                r["posScores"], r["velScores"] = ps[0].copy(), vs[0].copy()
+            suspects[w], seps[w] = solution_separation(r, r["subs"], masks, threshold_m, K)
+            r["suspect"] = int(suspects[w])
+            chosen = r["subs"][suspects[w]] if (exclude and suspects[w] >= 0) else r
+            x = chosen["zVal"].copy()
+            fixes[w] = x
+            results.append(r)
+    finally:
+        if cm is not None:
+            cm.Stop()
+        bcm.Stop()
+        bcs.Stop()
+    return fixes, suspects, seps, results
+
+
 def run_vector_tracking(samples, start, fs, n_epochs=None, T=1e-3, N=20, fix=None, Sigma=None, stream=None, **cfg):
     """The vector-tracking loop (engine.VectorTracker, DESIGN.md 7e) over `samples` (int16 interleaved I/Q, numpy or a device tensor;
     n_epochs * N windows of round(T fs) samples from the sample `start` refers to).
