@@ -466,6 +466,54 @@ int dpe_bcm_update_subsets(dpe_bcm *h, const float *codeBank_dev, const float *c
  * [nWindows][2][nChan] (manifold 0 position, 1 velocity). */
 int dpe_bcm_results_subsets(dpe_bcm *h, dpe_bcm_subset_result *full, dpe_bcm_subset_result *subs, int64_t *oobPerSv, dpe_stream_t stream);
 
+/* Coarse-to-fine scan: up to 4 LEVELS of tensor-product grids (dpe_grid_axes), level l >= 1 scored around the point level l-1 peaked at,
+ * per window and per manifold -- resolution and span without scoring every point of one dense grid, and without a round trip to the host:
+ * in a batch every window peaks somewhere else.  A level is one launch behind the previous level's in stream order; its blocks read the
+ * previous level's packed key from device memory, decode it against that level's dims and form the CENTRE, the fp32 point that level scored
+ * at its arg-max (its own centre, 0 at level 0, plus its axis values, each sum rounded once to fp32); level l then scores
+ * x = fl32(cx + axX[ix]), y, z, t likewise.  The expansion about the window centre holds for any |delta| < 3 km, so all levels share one set
+ * of per-(window, SV) coefficients.
+ * Contract: for every window, level and manifold the score row, the key and the out-of-window count are, bit for bit, those of a
+ * dpe_bcm_create_axes handle (weightedMean 0) given that window alone and fp64 axes equal to the fp32 values fl32(c + a_i); the last level's
+ * offset and zVal are that handle's point and zVal.  Level 0 is the plain axes scan of its own axes.
+ * Span: the library imposes none.  A level finds the maximum only if it covers the distance between the previous level's arg-max and the
+ * true peak; along a ridge of the score (up / clock) the coarse arg-max may sit one to two coarse steps from it, so a fine level of +-1
+ * coarse step can miss where +-2 steps does not.  Choose each level's half-span accordingly.
+ * A (window, manifold) none of whose points has a score at some level (a channel with NaN banks) has key 0 there; it is not scanned at any
+ * later level and reports index -1, score 0, count 0 from that level on and NaN offset / zVal; the rest of the batch stands.
+ * cfg: posGrid / velGrid NULL; posGridSize / velGridSize are ignored (every level scans its whole axis product); weightedMean, referencePair
+ * and the grid index offsets must be 0.  Refused, each with a message before anything is launched: nLevels outside 1 .. 4; per level what
+ * dpe_bcm_create_axes refuses (dim < 1, non-finite entries, an index beyond 32 bits, banks that leave no room for the 17 KB score stage);
+ * the SUM over levels of the position corner distances >= 3 km.  The clamp variant of a manifold is chosen from the summed reach of the levels.
+ * On such a handle dpe_bcm_profile (over the whole Update), dpe_bcm_last_split (the LAST level's split) and dpe_bcm_destroy work; refused,
+ * each with a message: dpe_bcm_update / _update_dev / _update_prepared, dpe_bcm_results, dpe_bcm_results_from_keys, dpe_bcm_exchange_keys
+ * (sharding), dpe_bcm_set_graph, dpe_bcm_scores / _scores_pitch / _keys / _export_scores_f64 (use the per-level calls below),
+ * dpe_chm_dev_attach (the device-resident loop), dpe_pipe lanes and the joint, epochs and subsets calls; the calls below are refused on
+ * every other kind of handle.  Out of scope: sharding, dpe_pipe, the device-resident loop and dpe_flow. */
+#define DPE_REFINE_MAX_LEVELS 4
+typedef struct dpe_bcm_refine_result {
+    double zVal[8];                                 /* the window centre moved by offset (BCM_MakePosMeas / MakeVelMeas) */
+    double offset[8];                               /* the fp32 points the LAST level scored at its maxima, widened: ENU-dt, ENU-dt_dot */
+    int64_t posIndex[DPE_REFINE_MAX_LEVELS];        /* first maximum per level, index within that level's grid; -1: not scanned / no score */
+    int64_t velIndex[DPE_REFINE_MAX_LEVELS];
+    float posScore[DPE_REFINE_MAX_LEVELS];
+    float velScore[DPE_REFINE_MAX_LEVELS];
+    int64_t posOutOfWindow[DPE_REFINE_MAX_LEVELS];  /* (point, SV) pairs of the level whose index left a bank */
+    int64_t velOutOfWindow[DPE_REFINE_MAX_LEVELS];
+} dpe_bcm_refine_result;
+/* pos / vel: HOST [nLevels], copied at create. */
+int dpe_bcm_create_refine(const dpe_bcm_config *cfg, int32_t nLevels, const dpe_grid_axes *pos, const dpe_grid_axes *vel, dpe_bcm **out);
+/* Arrays as for dpe_bcm_update.  Asynchronous on `stream`: nLevels launches, nothing read back in between. */
+int dpe_bcm_update_refine(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, int32_t nWindows, int32_t nChan,
+                          const dpe_bcm_window *win_host, const dpe_chan_end *chan_host, dpe_stream_t stream);
+/* Waits for the last refine Update (the only host synchronisation) and copies every level's keys and counts.  results: [nWindows];
+ * entries of levels >= nLevels are -1 / 0.  offset is recomputed from the indices by the device's own fp32 additions. */
+int dpe_bcm_results_refine(dpe_bcm *h, dpe_bcm_refine_result *results, dpe_stream_t stream);
+/* Level `level`'s score rows (writeScores): window w's row at scores + w * pitch, pitch = the level's grid size rounded up to 32 floats. */
+int dpe_bcm_refine_scores(dpe_bcm *h, int32_t level, const float **pos_dev, const float **vel_dev, int64_t *posPitch, int64_t *velPitch);
+/* Level `level`'s packed keys of the LAST Update (the two sets alternate: query after every Update), device uint64 [maxWindows][2]. */
+int dpe_bcm_refine_keys(dpe_bcm *h, int32_t level, const uint64_t **keys_dev);
+
 /* ------------------------------------------------------------------ batches in flight ------ */
 /* Several batches of the path on the device at once -- what the reference gets from SampleBlock's 32-slot ring and reader thread
  * (sampleblock.cu:327-447) and from the side streams of BatchCorrScores / BatchCorrManifold (batchcorrscores.h:60-64,

@@ -424,6 +424,7 @@ __global__ __launch_bounds__(256) void bcm_scan_kernel(BcmParamBlock pb, int inl
 }  // namespace dpe
 
 #include "dpe_bcm_axes.h"
+#include "dpe_bcm_refine.h"
 #include "dpe_bcm_joint.h"
 #include "dpe_bcm_epochs.h"
 #include "dpe_bcm_subsets.h"
@@ -683,6 +684,19 @@ struct dpe_bcm {
     unsigned long long *sub_d = nullptr;    // {masks [W][subMax], subset keys [W][2][subMax], per-SV out-of-window counts [W][2][maxK]}
     unsigned long long *subMaskBase_h = nullptr;   // pinned staging ring of the masks
     std::vector<unsigned long long> sub_h, subMask_h;   // host copies: keys and counts of the last Update; its masks
+    // coarse-to-fine levels, each scanned around the previous arg-max (dpe_bcm_create_refine): the level axes share axes_d
+    bool refine = false;
+    int rfLevels = 0;
+    struct RefineLevel {
+        int dim[2][4];                   // [manifold][axis]
+        std::vector<float> v[2][4];      // the fp32 axis values the device adds to the centre
+        int off[2][4];                   // their float offsets in axes_d
+        long long G[2], pitch[2];
+        float *scores[2];                // [W][pitch] or nullptr
+    } rf[DPE_REFINE_MAX_LEVELS] = {};
+    unsigned long long *rfKeys_d = nullptr;   // [2 sets][{keys [levels][W][2], counts [levels][W][2]}], alternating between Updates
+    float *rfCentre_d = nullptr;              // [levels][W][2][4]: the fp32 centre each level scanned around
+    std::vector<unsigned long long> rfKeys_h; // one set: the last Update's keys and counts (dpe_bcm_results_refine)
     dpe::KernelProfiler prof;  // slot 0: the fused position + velocity scan
     dpe::GraphCache graphs;
 };
@@ -979,6 +993,46 @@ static void allow_big_lds_subsets()
     DPE_SUBSETS_LDS(true, true, false); DPE_SUBSETS_LDS(true, false, false); DPE_SUBSETS_LDS(false, true, false); DPE_SUBSETS_LDS(false, false, false);
     DPE_SUBSETS_LDS(true, true, true); DPE_SUBSETS_LDS(true, false, true); DPE_SUBSETS_LDS(false, true, true); DPE_SUBSETS_LDS(false, false, true);
 #undef DPE_SUBSETS_LDS
+}
+
+// One level of a coarse-to-fine Update (dpe_bcm_update_refine)
+struct RefineLaunch {
+    dpe::RefineSide sp, sv;
+    int level, K, maxK, lp;
+    unsigned long long *keys, *oob;
+    const unsigned long long *prevKeys;
+    float *centres;
+    const float *prevCentres;
+    unsigned long long *clr;
+    int clrN;
+    dim3 grid;
+    size_t lds;
+    hipStream_t st;
+};
+
+template <int LP, bool CP, bool CV>
+static void launch_refine3(const RefineLaunch &a)
+{
+    hipLaunchKernelGGL((dpe::bcm_scan_refine_kernel<LP, CP, CV>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.level, a.K, a.maxK, a.lp, a.keys, a.oob,
+                       a.prevKeys, a.centres, a.prevCentres, a.clr, a.clrN);
+}
+
+static void launch_refine(bool clampP, bool clampV, const RefineLaunch &a)
+{
+#define DPE_REFINE_PICK(CP, CV) do { if (a.lp == 1) launch_refine3<1, CP, CV>(a); else if (a.lp == 2) launch_refine3<2, CP, CV>(a); \
+                                     else launch_refine3<0, CP, CV>(a); } while (0)
+    if (clampP) { if (clampV) DPE_REFINE_PICK(true, true); else DPE_REFINE_PICK(true, false); }
+    else { if (clampV) DPE_REFINE_PICK(false, true); else DPE_REFINE_PICK(false, false); }
+#undef DPE_REFINE_PICK
+}
+
+template <int LP>
+static void allow_big_lds_refine()
+{
+#define DPE_REFINE_LDS(CP, CV) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_refine_kernel<LP, CP, CV>, \
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
+    DPE_REFINE_LDS(true, true); DPE_REFINE_LDS(true, false); DPE_REFINE_LDS(false, true); DPE_REFINE_LDS(false, false);
+#undef DPE_REFINE_LDS
 }
 
 // ---- referencePair mode ---------------------------------------------------------------------
@@ -1473,6 +1527,119 @@ int dpe_bcm_create_axes(const dpe_bcm_config *cfg, const dpe_grid_axes *pos, con
     return dpe_bcm_create_axes_sharing(cfg, pos, vel, nullptr, out);
 }
 
+// Coarse-to-fine levels (dpe_bcm_refine.h): every level's axes in one device block, per-level score rows, two alternating sets of
+// per-level keys and counts, and the fp32 centres the levels hand on.
+int dpe_bcm_create_refine(const dpe_bcm_config *cfg, int32_t nLevels, const dpe_grid_axes *pos, const dpe_grid_axes *vel, dpe_bcm **out)
+{
+    using namespace dpe;
+    DPE_REQUIRE(cfg && pos && vel && out, "[BatchCorrManifold] create_refine: null argument");
+    DPE_REQUIRE(nLevels >= 1 && nLevels <= DPE_REFINE_MAX_LEVELS, "[BatchCorrManifold] create_refine: nLevels %d out of range (1 .. %d levels)", nLevels,
+                DPE_REFINE_MAX_LEVELS);
+    DPE_REQUIRE(!cfg->posGrid && !cfg->velGrid, "[BatchCorrManifold] create_refine: posGrid / velGrid must be NULL (the grids are the levels' axes)");
+    DPE_REQUIRE(!cfg->weightedMean, "[BatchCorrManifold] create_refine: the weighted-mean estimator is not formed per level (weightedMean must be 0)");
+    DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_refine: referencePair is not supported with grid axes (referencePair must be 0)");
+    DPE_REQUIRE(cfg->posGridIndexOffset == 0 && cfg->velGridIndexOffset == 0,
+                "[BatchCorrManifold] create_refine: grid shards are not supported (the index offsets must be 0)");
+    DPE_REQUIRE(cfg->samplesPerWindow > 0 && (cfg->samplesPerWindow % 2) == 0,
+                "[BatchCorrManifold] create_refine: samplesPerWindow must be even and positive");
+    DPE_REQUIRE(cfg->samplingFrequency > 0 && cfg->numFFTPoints > 0, "[BatchCorrManifold] create_refine: bad fs / numFFTPoints");
+    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
+                "[BatchCorrManifold] create_refine: maxWindows/maxChannels out of range");
+    DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1 && cfg->lPower >= 1, "[BatchCorrManifold] create_refine: bad L/B/LPower");
+    const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
+    DPE_REQUIRE((size_t)cfg->maxChannels * (nEntMax * 16 + 32) + (size_t)kAxStageBytes <= 150 * 1024,
+                "[BatchCorrManifold] create_refine: score banks (%zu B) and the score stage (%d B) exceed the LDS (no 12-byte bank entries with grid axes)",
+                (size_t)cfg->maxChannels * nEntMax * 16, kAxStageBytes);
+    // the reach of a chain of levels: a point is a sum of one entry per level, so per-level corner distances and |t| maxima add up
+    double corner[2] = {0, 0}, tmax[2] = {0, 0};
+    for (int l = 0; l < nLevels; ++l) {
+        const dpe_grid_axes *ga[2] = {pos + l, vel + l};
+        for (int m = 0; m < 2; ++m) {
+            const char *name = m ? "velocity" : "position";
+            double mx[4] = {0, 0, 0, 0};
+            int64_t prod = 1;
+            for (int c = 0; c < 4; ++c) {
+                DPE_REQUIRE(ga[m]->dim[c] >= 1 && ga[m]->axis[c], "[BatchCorrManifold] create_refine: level %d %s axis %d: dim %d < 1 or no array", l, name, c,
+                            ga[m]->dim[c]);
+                for (int i = 0; i < ga[m]->dim[c]; ++i) {
+                    const double v = ga[m]->axis[c][i];
+                    DPE_REQUIRE(std::isfinite(v), "[BatchCorrManifold] create_refine: level %d %s axis %d entry %d is not finite", l, name, c, i);
+                    mx[c] = std::max(mx[c], std::fabs(v));
+                }
+                DPE_REQUIRE(prod <= 0xFFFFFFFFll / ga[m]->dim[c], "[BatchCorrManifold] create_refine: level %d %s grid index does not fit 32 bits", l, name);
+                prod *= ga[m]->dim[c];
+            }
+            // every index the scan forms, including those of the lanes that run past the last row, fits 32 bits
+            const int64_t dimT = ga[m]->dim[3];
+            DPE_REQUIRE((prod / dimT + 256) * dimT + kAxT < 0xFFFFFFFFll, "[BatchCorrManifold] create_refine: level %d %s grid index does not fit 32 bits", l,
+                        name);
+            corner[m] += std::sqrt(mx[0] * mx[0] + mx[1] * mx[1] + mx[2] * mx[2]);
+            tmax[m] += mx[3];
+        }
+    }
+    DPE_REQUIRE(corner[0] < 3.0e3, "[BatchCorrManifold] create_refine: the levels' position grids together extend beyond 3 km from the window centre "
+                                   "(sum of the corner distances %.1f m)", corner[0]);
+    dpe_bcm *h = new dpe_bcm();
+    h->cfg = *cfg;
+    h->refine = true;
+    h->rfLevels = nLevels;
+    // (the fp32 roundings of the centres, a few ulp of a kilometre, are inside the slack terms)
+    h->posExtent = (corner[0] + tmax[0]) * 1.000001 + corner[0] * corner[0] / 2.0e7 + 1e-3;
+    h->velExtent = (corner[1] + tmax[1]) * 1.000001 + 1e-6;
+    size_t nf = 0;
+    for (int l = 0; l < nLevels; ++l) {
+        dpe_bcm::RefineLevel &lv = h->rf[l];
+        const dpe_grid_axes *ga[2] = {pos + l, vel + l};
+        for (int m = 0; m < 2; ++m) {
+            lv.G[m] = 1;
+            for (int c = 0; c < 4; ++c) {
+                lv.dim[m][c] = ga[m]->dim[c];
+                lv.v[m][c].resize((size_t)ga[m]->dim[c]);
+                for (int i = 0; i < ga[m]->dim[c]; ++i) lv.v[m][c][(size_t)i] = (float)ga[m]->axis[c][i];
+                lv.off[m][c] = (int)nf;
+                nf += (size_t)ga[m]->dim[c] + (c == 3 ? kAxT : 0);
+                lv.G[m] *= ga[m]->dim[c];
+            }
+            lv.pitch[m] = (lv.G[m] + 31) / 32 * 32;
+        }
+    }
+    dpe_bcm_config c = *cfg;
+    c.writeScores = 0;   // (the rows are per level: allocated below)
+    c.posGridSize = h->rf[nLevels - 1].G[0];
+    c.velGridSize = h->rf[nLevels - 1].G[1];
+    h->cfg.posGridSize = c.posGridSize; h->cfg.velGridSize = c.velGridSize;
+    dpe_bcm *made = nullptr;
+    if (bcm_finish_create(h, &c, &made)) return -1;   // (h is destroyed on failure)
+    const size_t W = cfg->maxWindows;
+    const auto finish = [&]() -> int {
+        std::vector<float> f(nf, 0.f);
+        for (int l = 0; l < nLevels; ++l)
+            for (int m = 0; m < 2; ++m)
+                for (int cc = 0; cc < 4; ++cc) std::copy(h->rf[l].v[m][cc].begin(), h->rf[l].v[m][cc].end(), f.begin() + h->rf[l].off[m][cc]);
+        h->axes_d = dev_alloc<float>(nf);
+        h->rfKeys_d = dev_alloc<unsigned long long>(2 * 4 * W * (size_t)nLevels);
+        h->rfCentre_d = dev_alloc<float>((size_t)nLevels * W * 8);
+        DPE_REQUIRE(h->axes_d && h->rfKeys_d && h->rfCentre_d, "[BatchCorrManifold] create_refine: device allocation failed");
+        for (int l = 0; cfg->writeScores && l < nLevels; ++l)
+            for (int m = 0; m < 2; ++m) {
+                h->rf[l].scores[m] = dev_alloc<float>(W * (size_t)h->rf[l].pitch[m]);
+                DPE_REQUIRE(h->rf[l].scores[m], "[BatchCorrManifold] create_refine: score rows of level %d: device allocation failed", l);
+            }
+        DPE_CHECK_HIP(hipMemcpy(h->axes_d, f.data(), sizeof(float) * nf, hipMemcpyHostToDevice));
+        DPE_CHECK_HIP(hipMemset(h->rfKeys_d, 0, sizeof(unsigned long long) * 2 * 4 * W * (size_t)nLevels));
+        DPE_CHECK_HIP(hipMemset(h->rfCentre_d, 0, sizeof(float) * (size_t)nLevels * W * 8));
+        return 0;
+    };
+    if (finish()) {
+        dpe_bcm_destroy(h);
+        return -1;
+    }
+    h->rfKeys_h.assign(4 * W * (size_t)nLevels, 0ull);
+    allow_big_lds_refine<0>(); allow_big_lds_refine<1>(); allow_big_lds_refine<2>();
+    *out = h;
+    return 0;
+}
+
 int dpe_bcm_destroy(dpe_bcm *h)
 {
     if (!h) return 0;
@@ -1491,6 +1658,8 @@ int dpe_bcm_destroy(dpe_bcm *h)
     (void)hipFree(h->jrx_d); (void)hipFree(h->own_d);
     if (h->subMaskBase_h) (void)hipHostFree(h->subMaskBase_h);
     (void)hipFree(h->sub_d);
+    (void)hipFree(h->rfKeys_d); (void)hipFree(h->rfCentre_d);
+    for (auto &lv : h->rf) { (void)hipFree(lv.scores[0]); (void)hipFree(lv.scores[1]); }
     (void)hipFree(h->refCand_d); (void)hipFree(h->refWhere_d); (void)hipFree(h->refValue_d); (void)hipFree(h->refOld_d);
     for (hipEvent_t e : h->stagingFree)
         if (e) (void)hipEventDestroy(e);
@@ -1559,6 +1728,7 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] Update: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_update_epochs");
     DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] Update: this handle scans SV subsets (dpe_bcm_create_subsets): use dpe_bcm_update_subsets");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] Update: this handle scans coarse-to-fine levels (dpe_bcm_create_refine): use dpe_bcm_update_refine");
     DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] Update: nWindows %d out of range", nWindows);
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     hipStream_t stream = (hipStream_t)stream_;
@@ -1952,6 +2122,97 @@ int dpe_bcm_update_subsets(dpe_bcm *h, const float *codeBank_dev, const float *c
     return 0;
 }
 
+// One launch per level, in stream order; level l >= 1 takes its centre from level l-1's key in device memory (dpe_bcm_refine.h).
+// The coefficients are expanded once and shared by the levels; the clamp variants follow from the summed reach (create_refine).
+int dpe_bcm_update_refine(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, int32_t nWindows, int32_t nChan,
+                          const dpe_bcm_window *win_host, const dpe_chan_end *chan_host, dpe_stream_t stream_)
+{
+    using namespace dpe;
+    DPE_REQUIRE(h && codeBank_dev && carrBank_dev && win_host && chan_host, "[BatchCorrManifold] update_refine: null argument");
+    DPE_REQUIRE(h->refine, "[BatchCorrManifold] update_refine: the handle was not made by dpe_bcm_create_refine");
+    // everything is checked before anything is staged or launched
+    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] update_refine: nWindows %d out of range", nWindows);
+    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] update_refine: nChan %d out of range", nChan);
+    for (int w = 0; w < nWindows; ++w)
+        DPE_REQUIRE(win_host[w].dopplerSign == 1 || win_host[w].dopplerSign == -1, "[BatchCorrManifold] update_refine: dopplerSign must be +/-1");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int maxK = h->cfg.maxChannels, W = h->cfg.maxWindows, nL = h->rfLevels;
+    bool posInside = true, velInside = true;
+    h->lastDev = false;
+    h->slot = (h->slot + 1) % dpe_bcm::kStaging;
+    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
+    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * W * maxK;
+    for (int w = 0; w < nWindows; ++w) {
+        h->win_h[w] = win_host[w];
+        for (int k = 0; k < nChan; ++k)
+            bcm_expand(h, win_host[w], chan_host[(size_t)w * nChan + k], h->sv_h[(size_t)(0 * W + w) * maxK + k], h->sv_h[(size_t)(1 * W + w) * maxK + k],
+                       posInside, velInside);
+    }
+    h->lastW = nWindows;
+    const int use = h->cur ^ 1;
+    const size_t setLen = 4 * (size_t)W * nL;   // {keys [levels][W][2], counts [levels][W][2]}
+    unsigned long long *keys = h->rfKeys_d + (size_t)use * setLen, *oob = keys + 2 * (size_t)W * nL;
+    unsigned long long *other = h->rfKeys_d + (size_t)(use ^ 1) * setLen;
+    upload_params(h->sv_d, h->svBase_hd + (h->sv_h - h->svBase_h), sizeof(BcmSvDev) * 2 * (size_t)W * maxK, stream);
+    DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
+    const int nLag = 2 * h->cfg.lagHalfWidth + 1, nBin = 2 * h->cfg.binHalfWidth + 1;
+    h->pollable = false;
+    h->lastPublished = false;
+    h->prof.begin(0, stream);
+    for (int l = 0; l < nL; ++l) {
+        const dpe_bcm::RefineLevel &lv = h->rf[l];
+        RefineLaunch a{};
+        RefineSide *side[2] = {&a.sp, &a.sv};
+        for (int m = 0; m < 2; ++m) {
+            RefineSide &s = *side[m];
+            const long long dimT = lv.dim[m][3], nRows = lv.G[m] / dimT;
+            s.ax = h->axes_d;
+            s.offX = lv.off[m][0]; s.offY = lv.off[m][1]; s.offZ = lv.off[m][2]; s.offT = lv.off[m][3];
+            s.dimY = lv.dim[m][1]; s.dimZ = lv.dim[m][2]; s.dimT = (int)dimT;
+            s.nChunks = (int)((dimT + kAxT - 1) / kAxT);
+            s.chunk = (int)((dimT + s.nChunks - 1) / s.nChunks);   // chunks of (nearly) equal length, as axes_side
+            s.nRows = (unsigned)nRows; s.G = (unsigned)lv.G[m];
+            if (l > 0) {
+                const dpe_bcm::RefineLevel &pv = h->rf[l - 1];
+                s.pOffX = pv.off[m][0]; s.pOffY = pv.off[m][1]; s.pOffZ = pv.off[m][2]; s.pOffT = pv.off[m][3];
+                s.pDimY = pv.dim[m][1]; s.pDimZ = pv.dim[m][2]; s.pDimT = pv.dim[m][3];
+                s.pG = (unsigned)pv.G[m];
+            } else {
+                s.pDimY = s.pDimZ = s.pDimT = 1;
+            }
+            s.bank = reinterpret_cast<const float2 *>(m ? carrBank_dev : codeBank_dev);
+            s.sv = h->sv_d + (size_t)m * W * maxK;
+            s.scores = lv.scores[m];
+            s.pitch = lv.pitch[m];
+            s.nEnt = m ? nBin : nLag;
+            // scan_split per level from that level's tile count (a tile: 256 rows x one chunk)
+            const long long nTiles = (nRows + 255) / 256 * s.nChunks;
+            h->lastSplit[m] = scan_split(nTiles * kPtsPerBlock, nWindows, h->splitForce);
+            s.split = (int)h->lastSplit[m];
+        }
+        a.level = l; a.K = nChan; a.maxK = maxK; a.lp = h->cfg.lPower;
+        a.keys = keys + (size_t)l * 2 * W; a.oob = oob + (size_t)l * 2 * W;
+        a.prevKeys = l ? keys + (size_t)(l - 1) * 2 * W : nullptr;
+        a.centres = h->rfCentre_d + (size_t)l * W * 8;
+        a.prevCentres = l ? h->rfCentre_d + (size_t)(l - 1) * W * 8 : nullptr;
+        a.clr = other; a.clrN = l == 0 ? (int)setLen : 0;
+        a.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], nWindows, 2);
+        a.lds = (size_t)nChan * (nLag > nBin ? nLag : nBin) * 16 + kAxStageBytes;
+        a.st = stream;
+        launch_refine(!posInside, !velInside, a);
+    }
+    h->prof.end(0, stream);
+    {
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) {
+            dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
+            return -1;
+        }
+    }
+    h->cur = use;
+    return 0;
+}
+
 int dpe_bcm_joint_set_own_keys(dpe_bcm *h, int32_t enable)
 {
     DPE_REQUIRE(h && h->joint, "[BatchCorrManifold] joint_set_own_keys: not a handle of dpe_bcm_create_joint");
@@ -1967,6 +2228,7 @@ int dpe_bcm_update_dev(dpe_bcm *h, const float *codeBank_dev, const float *carrB
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");   // (before the prep kernel: a refusal launches nothing)
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] Update: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_update_epochs");
     DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] Update: this handle scans SV subsets (dpe_bcm_create_subsets): use dpe_bcm_update_subsets");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] Update: this handle scans coarse-to-fine levels (dpe_bcm_create_refine): use dpe_bcm_update_refine");   // (before the prep kernel)
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     DPE_REQUIRE(!h->refPair || (h->cfg.writeScores && !h->cfg.weightedMean),
                 "[BatchCorrManifold] Update: referencePair with the device ports patches the scores on the device: it needs writeScores and no weightedMean "
@@ -1990,6 +2252,7 @@ int dpe_bcm_update_prepared(dpe_bcm *h, const float *codeBank_dev, const float *
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] Update: null argument");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] Update: this handle scans coarse-to-fine levels (dpe_bcm_create_refine): use dpe_bcm_update_refine");
     DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
     // referencePair (batchcorrmanifold.cu:1798-1812): the prepared blocks hold expansion coefficients only, so the fp64 re-evaluation
     // reads the port arrays of the channel manager that wrote them (handed over at dpe_chm_dev_attach) -- the same device-side
@@ -2020,6 +2283,7 @@ int dpe_bcm_hook_get(dpe_bcm *h, dpe_bcm_hook *out)
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] hook: a joint handle (dpe_bcm_create_joint) cannot serve the device-resident loop or a dpe_pipe lane");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] hook: an epochs handle (dpe_bcm_create_epochs) cannot serve the device-resident loop or a dpe_pipe lane");
     DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] hook: a subsets handle (dpe_bcm_create_subsets) cannot serve the device-resident loop or a dpe_pipe lane");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] hook: a refine handle (dpe_bcm_create_refine) cannot serve the device-resident loop or a dpe_pipe lane");
     const size_t W = h->cfg.maxWindows, maxK = h->cfg.maxChannels;
     if (h->axes && !h->posAx64_d) {   // the global axes in fp64 (a few KB): the measurement kernel decodes its index from them
         dpe_bcm::Axes *ax[2] = {&h->posAx, &h->velAx};
@@ -2083,6 +2347,7 @@ int dpe_bcm_set_graph(dpe_bcm *h, int32_t enable)
     DPE_REQUIRE(!h->joint || !enable, "[BatchCorrManifold] set_graph: joint Updates (dpe_bcm_update_joint) always launch eagerly");
     DPE_REQUIRE(!h->epochs || !enable, "[BatchCorrManifold] set_graph: epochs Updates (dpe_bcm_update_epochs) always launch eagerly");
     DPE_REQUIRE(!h->subsets || !enable, "[BatchCorrManifold] set_graph: subsets Updates (dpe_bcm_update_subsets) always launch eagerly");
+    DPE_REQUIRE(!h->refine || !enable, "[BatchCorrManifold] set_graph: refine Updates (dpe_bcm_update_refine) always launch eagerly");
     h->graphs.enabled = enable != 0;
     if (!enable) h->graphs.clear();
     return 0;
@@ -2146,6 +2411,7 @@ int dpe_bcm_results(dpe_bcm *h, dpe_bcm_result *results, dpe_stream_t stream)
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] results: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_results_joint");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] results: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_results_epochs");
     DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] results: this handle scans SV subsets (dpe_bcm_create_subsets): use dpe_bcm_results_subsets");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] results: this handle scans coarse-to-fine levels (dpe_bcm_create_refine): use dpe_bcm_results_refine");
     // Single-window Updates: the scan's last block writes a sequence word right behind the results in the pinned
     // mirror.  Polling it returns the fix as soon as it lands, without the stream-wait wake-up (a few us of a ~58 us
     // closed-loop window); anything unexpected falls back to the stream wait.
@@ -2319,6 +2585,71 @@ int dpe_bcm_results_subsets(dpe_bcm *h, dpe_bcm_subset_result *full, dpe_bcm_sub
     return 0;
 }
 
+int dpe_bcm_results_refine(dpe_bcm *h, dpe_bcm_refine_result *results, dpe_stream_t stream)
+{
+    DPE_REQUIRE(h && results, "[BatchCorrManifold] results_refine: null argument");
+    DPE_REQUIRE(h->refine, "[BatchCorrManifold] results_refine: the handle was not made by dpe_bcm_create_refine");
+    DPE_REQUIRE(h->lastW > 0, "[BatchCorrManifold] results_refine: no refine update yet");
+    DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    const int W = h->lastW, nL = h->rfLevels;
+    const size_t Wm = h->cfg.maxWindows, setLen = 4 * Wm * nL;
+    DPE_CHECK_HIP(hipMemcpy(h->rfKeys_h.data(), h->rfKeys_d + (size_t)h->cur * setLen, sizeof(unsigned long long) * setLen, hipMemcpyDeviceToHost));
+    const unsigned long long *keys = h->rfKeys_h.data(), *oob = keys + 2 * Wm * nL;
+    for (int w = 0; w < W; ++w) {
+        dpe_bcm_refine_result &r = results[w];
+        double pt[2][4];
+        for (int m = 0; m < 2; ++m) {
+            int64_t *index = m ? r.velIndex : r.posIndex, *count = m ? r.velOutOfWindow : r.posOutOfWindow;
+            float *score = m ? r.velScore : r.posScore;
+            float c[4] = {0.f, 0.f, 0.f, 0.f};   // the centre chain, with the device's own fp32 additions
+            bool alive = true;
+            for (int l = 0; l < DPE_REFINE_MAX_LEVELS; ++l) {
+                index[l] = -1; score[l] = 0.f; count[l] = 0;
+                if (l >= nL) continue;
+                const unsigned long long key = keys[((size_t)l * Wm + w) * 2 + m];
+                if (!key) alive = false;   // no point scored here: this and every later level were not scanned
+                if (!alive) continue;
+                decode_key(key, &score[l], &index[l]);
+                count[l] = (int64_t)oob[((size_t)l * Wm + w) * 2 + m];
+                const dpe_bcm::RefineLevel &lv = h->rf[l];
+                DPE_REQUIRE(index[l] >= 0 && index[l] < lv.G[m], "[BatchCorrManifold] results_refine: arg-max index outside level %d's grid", l);
+                int64_t rest = index[l];
+                for (int a = 3; a >= 0; --a) {
+                    c[a] = c[a] + lv.v[m][a][(size_t)(rest % lv.dim[m][a])];   // fp32: rounded once, as on the device
+                    rest /= lv.dim[m][a];
+                }
+            }
+            for (int a = 0; a < 4; ++a) pt[m][a] = alive ? (double)c[a] : (double)NAN;
+        }
+        for (int a = 0; a < 4; ++a) { r.offset[a] = pt[0][a]; r.offset[4 + a] = pt[1][a]; }
+        make_meas(h->win_h[w], pt[0], pt[1], r.zVal);
+    }
+    return 0;
+}
+
+int dpe_bcm_refine_scores(dpe_bcm *h, int32_t level, const float **pos_dev, const float **vel_dev, int64_t *posPitch, int64_t *velPitch)
+{
+    DPE_REQUIRE(h, "[BatchCorrManifold] refine_scores: null handle");
+    DPE_REQUIRE(h->refine, "[BatchCorrManifold] refine_scores: the handle was not made by dpe_bcm_create_refine");
+    DPE_REQUIRE(level >= 0 && level < h->rfLevels, "[BatchCorrManifold] refine_scores: level %d out of range (the handle holds %d levels)", level, h->rfLevels);
+    DPE_REQUIRE(h->cfg.writeScores, "[BatchCorrManifold] refine_scores: created with writeScores=0");
+    if (pos_dev) *pos_dev = h->rf[level].scores[0];
+    if (vel_dev) *vel_dev = h->rf[level].scores[1];
+    if (posPitch) *posPitch = h->rf[level].pitch[0];
+    if (velPitch) *velPitch = h->rf[level].pitch[1];
+    return 0;
+}
+
+int dpe_bcm_refine_keys(dpe_bcm *h, int32_t level, const uint64_t **keys_dev)
+{
+    DPE_REQUIRE(h && keys_dev, "[BatchCorrManifold] refine_keys: null argument");
+    DPE_REQUIRE(h->refine, "[BatchCorrManifold] refine_keys: the handle was not made by dpe_bcm_create_refine");
+    DPE_REQUIRE(level >= 0 && level < h->rfLevels, "[BatchCorrManifold] refine_keys: level %d out of range (the handle holds %d levels)", level, h->rfLevels);
+    const size_t W = h->cfg.maxWindows;
+    *keys_dev = reinterpret_cast<const uint64_t *>(h->rfKeys_d + (size_t)h->cur * 4 * W * h->rfLevels + (size_t)level * 2 * W);
+    return 0;
+}
+
 int dpe_bcm_profile(dpe_bcm *h, int32_t enable, float *ms, int32_t *count)
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] profile: null handle");
@@ -2336,6 +2667,7 @@ int dpe_bcm_profile(dpe_bcm *h, int32_t enable, float *ms, int32_t *count)
 int dpe_bcm_scores(dpe_bcm *h, const float **posScores_dev, const float **velScores_dev)
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] scores: null handle");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] scores: a refine handle (dpe_bcm_create_refine) keeps rows per level: use dpe_bcm_refine_scores");
     DPE_REQUIRE(h->cfg.writeScores, "[BatchCorrManifold] scores: created with writeScores=0");
     if (posScores_dev) *posScores_dev = h->posScores_d;
     if (velScores_dev) *velScores_dev = h->velScores_d;
@@ -2345,6 +2677,7 @@ int dpe_bcm_scores(dpe_bcm *h, const float **posScores_dev, const float **velSco
 int dpe_bcm_export_scores_f64(dpe_bcm *h, int32_t window, double *posScores_dev, double *velScores_dev, dpe_stream_t stream)
 {
     DPE_REQUIRE(h && h->cfg.writeScores, "[BatchCorrManifold] export_scores_f64: created with writeScores=0");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] export_scores_f64: a refine handle (dpe_bcm_create_refine) keeps rows per level: use dpe_bcm_refine_scores");
     DPE_REQUIRE(window >= 0 && window < h->lastW, "[BatchCorrManifold] export_scores_f64: bad window %d", window);
     const long long Gp = h->cfg.posGridSize, Gv = h->cfg.velGridSize;
     if (posScores_dev)
@@ -2360,6 +2693,7 @@ int dpe_bcm_export_scores_f64(dpe_bcm *h, int32_t window, double *posScores_dev,
 int dpe_bcm_scores_pitch(dpe_bcm *h, int64_t *posPitch, int64_t *velPitch)
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] scores_pitch: null handle");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] scores_pitch: a refine handle (dpe_bcm_create_refine) keeps rows per level: use dpe_bcm_refine_scores");
     if (posPitch) *posPitch = h->posPitch;
     if (velPitch) *velPitch = h->velPitch;
     return 0;
@@ -2368,6 +2702,7 @@ int dpe_bcm_scores_pitch(dpe_bcm *h, int64_t *posPitch, int64_t *velPitch)
 int dpe_bcm_keys(dpe_bcm *h, const uint64_t **keys_dev)
 {
     DPE_REQUIRE(h && keys_dev, "[BatchCorrManifold] keys: null argument");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] keys: a refine handle (dpe_bcm_create_refine) keeps keys per level: use dpe_bcm_refine_keys");
     *keys_dev = reinterpret_cast<const uint64_t *>(h->keys_d + (size_t)h->cur * 4 * h->cfg.maxWindows);
     return 0;
 }
@@ -2387,6 +2722,7 @@ int dpe_bcm_exchange_keys(dpe_bcm *h, dpe_comm *c, uint64_t *keys_host, dpe_stre
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] exchange_keys: a joint handle (dpe_bcm_create_joint) scans whole grids: sharding is not supported");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] exchange_keys: an epochs handle (dpe_bcm_create_epochs) scans whole grids: sharding is not supported");
     DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] exchange_keys: a subsets handle (dpe_bcm_create_subsets) scans whole grids: sharding is not supported");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] exchange_keys: a refine handle (dpe_bcm_create_refine) scans whole grids: sharding is not supported");
     unsigned long long *keys = h->keys_d + (size_t)h->cur * 4 * h->cfg.maxWindows;
     if (dpe_comm_allreduce_max_u64(c, reinterpret_cast<uint64_t *>(keys), 2 * (int64_t)h->lastW, stream)) return -1;
     if (keys_host) {
@@ -2406,6 +2742,7 @@ int dpe_bcm_results_from_keys(dpe_bcm *h, const uint64_t *keys_host, int32_t nWi
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] results_from_keys: a joint handle (dpe_bcm_create_joint) scans whole grids: use dpe_bcm_results_joint");
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] results_from_keys: an epochs handle (dpe_bcm_create_epochs) scans whole grids: use dpe_bcm_results_epochs");
     DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] results_from_keys: a subsets handle (dpe_bcm_create_subsets) scans whole grids: use dpe_bcm_results_subsets");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] results_from_keys: a refine handle (dpe_bcm_create_refine) scans whole grids: use dpe_bcm_results_refine");
     if (!posGridGlobal) {   // an axes handle decodes from its axes, which are the global ones
         posGridGlobalSize = axes_size(h->posAx);
         velGridGlobalSize = axes_size(h->velAx);

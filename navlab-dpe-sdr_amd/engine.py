@@ -40,6 +40,7 @@ EXPORTS = [
     "dpe_bcm_create_joint", "dpe_bcm_update_joint", "dpe_bcm_results_joint", "dpe_bcm_joint_set_own_keys",
     "dpe_bcm_create_epochs", "dpe_bcm_update_epochs", "dpe_bcm_results_epochs", "dpe_bcm_last_split",
     "dpe_bcm_create_subsets", "dpe_bcm_update_subsets", "dpe_bcm_results_subsets",
+    "dpe_bcm_create_refine", "dpe_bcm_update_refine", "dpe_bcm_results_refine", "dpe_bcm_refine_scores", "dpe_bcm_refine_keys",
     "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
     "dpe_vt_create", "dpe_vt_destroy", "dpe_vt_set_ephemerides", "dpe_vt_init", "dpe_vt_init_from_trk", "dpe_vt_track", "dpe_vt_read_log",
     "dpe_vt_read_corr", "dpe_vt_state", "dpe_vt_dev_status", "dpe_vt_filter_step_host",
@@ -124,6 +125,16 @@ class BcmEpochsResult(C.Structure):  # dpe_bcm_epochs_result
 class BcmSubsetResult(C.Structure):  # dpe_bcm_subset_result
     _fields_ = [("zVal", C.c_double * 8), ("offset", C.c_double * 8), ("posIndex", C.c_int64), ("velIndex", C.c_int64),
                 ("posScore", C.c_float), ("velScore", C.c_float), ("posOutOfWindow", C.c_int64), ("velOutOfWindow", C.c_int64)]
+
+
+REFINE_MAX_LEVELS = 4    # DPE_REFINE_MAX_LEVELS
+
+
+class BcmRefineResult(C.Structure):  # dpe_bcm_refine_result
+    _fields_ = [("zVal", C.c_double * 8), ("offset", C.c_double * 8), ("posIndex", C.c_int64 * REFINE_MAX_LEVELS),
+                ("velIndex", C.c_int64 * REFINE_MAX_LEVELS), ("posScore", C.c_float * REFINE_MAX_LEVELS),
+                ("velScore", C.c_float * REFINE_MAX_LEVELS), ("posOutOfWindow", C.c_int64 * REFINE_MAX_LEVELS),
+                ("velOutOfWindow", C.c_int64 * REFINE_MAX_LEVELS)]
 
 
 CHAN_START_DTYPE = np.dtype([("codePhaseStart", "<f8"), ("carrierPhaseStart", "<f8"), ("codeFrequency", "<f8"),
@@ -873,6 +884,110 @@ class SubsetManifold(BatchCorrManifold):
     def read_keys(self, stream=None):
         """The full set's packed keys of the last Update, uint64 [W, 2] (dpe_bcm_keys)."""
         return d2h(self.Keys, self._W * 2 * 8, np.uint64, stream).reshape(self._W, 2)
+
+
+class RefineManifold:
+    """Coarse-to-fine scan (dpe_bcm_create_refine): levels = [(GridAxes pos, GridAxes vel), ...], level l >= 1 scored around the
+    fp32 point level l - 1 peaked at, per window and manifold, one launch per level and nothing read back in between.  Every
+    level's rows, keys and counts carry the bits of an axes handle on the fp32 values centre + axis.  The span
+    of a level is the caller's choice: it has to cover the distance between the previous level's arg-max and the true peak."""
+
+    def __init__(self, SamplingFrequency, samples_per_window, NumFFTPoints, levels, LPower=1, lag_half_width=8, bin_half_width=48,
+                 max_windows=1, max_channels=8, write_scores=True):
+        from .grid_axes import GridAxes
+        self.fs, self.S, self.C = float(SamplingFrequency), int(samples_per_window), int(NumFFTPoints)
+        self.levels = [tuple(lv) for lv in levels]
+        for lv in self.levels:
+            if len(lv) != 2 or not all(isinstance(a, GridAxes) and a.size == a.global_size for a in lv):
+                raise DpeError("[BatchCorrManifold] create_refine: every level is a pair of whole GridAxes (position, velocity)")
+        self.LPower, self.L, self.B = int(LPower), int(lag_half_width), int(bin_half_width)
+        self.max_windows, self.max_channels = int(max_windows), int(max_channels)
+        self.write_scores = bool(write_scores)
+        self._h = C.c_void_p(None)
+        self.Started = False
+        self._W = 0
+
+    def Start(self):
+        if self.Started:
+            return 0
+        from .grid_axes import GridAxesC
+        n = len(self.levels)
+        cfg = BcmConfig(self.S, self.L, self.B, self.LPower, self.max_windows, self.max_channels, self.C, self.fs, None, None,
+                        0, 0, 0, 0, 1 if self.write_scores else 0, 0, 0, 0)
+        pa, va = (GridAxesC * max(n, 1))(), (GridAxesC * max(n, 1))()
+        for i, (p, v) in enumerate(self.levels):
+            pa[i], va[i] = p.c_struct(), v.c_struct()
+        _check(lib().dpe_bcm_create_refine(C.byref(cfg), C.c_int32(n), pa, va, C.byref(self._h)))
+        self.Started = True
+        return 0
+
+    def Update(self, CodeScores, CarrScores, win, chan, stream=None):
+        """win: BCM_WINDOW_DTYPE [W]; chan: CHAN_END_DTYPE [W, K]; banks: device pointers from BatchCorrScores."""
+        if not self.Started:
+            raise DpeError("[BatchCorrManifold] Error: Update() Failed due to module not initialized")
+        win = np.ascontiguousarray(np.atleast_1d(win))
+        chan = np.ascontiguousarray(chan)
+        if chan.ndim == 1:
+            chan = chan[None, :]
+        W, K = chan.shape
+        assert win.shape[0] == W
+        _check(lib().dpe_bcm_update_refine(self._h, _ptr(CodeScores), _ptr(CarrScores), C.c_int32(W), C.c_int32(K),
+                                           win.ctypes.data_as(C.POINTER(BcmWindow)), chan.ctypes.data_as(C.POINTER(ChanEnd)),
+                                           _stream(stream)))
+        self._W = W
+        return 0
+
+    def results(self, stream=None):
+        """-> per window a dict: zVal, offset[8] (the fp32 points of the last level's maxima) and, per level, posIndex / velIndex
+        (-1: not scanned), posScore / velScore, posOutOfWindow / velOutOfWindow as arrays [levels]."""
+        res = (BcmRefineResult * self._W)()
+        _check(lib().dpe_bcm_results_refine(self._h, res, _stream(stream)))
+        n = len(self.levels)
+        return [dict(zVal=np.array(r.zVal), RVal=np.eye(8), offset=np.array(r.offset),
+                     posIndex=np.array(r.posIndex[:n], dtype=np.int64), velIndex=np.array(r.velIndex[:n], dtype=np.int64),
+                     posScore=np.array(r.posScore[:n], dtype=np.float32), velScore=np.array(r.velScore[:n], dtype=np.float32),
+                     posOutOfWindow=np.array(r.posOutOfWindow[:n], dtype=np.int64),
+                     velOutOfWindow=np.array(r.velOutOfWindow[:n], dtype=np.int64)) for r in res]
+
+    def read_scores(self, level, stream=None):
+        """Level `level`'s position and velocity rows of the last Update, float32 [W, G_level] each."""
+        ps, vs, pp, vp = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
+        _check(lib().dpe_bcm_refine_scores(self._h, C.c_int32(level), C.byref(ps), C.byref(vs), C.byref(pp), C.byref(vp)))
+        Gp, Gv = (a.global_size for a in self.levels[level])
+        p = d2h(ps.value, self._W * pp.value * 4, np.float32, stream).reshape(self._W, pp.value)[:, :Gp]
+        v = d2h(vs.value, self._W * vp.value * 4, np.float32, stream).reshape(self._W, vp.value)[:, :Gv]
+        return np.ascontiguousarray(p), np.ascontiguousarray(v)
+
+    def read_keys(self, level, stream=None, all_windows=False):
+        """Level `level`'s packed keys of the last Update, uint64 [W, 2]; all_windows: the whole set, [max_windows, 2]."""
+        keys = C.c_void_p()
+        _check(lib().dpe_bcm_refine_keys(self._h, C.c_int32(level), C.byref(keys)))
+        n = self.max_windows if all_windows else self._W
+        return d2h(keys.value, n * 2 * 8, np.uint64, stream).reshape(n, 2)
+
+    def last_split(self):
+        """(position, velocity) blocks per window of the LAST level's launch (dpe_bcm_last_split)."""
+        split = (C.c_int32 * 2)()
+        _check(lib().dpe_bcm_last_split(self._h, split))
+        return (int(split[0]), int(split[1]))
+
+    def profile(self, enable=True):
+        ms, cnt = (C.c_float * 2)(), (C.c_int32 * 2)()
+        _check(lib().dpe_bcm_profile(self._h, C.c_int32(1 if enable else 0), ms, cnt))
+        return {"bcm_scan": (ms[0], cnt[0])}   # the levels' launches of an Update together
+
+    def Stop(self):
+        if self.Started:
+            _check(lib().dpe_bcm_destroy(self._h))
+            self._h = C.c_void_p(None)
+            self.Started = False
+        return 0
+
+    def __del__(self):
+        try:
+            self.Stop()
+        except Exception:
+            pass
 
 
 def bank_rows(bcs, window=0):

@@ -15,6 +15,17 @@ def bank_half_widths(pos_grid, vel_grid, fs, nfft):
     return L, B
 
 
+def bank_half_widths_refine(levels, fs, nfft):
+    """Bank half-widths for a chain of refine levels (engine.RefineManifold): levels = [(GridAxes pos, GridAxes vel), ...].  A
+    scored point is a sum of one axis entry per level, so the extent is the sum over levels of each level's corner distance
+    and largest |delta_t| -- the rule of bank_half_widths on the summed extents."""
+    ep = sum(np.sqrt(sum(np.abs(a).max() ** 2 for a in p.axes[:3])) + np.abs(p.axes[3]).max() for p, _ in levels)
+    ev = sum(np.sqrt(sum(np.abs(a).max() ** 2 for a in v.axes[:3])) + np.abs(v.axes[3]).max() for _, v in levels)
+    L = int(np.ceil(ep * fs / 299792458.0)) + 2
+    B = int(np.ceil(ev * (nfft / fs) * 1.57542e9 / 299792458.0)) + 3
+    return L, B
+
+
 def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), init_delta=(0, 0, 0, 0), K=None,
                     lpower=1, enable_ekf=False, reference_pair=False, keep_scores=False, couple_velocity=True):
     """iq_windows: int16 [W, 2S] (host).  Returns fixes [W, 8] (= xCurrk1k1 per window) and the raw
@@ -248,6 +259,57 @@ def run_epoch_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, n_epochs, time
         bcm.Stop()
         bcs.Stop()
     return np.stack(fixes), results
+
+
+def run_refine_closed_loop(iq_windows, ho, fs, levels, time_grid=(0.0,), init_delta=(0, 0, 0, 0), K=None, lpower=1,
+                           lag_half_width=None, bin_half_width=None, keep_scores=False, keep_banks=False):
+    """run_closed_loop with the coarse-to-fine scan (engine.RefineManifold) in place of the one-grid scan: one Update of all
+    levels per window, the last level's fix (the window centre moved by the refined offset) fed back to the channel manager
+    through the pass-through filter.  levels = [(GridAxes pos, GridAxes vel), ...]; their spans are the caller's choice
+    (DESIGN.md 2.4g).  keep_scores: every result dict carries posScores / velScores, lists of the levels' rows; keep_banks: also
+    the window's codeBank / carrBank [K, 2L+1] / [K, 2B+1] complex64 and `inputs` = the channel manager's outputs it was scored with.
+    Returns fixes [W, 8] and the per-window result dicts."""
+    import torch
+    iq_windows = np.ascontiguousarray(iq_windows)
+    W, S2 = iq_windows.shape
+    S = S2 // 2
+    K = len(ho["prn_list"]) if K is None else K
+    nfft = engine.carr_fft_len(S)
+    L, B = bank_half_widths_refine(levels, fs, nfft)
+    L = L if lag_half_width is None else int(lag_half_width)
+    B = B if bin_half_width is None else int(bin_half_width)
+    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_channels=K)
+    bcm = engine.RefineManifold(fs, S, nfft, levels, LPower=lpower, lag_half_width=L, bin_half_width=B, max_channels=K)
+    cm = None
+    try:
+        bcs.Start()
+        bcm.Start()
+        cm = engine.ChanMgr.from_handoff(ho, S / fs, K)
+        x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
+        x[:4] += np.asarray(init_delta, dtype=np.float64)
+        iq_d = torch.from_numpy(iq_windows).to("cuda:0")
+        fixes, results = np.zeros((W, 8)), []
+        for w in range(W):
+            (cm.Start if w == 0 else cm.Update)(x, x, time_grid)
+            cs, ce, bw = cm.outputs()
+            bcs.Update(iq_d[w], cs)
+            bcm.Update(bcs.CodeScores, bcs.CarrScores, bw, ce)
+            r = bcm.results()[0]
+            if keep_scores:
+                rows = [bcm.read_scores(l) for l in range(len(levels))]
+                r["posScores"], r["velScores"] = [p[0].copy() for p, _ in rows], [v[0].copy() for _, v in rows]
+            if keep_banks:
+                code, carr = bcs.read_banks()
+                r["codeBank"], r["carrBank"], r["inputs"] = code[0].copy(), carr[0].copy(), (cs, ce, bw)
+            x = r["zVal"].copy()
+            fixes[w] = x
+            results.append(r)
+    finally:
+        if cm is not None:
+            cm.Stop()
+        bcm.Stop()
+        bcs.Stop()
+    return fixes, results
 
 
 def solution_separation(full, subs, masks, threshold_m, n_chan=None):
