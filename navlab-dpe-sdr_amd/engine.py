@@ -1155,10 +1155,11 @@ class ChanMgr:
         _check(lib().dpe_chm_create(C.byref(cfg), init.ctypes.data_as(C.c_void_p), C.byref(self._h)))
 
     @classmethod
-    def from_handoff(cls, ho, T, K=None):
+    def from_handoff(cls, ho, T, K=None, DopplerSign=1):
+        """The handoff carries no sign of the front end's spectrum: the caller states it (fi is then the -1 receiver's own)."""
         sl = slice(0, K)
         return cls(ho["prn_list"][sl], ho["rc"][sl], ho["ri"][sl], ho["fc"][sl], ho["fi"][sl], ho["cp"][sl],
-                   ho["cp_timestamp"][sl], ho["TOW"][sl], ho["eph"][sl], ho["rxTime"], T)
+                   ho["cp_timestamp"][sl], ho["TOW"][sl], ho["eph"][sl], ho["rxTime"], T, DopplerSign=DopplerSign)
 
     def _step(self, fn, x_k1k1, x_kk1, time_grid):
         a = np.ascontiguousarray(x_k1k1, dtype=np.float64)
@@ -1225,10 +1226,10 @@ class ChanMgrDev:
                                         C.c_int32(tg.size), C.byref(self._h)))
 
     @classmethod
-    def from_handoff(cls, ho, T, K=None, time_grid=(0.0,)):
+    def from_handoff(cls, ho, T, K=None, time_grid=(0.0,), DopplerSign=1):
         sl = slice(0, K)
         return cls(ho["prn_list"][sl], ho["rc"][sl], ho["ri"][sl], ho["fc"][sl], ho["fi"][sl], ho["cp"][sl],
-                   ho["cp_timestamp"][sl], ho["TOW"][sl], ho["eph"][sl], ho["rxTime"], T, time_grid)
+                   ho["cp_timestamp"][sl], ho["TOW"][sl], ho["eph"][sl], ho["rxTime"], T, time_grid, DopplerSign=DopplerSign)
 
     def attach(self, bcs=None, bcm=None, ring_depth=64):
         _check(lib().dpe_chm_dev_attach(self._h, bcs._h if bcs is not None else None, bcm._h if bcm is not None else None,

@@ -27,12 +27,13 @@ def bank_half_widths_refine(levels, fs, nfft):
 
 
 def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), init_delta=(0, 0, 0, 0), K=None,
-                    lpower=1, enable_ekf=False, reference_pair=False, keep_scores=False, couple_velocity=True):
+                    lpower=1, enable_ekf=False, reference_pair=False, keep_scores=False, couple_velocity=True, doppler_sign=1):
     """iq_windows: int16 [W, 2S] (host).  Returns fixes [W, 8] (= xCurrk1k1 per window) and the raw
     per-window result dicts.  One window per Update, fix fed back to the channel manager.
     enable_ekf: route the fix through cuEKF's real filter (EnableEKF=true) instead of the shipped pass-through.
     reference_pair: dpe_bcm_config.referencePair; keep_scores: every result dict also carries the window's position and velocity scores;
-    couple_velocity: the filter's F couples position and velocity over one window (cuekf.cu:111-143) or is the identity (ekf.py:47)."""
+    couple_velocity: the filter's F couples position and velocity over one window (cuekf.cu:111-143) or is the identity (ekf.py:47).
+    doppler_sign: the channel manager's DopplerSign (+1 / -1); the handoff's fi is the front end's own, the handoff names no sign."""
     import torch
     iq_windows = np.ascontiguousarray(iq_windows)
     W, S2 = iq_windows.shape
@@ -45,7 +46,7 @@ def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
     bcm = engine.BatchCorrManifold(fs, S, bcs.NumFFTPoints, pos_grid, vel_grid, LPower=lpower, lag_half_width=L,
                                    bin_half_width=B, max_channels=K, reference_pair=reference_pair)
     bcm.Start()
-    cm = engine.ChanMgr.from_handoff(ho, S / fs, K)
+    cm = engine.ChanMgr.from_handoff(ho, S / fs, K, DopplerSign=doppler_sign)
     x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
     x[:4] += np.asarray(init_delta, dtype=np.float64)
     iq_d = torch.from_numpy(iq_windows).to("cuda:0")
@@ -73,7 +74,8 @@ def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
 
 
 def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), init_delta=(0, 0, 0, 0), K=None, lpower=1,
-                    ring_depth=64, stream=None, reference_pair=False, keep_scores=False, enable_ekf=False, couple_velocity=True):
+                    ring_depth=64, stream=None, reference_pair=False, keep_scores=False, enable_ekf=False, couple_velocity=True,
+                    doppler_sign=1):
     """The same loop with nothing read back per window: the channel manager lives on the device (engine.ChanMgrDev), forms
     the measurement from the scan's keys, passes it through and writes the next window's parameter blocks; the host enqueues
         BatchCorrScores.UpdatePrepared -> BatchCorrManifold.UpdatePrepared -> ChanMgrDev.step
@@ -81,7 +83,8 @@ def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
     reference_pair: dpe_bcm_config.referencePair (the prepared form re-evaluates from the attached manager's port arrays);
     keep_scores (tests): waits for every window and keeps its position and velocity scores, its code banks and the channel manager's outputs the
     window was scored with (`inputs` = ChanMgrDev.outputs() before the window) -- the loop then does read back.
-    enable_ekf: cuEKF's filter inside the measurement kernel (dpe_chm_dev_set_ekf) instead of the pass-through; the fixes are then x_k|k."""
+    enable_ekf: cuEKF's filter inside the measurement kernel (dpe_chm_dev_set_ekf) instead of the pass-through; the fixes are then x_k|k.
+    doppler_sign: the channel manager's DopplerSign, as in run_closed_loop."""
     import torch
     iq_windows = np.ascontiguousarray(iq_windows)
     W, S2 = iq_windows.shape
@@ -94,7 +97,7 @@ def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
     bcm = engine.BatchCorrManifold(fs, S, bcs.NumFFTPoints, pos_grid, vel_grid, LPower=lpower, lag_half_width=L,
                                    bin_half_width=B, max_channels=K, reference_pair=reference_pair)
     bcm.Start()
-    cm = engine.ChanMgrDev.from_handoff(ho, S / fs, K, time_grid)
+    cm = engine.ChanMgrDev.from_handoff(ho, S / fs, K, time_grid, DopplerSign=doppler_sign)
     cm.attach(bcs, bcm, ring_depth)
     x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
     x[:4] += np.asarray(init_delta, dtype=np.float64)

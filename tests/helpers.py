@@ -16,16 +16,21 @@ def _oracle():
 
 
 def make_case(seed=0, fs=2.5e6, S=50000, K=8, G=4096, amp=200.0, W=1, grid="rand", vel_G=None,
-              center_offset=None, flips=None):
+              center_offset=None, flips=None, ds=1):
     """W consecutive windows on the handoff geometry (static receiver), channel state advanced by
-    the oracle's cuChanMgr restatement; I/Q synthesised from each window's start-referenced params."""
+    the oracle's cuChanMgr restatement; I/Q synthesised from each window's start-referenced params.
+    ds = -1: the same geometry seen by a front end whose spectrum runs the other way (DopplerSign -1): the handoff's fi negated,
+    the channel manager, the velocity manifold and BatchCorrManifold's window told so."""
     o = _oracle()
     ho = dpe.workload.extend_handoff(dpe.handoff.read_handoff(HANDOFF), K)   # K > 8: synthetic extra SVs
     T = S / fs
     X = ho["X_ECEF"].copy()
     sl = slice(0, K)
+    assert ds in (1, -1)
+    if ds == -1:
+        ho = dict(ho, fi=-ho["fi"])
     cm = o.ChanMgr(ho["prn_list"][sl], ho["rc"][sl], ho["ri"][sl], ho["fc"][sl], ho["fi"][sl], ho["cp"][sl],
-                   ho["cp_timestamp"][sl], ho["TOW"][sl], ho["eph"][sl], ho["rxTime"], T)
+                   ho["cp_timestamp"][sl], ho["TOW"][sl], ho["eph"][sl], ho["rxTime"], T, doppler_sign=ds)
     if grid == "rand":
         pos = dpe.synth.rand_grid(seed + 100, G)
         vel = dpe.synth.rand_grid(seed + 200, vel_G or G, half=(6.0, 6.0, 6.0, 3.0))
@@ -56,7 +61,7 @@ def make_case(seed=0, fs=2.5e6, S=50000, K=8, G=4096, amp=200.0, W=1, grid="rand
                          cpRefTOW=cm.cpRefTOW.copy(), fc=cm.fc.copy(), fi=cm.fi.copy(), centre=centre.copy(),
                          flip=fl))
     return dict(fs=fs, S=S, K=K, W=W, C=dpe.engine.carr_fft_len(S), pos=pos, vel=vel, wins=wins,
-                prn=np.asarray(cm.prns))
+                prn=np.asarray(cm.prns), ds=ds)
 
 
 def run_oracle(case, L, B, lpower=1, windows=None):
@@ -81,7 +86,7 @@ def run_oracle(case, L, B, lpower=1, windows=None):
         spx, oobx = o.bcm_pos(w["sat"], code, S // 2 - L, w["centre"], case["pos"], w["R"], w["fc"], w["cpRefTOW"],
                            w["cpElaEnd"], w["cpRef"], w["rcEnd"], w["rxTime"], fs, S, lpower, extended=True)
         sv, oobv = o.bcm_vel(w["sat"], carr, C // 2 - B, w["centre"], case["vel"], w["R"], w["fi"], w["rxTime"], fs,
-                             C, 1, lpower)
+                             C, case.get("ds", 1), lpower)
         ip, iv = o.argmax_first(sp), o.argmax_first(sv)
         z, _ = o.make_meas(ip, iv, w["centre"], case["pos"], case["vel"], w["R"])
         out["code"].append(code)
@@ -106,7 +111,8 @@ def pack_gpu_inputs(case):
                                                w["start"]["fi"], w["start"]["cp"], w["start"]["cp_ref"]) for w in wins])
     ce = np.stack([dpe.engine.chan_end_array(w["sat"], w["rcEnd"], w["fc"], w["fi"], w["cpRefTOW"], w["cpElaEnd"],
                                              w["cpRef"]) for w in wins])
-    bw = np.concatenate([dpe.engine.bcm_window_array(w["centre"][None, :], w["R"][None, :], [w["rxTime"]]) for w in wins])
+    bw = np.concatenate([dpe.engine.bcm_window_array(w["centre"][None, :], w["R"][None, :], [w["rxTime"]], doppler_sign=case.get("ds", 1))
+                         for w in wins])
     iq = np.stack([w["iq"] for w in wins])
     return iq, cs, ce, bw
 

@@ -81,18 +81,21 @@ def test_no_cpu_fallback(built):
         dpe.Pipe(2.5e6, 50000, g, g, lag_half_width=4, bin_half_width=20, max_windows=2, max_channels=8, in_flight=2)
 
 
-def test_chanmgr_matches_oracle(built, oracle):
+@pytest.mark.parametrize("sign", [1, -1])
+def test_chanmgr_matches_oracle(built, oracle, sign):
     """Product cuChanMgr (host C++ in libdpe_hip.so) vs the oracle's independent restatement:
-    Start + 3 Updates on the handoff state, spread time grid."""
+    Start + 3 Updates on the handoff state, spread time grid.  sign = -1: DopplerSign -1 on the handoff with fi negated."""
     from tests import helpers
     ho = dpe.handoff.read_handoff(helpers.HANDOFF)
+    if sign == -1:
+        ho = dict(ho, fi=-ho["fi"])
     T = 0.02
     X = ho["X_ECEF"]
     pos, _ = dpe.synth.spread_grid()
     tg = np.unique(pos[:, 3])
-    cm = dpe.ChanMgr.from_handoff(ho, T)
+    cm = dpe.ChanMgr.from_handoff(ho, T, DopplerSign=sign)
     om = oracle.ChanMgr(ho["prn_list"], ho["rc"], ho["ri"], ho["fc"], ho["fi"], ho["cp"], ho["cp_timestamp"],
-                        ho["TOW"], ho["eph"], ho["rxTime"], T)
+                        ho["TOW"], ho["eph"], ho["rxTime"], T, doppler_sign=sign)
     for it in range(4):
         xk = X + np.array([0.3, -0.2, 0.1, 0.5, 0.01, 0.0, -0.02, 0.003]) * it   # a moving fix
         if it == 0:
@@ -106,29 +109,32 @@ def test_chanmgr_matches_oracle(built, oracle):
         assert np.abs(e["codePhaseEnd"] - om.rcEnd).max() < 1e-9 and np.array_equal(e["cpElapsedEnd"], om.cpElaEnd)
         assert np.abs(s["carrierPhaseStart"] - om.riStart).max() < 1e-12
         assert np.abs(s["codeFrequency"] - om.fc).max() < 1e-6 and np.abs(s["carrierFrequency"] - om.fi).max() < 1e-6
-        assert w["rxTime"][0] == om.rxTime
+        assert w["rxTime"][0] == om.rxTime and w["dopplerSign"][0] == sign
         assert np.abs(batch - ob).max() < 1e-6 and np.abs(w["enu2ecef"][0] - oR).max() < 1e-14
         assert np.abs(e["satState"] - ob[:, tg.size // 2]).max() < 1e-6
     cm.Stop()
 
 
-@pytest.mark.parametrize("seed,T,n", [(1, 0.02, 120), (2, 0.005, 150), (3, 0.001, 200), (4, 0.02, 60)])
-def test_chanmgr_long_runs_random_subsets(built, oracle, seed, T, n):
+@pytest.mark.parametrize("seed,T,n,sign", [(1, 0.02, 120, 1), (2, 0.005, 150, 1), (3, 0.001, 200, 1), (4, 0.02, 60, 1), (2, 0.005, 150, -1)],
+                         ids=["1-0.02-120", "2-0.005-150", "3-0.001-200", "4-0.02-60", "2-0.005-150-sign-1"])
+def test_chanmgr_long_runs_random_subsets(built, oracle, seed, T, n, sign):
     """Product cuChanMgr vs the oracle over long runs: random SV subsets, window lengths of 1 / 5 / 20 ms (code-period
     counters and nav-bit references roll over many times), a receiver that accelerates and whose fix is noisy.
-    Integer state must agree exactly at every step; phases must not drift apart."""
+    Integer state must agree exactly at every step; phases must not drift apart.  sign = -1: one seed again at DopplerSign -1."""
     from tests import helpers
     rng = np.random.Generator(np.random.PCG64(seed))
     ho = dpe.handoff.read_handoff(helpers.HANDOFF)
+    if sign == -1:
+        ho = dict(ho, fi=-ho["fi"])
     K = int(rng.integers(1, 9))
     sel = np.sort(rng.choice(8, size=K, replace=False))
     sub = dict(ho)
     for key in ("prn_list", "rc", "ri", "fc", "fi", "cp", "cp_timestamp", "TOW", "eph"):
         sub[key] = ho[key][sel]
     tg = np.array([-2.0, -1.0, 0.0, 1.0, 2.0]) * 6.0
-    cm = dpe.ChanMgr.from_handoff(sub, T)
+    cm = dpe.ChanMgr.from_handoff(sub, T, DopplerSign=sign)
     om = oracle.ChanMgr(sub["prn_list"], sub["rc"], sub["ri"], sub["fc"], sub["fi"], sub["cp"], sub["cp_timestamp"],
-                        sub["TOW"], sub["eph"], sub["rxTime"], T)
+                        sub["TOW"], sub["eph"], sub["rxTime"], T, doppler_sign=sign)
     x = ho["X_ECEF"].copy()
     v = rng.uniform(-30.0, 30.0, 3)
     for it in range(n):

@@ -49,20 +49,24 @@ def _compare(dev, host, K):
     return worst
 
 
-@pytest.mark.parametrize("K", [8, 1])
-def test_device_channel_manager_matches_the_host_form(K):
+@pytest.mark.parametrize("K,sign", [(8, 1), (1, 1), (8, -1), (1, -1)], ids=["8", "1", "8-sign-1", "1-sign-1"])
+def test_device_channel_manager_matches_the_host_form(K, sign):
     """Start + 5 Updates with a moving fix (tens of metres and m/s per window, clock terms included), time grid of 9 entries:
-    every port of the device form against dpe_chm_outputs."""
+    every port of the device form against dpe_chm_outputs.  sign = -1: DopplerSign -1 on the mirrored handoff (tests/mirror.py)."""
     import torch
+    from tests import mirror
     ho = dpe.handoff.read_handoff(dpe.workload.HANDOFF_CSV)
+    if sign == -1:
+        ho = mirror.mirror_handoff(ho)
     T = 0.02
     tg = np.linspace(-12.0, 12.0, 9)
-    host = dpe.engine.ChanMgr.from_handoff(ho, T, K)
-    dev = dpe.engine.ChanMgrDev.from_handoff(ho, T, K, tg)
+    host = dpe.engine.ChanMgr.from_handoff(ho, T, K, DopplerSign=sign)
+    dev = dpe.engine.ChanMgrDev.from_handoff(ho, T, K, tg, DopplerSign=sign)
     x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
     host.Start(x, x, tg)
     dev.Start(x)
     w = _compare(dev.outputs(with_batch=True), host.outputs(with_batch=True), K)
+    assert host.outputs()[2]["dopplerSign"][0] == sign
     rng = np.random.Generator(np.random.PCG64(5))
     for it in range(5):
         x1 = x + np.concatenate([rng.uniform(-30, 30, 3), rng.uniform(-40, 40, 1), rng.uniform(-3, 3, 3), rng.uniform(-1, 1, 1)])
@@ -73,7 +77,7 @@ def test_device_channel_manager_matches_the_host_form(K):
         w = _compare(dev.outputs(with_batch=True), host.outputs(with_batch=True), K)
         assert dev.status == 0, dev.status     # no Kepler failure
         x = x1
-    print("worst differences after 5 Updates:", {k: float("%.3g" % v) for k, v in w.items()})
+    print("worst differences after 5 Updates, DopplerSign %+d:" % sign, {k: float("%.3g" % v) for k, v in w.items()})
     dev.Stop(); host.Stop()
 
 

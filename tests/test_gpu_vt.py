@@ -33,7 +33,7 @@ def to_dev(iq):
 
 def make_vt(w, cfg, X0, n_epochs, **kw):
     s = w["start"]
-    vt = dpe.VectorTracker(cfg.fs, cfg.prns, T=cfg.T, N=cfg.N, num_prev=cfg.num_prev, log_capacity_epochs=max(n_epochs, 1), **kw)
+    vt = dpe.VectorTracker(cfg.fs, cfg.prns, T=cfg.T, N=cfg.N, ds=cfg.ds, num_prev=cfg.num_prev, log_capacity_epochs=max(n_epochs, 1), **kw)
     vt.set_ephemerides(s["eph"], s["tow"], s["cps"])
     vt.init(X0, vt_world.sigma0(), s["rxTime0"], s["chan"])
     return vt
@@ -61,15 +61,16 @@ def hold_to_yardstick(dev, ref_t, rnd_t, label, capsys):
     assert not bad, bad
 
 
-def small_case(oracle, K, T, N, n_epochs, seed=4):
-    """A short world for the shape tests: K channels (synthetic PRNs beyond the handoff's six), T, N."""
+def small_case(oracle, K, T, N, n_epochs, seed=4, ds=1.0):
+    """A short world for the shape tests: K channels (synthetic PRNs beyond the handoff's six), T, N; ds: the world's and the loop's
+    DopplerSign."""
     ho, chans = None, vt_world.CHANS[:K]
     if K > len(vt_world.CHANS):
         ho, chans = vt_world.synthetic_handoff(dpe.handoff.read_handoff(helpers.HANDOFF), K), list(range(K))
     S = int(round(T * vt_world.FS))
-    w = vt_world.build(oracle, n_epochs * N * S, chans=chans, ho=ho, seed=seed)
+    w = vt_world.build(oracle, n_epochs * N * S, chans=chans, ho=ho, seed=seed, ds=ds)
     iq = vt_world.record(w)
-    cfg = vt_ref.Config(vt_world.FS, w["start"]["prns"], T=T, N=N, num_prev=4)
+    cfg = vt_ref.Config(vt_world.FS, w["start"]["prns"], T=T, N=N, ds=ds, num_prev=4)
     X0 = vt_world.perturbed(w)
     ref = vt_ref.run(iq, cfg, oracle, w["start"], X0, vt_world.sigma0(), n_epochs)
     rnd = vt_ref.run(iq, cfg, oracle, w["start"], X0, vt_world.sigma0(), n_epochs, round_epl=np.float32)

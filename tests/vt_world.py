@@ -32,13 +32,18 @@ def synthetic_handoff(ho, K):
     return out
 
 
-def build(oracle, n_samples, chans=CHANS, fs=FS, seed=4, ho=None):
+def build(oracle, n_samples, chans=CHANS, fs=FS, seed=4, ho=None, ds=1.0):
     """nav_world.build with the epoch at sample n_samples // 2.  Adds `start`: the true state at sample 0 in the form the vector
-    tracker is initialised with (rxTime0, chan [K, 5] = rc ri fc fi cp, tow, cps, eph, prns, X)."""
+    tracker is initialised with (rxTime0, chan [K, 5] = rc ri fc fi cp, tow, cps, eph, prns, X).
+    ds = -1: the same world seen by a front end whose spectrum runs the other way: every fi negated, fc as it is (record() rotates by
+    ch["fi"], so the record is the mirrored one)."""
     ho = dpe.handoff.read_handoff(helpers.HANDOFF) if ho is None else ho
     n_e = n_samples // 2
     w = nav_world.build(oracle, ho, list(chans), fs, n_e, seed=seed, t_epoch=ho["rxTime"] + 2.0)
     ch, truth = w["ch"], w["truth"]
+    assert ds in (1.0, -1.0)
+    if ds == -1.0:
+        ch["fi"] = -np.asarray(ch["fi"], dtype=np.float64)
     K = len(chans)
     # nav_world encodes the bits up to its epoch; the second half of the span takes bits drawn from the seed (their content is not used)
     rng = np.random.default_rng(seed + 1000)
