@@ -1726,11 +1726,14 @@ class VectorTracker:
 
     def read_log(self, first=0, n=None, stream=None):
         """{X [n, 8], diag [n, 8], rxTime0, mask, status, n_incl [n], and per channel CHAN_NAMES [n, K]} for epochs [first, first + n)."""
+        return self.unpack_log(self.read_log_rows(first, n, stream), len(self.prns))
+
+    def read_log_rows(self, first=0, n=None, stream=None):
+        """The raw log rows [n, LOG_HEAD + MAX_CHAN * LOG_CHAN] of epochs [first, first + n), channels K .. MAX_CHAN - 1 included."""
         n = self.n_epochs - first if n is None else int(n)
-        K = len(self.prns)
         out = np.empty((n, self.LOG_HEAD + self.MAX_CHAN * self.LOG_CHAN), dtype=np.float64)
         _check(lib().dpe_vt_read_log(self._h, C.c_int64(first), C.c_int32(n), out.ctypes.data_as(C.POINTER(C.c_double)), _stream(stream)))
-        return self.unpack_log(out, K)
+        return out
 
     @classmethod
     def unpack_log(cls, out, K):
@@ -1747,10 +1750,15 @@ class VectorTracker:
         _check(lib().dpe_vt_read_corr(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), _stream(stream)))
         return out
 
-    def state(self, stream=None):
+    def state_rec(self, stream=None):
+        """The whole device state as the raw VtStateRec: beside what state() gives, every channel's satellite cache and residual
+        history, satValid and rxBase -- what filter_step_host takes as its `st`."""
         st = VtStateRec()
         _check(lib().dpe_vt_state(self._h, C.byref(st), _stream(stream)))
-        return self.unpack_state(st, len(self.prns))
+        return st
+
+    def state(self, stream=None):
+        return self.unpack_state(self.state_rec(stream), len(self.prns))
 
     @staticmethod
     def unpack_state(st, K):

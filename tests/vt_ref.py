@@ -38,6 +38,41 @@ def new_state(cfg, X, Sigma, rx_time0, chan):
                 histPos=np.zeros(cfg.K, dtype=np.int64))
 
 
+def state_from_rec(cfg, rec):
+    """dpe_vt_state_rec (engine.VtStateRec) -> the state dict of new_state: the inverse of tests/test_vt_host_cpu.host_state, with the
+    record's status kept."""
+    K, P = cfg.K, cfg.num_prev
+    ch = [rec.chan[k] for k in range(K)]
+    st = dict(X=np.array(rec.X, dtype=np.float64), Sigma=np.array(rec.Sigma, dtype=np.float64).reshape(8, 8), rxTime0=float(rec.rxTime0),
+              rxBase=float(rec.rxBase), epochs=int(rec.epochs), status=int(rec.status))
+    for n in ("rc", "ri", "fc", "fi", "cp"):
+        st[n] = np.array([getattr(c, n) for c in ch], dtype=np.float64)
+    st["sat"] = np.array([list(c.sat) for c in ch], dtype=np.float64) if rec.satValid else None
+    st["histR"] = np.array([list(c.histRange)[:P] for c in ch], dtype=np.float64)
+    st["histV"] = np.array([list(c.histRate)[:P] for c in ch], dtype=np.float64)
+    st["histN"] = np.array([c.histN for c in ch], dtype=np.int64)
+    st["histPos"] = np.array([c.histPos for c in ch], dtype=np.int64)
+    return st
+
+
+class Nudge:
+    """A model of another maths library and another Kepler solver, for measuring what such a difference does to an epoch's results:
+    every atan2 / sin / cos result handed to it moves by up to `ulps` units in the last place, in a seeded random direction; sat()
+    moves a satellite state by up to `sat_rel` of the orbit radius (2.6e7 m) and speed (3e3 m/s) and by sat_clk on the clock terms
+    -- the bounds tests/test_gpu_chm_dev.py holds sat_state to on the device."""
+
+    def __init__(self, seed, ulps=2, sat_rel=1e-12, sat_clk=1e-17):
+        self.rng, self.ulps, self.sat_rel, self.sat_clk = np.random.default_rng(seed), int(ulps), float(sat_rel), float(sat_clk)
+
+    def __call__(self, v):
+        return float(v + float(self.rng.integers(-self.ulps, self.ulps + 1)) * np.spacing(abs(v)))
+
+    def sat(self, s):
+        u = self.rng.uniform(-1.0, 1.0, 8)
+        scale = np.array([2.6e7 * self.sat_rel] * 3 + [self.sat_clk] + [3.0e3 * self.sat_rel] * 3 + [self.sat_clk])
+        return np.asarray(s, dtype=np.float64) + u * scale
+
+
 def window_params(st, k, j, T):
     return (np.mod(st["rc"][k] + j * st["fc"][k] * T, L_CA), np.mod(st["ri"][k] + j * st["fi"][k] * T, 1.0), st["fc"][k], st["fi"][k])
 
@@ -52,6 +87,9 @@ def correlate_epoch(iq, first_sample, cfg, st, chips=None, round_epl=None):
         x = wv[0::2] + 1j * wv[1::2]
         for k in range(cfg.K):
             rc, ri, fc, fi = window_params(st, k, j, cfg.T)
+            if not (fi == fi and ri == ri):            # vt_correlate_kernel's own test: such a window is case -1, its sums stay 0
+                out[j, k, 6] = -1.0
+                continue
             e, p, l, compl_, _, _, case, _ = trk_ref.correlate(x, chips[k], cfg.fs, rc, ri, fc, fi, 0j)
             if case < 0:
                 out[j, k, 6] = -1.0
@@ -68,11 +106,14 @@ def transmit(tow, cps, cp, rc, rx_time):
     return tow + ci + cf, ((rx_time - tow) - ci) - cf
 
 
-def geometry(sat, d, X, ds):
-    """-> los [3], Doppler / ds and predicted minus NCO code phase (chips) for the state X; sat at the NCO's transmit time."""
+def geometry(sat, d, X, ds, nudge=None):
+    """-> los [3], Doppler / ds and predicted minus NCO code phase (chips) for the state X; sat at the NCO's transmit time.
+    nudge: a Nudge that moves the cos and sin results (None: as computed)."""
     tau = d - (X[3] / C) + sat[3]
     a = -OE * tau
     ct, s_ = math.cos(a), math.sin(a)
+    if nudge is not None:
+        ct, s_ = nudge(ct), nudge(s_)
     p = np.array([ct * sat[0] - s_ * sat[1], s_ * sat[0] + ct * sat[1], sat[2]])
     v = np.array([ct * sat[4] - s_ * sat[5] - OE * s_ * sat[0] - OE * ct * sat[1], s_ * sat[4] + ct * sat[5] + OE * ct * sat[0] - OE * s_ * sat[1], sat[6]])
     lv = p - X[:3]
@@ -85,8 +126,8 @@ def geometry(sat, d, X, ds):
     return los, bc_fi, (d - pr / C) * F_CA, p, pr
 
 
-def discriminate(cfg, s):
-    """s [N, 8] of one channel -> bad, dpc, dfi, lock."""
+def discriminate(cfg, s, nudge=None):
+    """s [N, 8] of one channel -> bad, dpc, dfi, lock.  nudge: a Nudge that moves the atan2 result."""
     bad = bool(np.any(~(s[:, 6] >= 0.0)) or not np.all(np.isfinite(s[:, :6])))
     E = L = m1 = m2 = cross = dot = 0.0
     with np.errstate(all="ignore"):
@@ -109,7 +150,10 @@ def discriminate(cfg, s):
     if bad:
         return True, 0.0, 0.0, 0.0
     dpc = (E - L) / (2.0 * (E + L)) if E + L != 0.0 else 0.0
-    dfi = math.atan2(cross, dot) / (2.0 * math.pi * cfg.T)
+    at = math.atan2(cross, dot)
+    if nudge is not None:
+        at = nudge(at)
+    dfi = at / (2.0 * math.pi * cfg.T)
     m1, m2 = m1 / cfg.N, m2 / cfg.N
     var = m2 - m1 * m1
     lock = m1 / math.sqrt(var) if var > 0.0 else (1.0e30 if m1 > 0.0 else 0.0)
@@ -128,9 +172,11 @@ def variance(h, n):
     return v / n
 
 
-def filter_step(cfg, oracle, eph, tow, cps, st, sums, order=None):
+def filter_step(cfg, oracle, eph, tow, cps, st, sums, order=None, nudge=None):
     """One epoch's steps b - f on `st` (in place).  order: the sequence the included channels' rows are taken in (None: channel
-    order) -- the result's spread over such orders is the restatement's own rounding noise.  Returns the epoch's record (dict)."""
+    order) -- the result's spread over such orders is the restatement's own rounding noise.  nudge: a Nudge applied to every atan2,
+    sin and cos result and, in the epoch that computes them (st["sat"] None), to the satellite states of the epoch's start -- the
+    spread over such nudges is what another maths library may change.  Returns the epoch's record (dict)."""
     K, N = cfg.K, cfg.N
     X, P = st["X"], st["Sigma"]
     rec = {n: np.zeros(K) for n in CHAN_NAMES}
@@ -140,16 +186,18 @@ def filter_step(cfg, oracle, eph, tow, cps, st, sums, order=None):
         for k in range(K):
             tt, _ = transmit(tow[k], cps[k], st["cp"][k], st["rc"][k], st["rxTime0"])
             st["sat"][k], _ = oracle.sat_pos(eph[k], tt)
+            if nudge is not None:
+                st["sat"][k] = nudge.sat(st["sat"][k])
     rho = np.zeros(K)
     for k in range(K):
-        b, dpc, dfi, lock = discriminate(cfg, sums[:, k, :])
+        b, dpc, dfi, lock = discriminate(cfg, sums[:, k, :], nudge)
         wR, wV = cfg.init_var
         if st["histN"][k] >= cfg.num_prev:
             wR = max(variance(st["histR"][k], cfg.num_prev), cfg.min_var[0])
             wV = max(variance(st["histV"][k], cfg.num_prev), cfg.min_var[1])
         _, d = transmit(tow[k], cps[k], st["cp"][k], st["rc"][k], st["rxTime0"])
         with np.errstate(all="ignore"):
-            los[k], _, d_chips, _, pr = geometry(st["sat"][k], d, X, cfg.ds)
+            los[k], _, d_chips, _, pr = geometry(st["sat"][k], d, X, cfg.ds, nudge)
         if not np.all(np.isfinite(los[k])):
             b = True
         bad[k] = b
@@ -211,7 +259,7 @@ def filter_step(cfg, oracle, eph, tow, cps, st, sums, order=None):
         fiN, fcN = st["fi"][k], st["fc"][k]
         if rc_ == 0:
             with np.errstate(all="ignore"):
-                _, bc_fi, d_chips, _, _ = geometry(sat, d, X, cfg.ds)
+                _, bc_fi, d_chips, _, _ = geometry(sat, d, X, cfg.ds, nudge)
             fcB = F_CA + cfg.fcaid * bc_fi + d_chips / cfg.NT
             if np.isfinite(bc_fi) and np.isfinite(fcB):
                 fiN, fcN = bc_fi, fcB
