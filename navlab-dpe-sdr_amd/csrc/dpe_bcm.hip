@@ -68,6 +68,12 @@ __host__ __device__ inline size_t scan_grid_slot(long long i, int c)
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
+}  // namespace dpe
+
+#include "dpe_bcm_pieces.h"
+
+namespace dpe {
+
 // COMPACT: 12-byte LDS entries {A, B, C} instead of 16 (three dword reads per pair instead of b64 + b32): the layout for
 // bank sets that do not fit the LDS otherwise (37 channels with +-130 .. +-172 entries) -- slower, always with the clamps.
 template <int LP, bool SECOND, bool CLAMP, bool WMEAN, bool COMPACT = false>
@@ -76,19 +82,13 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
                                           int keyStride, int keySlot)
 {
     const f4 *__restrict__ grid = reinterpret_cast<const f4 *>(sd.grid);
-    const float2 *__restrict__ bank = sd.bank;
     float *__restrict__ scores = sd.scores;
     double *__restrict__ wsum = sd.wsum;
     const long long G = sd.G, indexOffset = sd.indexOffset;
     const int nEnt = sd.nEnt;
     const unsigned nBlkX = (unsigned)sd.split;   // persistent stride of this manifold's blocks
     extern __shared__ __align__(16) unsigned char smem[];
-    // |lerp|^2 = A + w (B + w C) per bank entry, stored as {A, B, 0, C}: one address register serves the
-    // ds_read_b64 {A,B} and the ds_read_b32 {C} (immediate offset 12; the gap keeps the compiler from fusing
-    // them into a slower ds_read_b96).  A wave's 64 points land on a few
-    // neighbouring entries (the index moves by << 1 entry per grid step), so the 16-byte stride is
-    // conflict-free as long as a wave spans < 16 entries.
-    float4 *sE = reinterpret_cast<float4 *>(smem);                           // [K][nEnt]
+    float4 *sE = reinterpret_cast<float4 *>(smem);                           // [K][nEnt] {A, B, 0, C} (scan_fill_bank)
     float *sF = reinterpret_cast<float *>(smem);                             // COMPACT: [K][nEnt][3]
     __shared__ unsigned long long sKey[4];
     __shared__ unsigned int sOob[4];
@@ -101,54 +101,21 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
     // robin, so each XCD's L2 keeps re-serving the same 1/8 of the grid for every window.
     // A thread's points: tile*1024 + tid + 256*it, held as PAIRS (scan_grid_slot) so that the geometry runs on packed fp32
     // (v_pk_fma_f32: two points per instruction).  The tile count and offsets fit 32 bits (G < 2^32, checked at create).
-    constexpr int kPairs = kPtsPerThread / 2;
     const unsigned nFull = (unsigned)(G / kPtsPerBlock);                         // tiles without padding
     const unsigned nTiles = (unsigned)((G + kPtsPerBlock - 1) / kPtsPerBlock);
     // two register sets for the grid points: tile n computes from one while tile n + nBlkX lands in the other
     f4 bufA[2 * kPairs], bufB[2 * kPairs];
-    // One tile's loads as buffer loads: the descriptor of the tile is built by scalar instructions, the lane's byte offset is
-    // loop-invariant and the slot offset an immediate, so fetching a tile issues no vector instruction besides the loads.
-    const auto load = [&](f4 (&g)[2 * kPairs], unsigned tile) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<f4 *>(grid + (size_t)tile * kPtsPerBlock), 0, kPtsPerBlock * (int)sizeof(f4), 0x00020000);
-#pragma unroll
-        for (int j = 0; j < 2 * kPairs; ++j)
-            g[j] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, tid * (int)sizeof(f4), j * 256 * (int)sizeof(f4), 0));
-    };
+    const auto load = [&](f4 (&g)[2 * kPairs], unsigned tile) { scan_load_tile(g, grid, tile, tid); };
     // first tile's grid points: issued before the bank fill so both latencies overlap
     if (blockIdx.x < nTiles) load(bufA, blockIdx.x);
-    const float2 *bw = bank + (size_t)w * maxK * nEnt;
-    for (int i = tid; i < K * nEnt; i += 256) {
-        const int k = i / nEnt, j = i - k * nEnt;
-        // |c0 + w (c1 - c0)|^2 = A + w (B + w C): the interpolated magnitude needs two FMAs per pair.
-        // Entry nEnt-1 can never be a valid lower neighbour: it is the all-zero slot that out-of-window
-        // indices are clamped to (contribution exactly 0).
-        if (j + 1 < nEnt) {
-            const float2 c0 = bw[(size_t)k * nEnt + j], c1 = bw[(size_t)k * nEnt + j + 1];
-            const float dr = c1.x - c0.x, di = c1.y - c0.y;
-            const float eA = c0.x * c0.x + c0.y * c0.y, eB = 2.f * (c0.x * dr + c0.y * di), eC = dr * dr + di * di;
-            if (COMPACT) { sF[3 * i] = eA; sF[3 * i + 1] = eB; sF[3 * i + 2] = eC; }
-#ifdef DPE_SCAN_SOA   // experiment (round 3, measured and dropped -- DESIGN.md 9): {A, B} as an 8-byte-stride array, C as a 4-byte-stride array behind it
-            else { reinterpret_cast<float2 *>(smem)[i] = make_float2(eA, eB); sF[2 * K * nEnt + i] = eC; }
-#else
-            else sE[i] = make_float4(eA, eB, 0.f, eC);
-#endif
-        } else {
-            if (COMPACT) { sF[3 * i] = 0.f; sF[3 * i + 1] = 0.f; sF[3 * i + 2] = 0.f; }
-#ifdef DPE_SCAN_SOA
-            else { reinterpret_cast<float2 *>(smem)[i] = make_float2(0.f, 0.f); sF[2 * K * nEnt + i] = 0.f; }
-#else
-            else sE[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
-        }
-    }
+    const float2 *bw = sd.bank + (size_t)w * maxK * nEnt;
+    scan_fill_bank<COMPACT>(sE, bw, K * nEnt, nEnt, tid);
     __syncthreads();
 
     const unsigned last = (unsigned)(nEnt - 1);
     // wave-uniform address -> scalar loads; inl: this manifold's coefficients come from pb.s[SECOND ? 0 : 1]
     const BcmSvDev *svw = params_ptr(sd.sv + (size_t)w * maxK, inl) + ((inl && !SECOND) ? DPE_MAX_CHAN : 0);
-    // per-lane running maximum as (score, index): a lane visits its points in increasing index order, so a strict
-    // "greater" keeps the first maximum; the packed 64-bit key is built once, after the tile loop
+    // per-lane running maximum as (score, tile, it); the packed 64-bit key is built once, after the tile loop
     float bestSc = -1.f;          // scores are >= 0
     unsigned int bestTile = 0u, bestIt = 0u;
     unsigned int nOob = 0;
@@ -160,91 +127,22 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
     const auto tile_body = [&](const f4 (&g)[2 * kPairs], unsigned tile, auto raggedTag) {
         constexpr bool RAGGED = decltype(raggedTag)::value;
         const long long base = (long long)tile * kPtsPerBlock + tid;   // (ragged tile only)
-        f2 dx[kPairs], dy[kPairs], dz[kPairs], dw[kPairs], q[kPairs], score[kPairs];
+        ScanPts pt;
+        scan_unpack(pt, g);
+        f2 score[kPairs];
 #pragma unroll
-        for (int p = 0; p < kPairs; ++p) {
-            dx[p] = g[2 * p].xy; dy[p] = g[2 * p].zw; dz[p] = g[2 * p + 1].xy; dw[p] = g[2 * p + 1].zw;
-            q[p] = dx[p] * dx[p] + dy[p] * dy[p] + dz[p] * dz[p];
-            score[p] = f2{0.f, 0.f};
-        }
+        for (int p = 0; p < kPairs; ++p) score[p] = f2{0.f, 0.f};
         unsigned emax = 0;
 #pragma unroll DPE_SV_UNROLL
         for (int k = 0; k < K; ++k) {
             const BcmSvDev s = svw[k];
-            const float4 *bk = sE + k * nEnt;
+            const void *bk = COMPACT ? (const void *)sF : (const void *)(sE + k * nEnt);   // COMPACT: the bank; the row goes with the entry
 #pragma unroll
-            for (int p = 0; p < kPairs; ++p) {
-                f2 idx;
-                if (SECOND) {
-                    f2 a = dx[p] * s.ue;
-                    a = __builtin_elementwise_fma(dy[p], f2{s.un, s.un}, a);
-                    a = __builtin_elementwise_fma(dz[p], f2{s.uu, s.uu}, a);
-                    f2 x = dw[p] - a;
-                    const f2 t = __builtin_elementwise_fma(-a, a, q[p]);          // q - a^2
-                    x = __builtin_elementwise_fma(t, f2{s.h, s.h}, x);             // + (q - a^2) / (2 range)
-                    idx = __builtin_elementwise_fma(x, f2{s.g, s.g}, f2{s.idx0, s.idx0});
-                } else {
-                    idx = __builtin_elementwise_fma(dw[p], f2{s.g, s.g}, f2{s.idx0, s.idx0});
-                    idx = __builtin_elementwise_fma(dx[p], f2{-s.h, -s.h}, idx);
-                    idx = __builtin_elementwise_fma(dy[p], f2{-s.pad0, -s.pad0}, idx);
-                    idx = __builtin_elementwise_fma(dz[p], f2{-s.pad1, -s.pad1}, idx);
-                }
-                float c[2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const float id = idx[j];
-                    const float wgt = __builtin_amdgcn_fractf(id);                 // id - floor(id)
-                    int ei;
-                    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ei) : "v"(id));          // (int)floor(id), saturating
-                    unsigned e = (unsigned)ei;
-                    if (CLAMP) {                                                   // negative -> huge -> zero slot
-                        e = min(e, last);
-                        emax = max(emax, e);
-                    }
-                    float m2;
-                    if (COMPACT) {
-                        const float *bf = sF + ((size_t)k * nEnt + e) * 3;
-                        m2 = fmaf(wgt, fmaf(wgt, bf[2], bf[1]), bf[0]);
-                    } else {
-#if defined(DPE_SCAN_SOA)
-                        const float2 ab = reinterpret_cast<const float2 *>(smem)[k * nEnt + e];
-                        m2 = fmaf(wgt, fmaf(wgt, sF[2 * K * nEnt + k * nEnt + e], ab.y), ab.x);
-#else
-                        const float2 ab = *reinterpret_cast<const float2 *>(&bk[e]);
-                        m2 = fmaf(wgt, fmaf(wgt, bk[e].w, ab.y), ab.x);
-#endif
-                    }
-                    if (LP == 1) c[j] = __builtin_amdgcn_sqrtf(__builtin_fabsf(m2));    // raw v_sqrt_f32 (1 ulp)
-                    else if (LP == 2) c[j] = m2;
-                    else c[j] = powf(__builtin_amdgcn_sqrtf(__builtin_fabsf(m2)), (float)lpower);
-                }
-                score[p] += f2{c[0], c[1]};
-            }
+            for (int p = 0; p < kPairs; ++p)
+                score[p] += scan_pair_term<LP, SECOND, CLAMP, COMPACT>(pt, p, s, bk, last, emax, lpower, COMPACT ? (size_t)k * nEnt : 0);
         }
-        // out-of-window bookkeeping off the fast path: recount only if this thread ever hit the zero slot (the ragged tile's
-        // padded points may have: they are skipped)
-        if (CLAMP && emax == last) {
-            for (int it = 0; it < kPtsPerThread; ++it) {
-                if (RAGGED && base + it * 256 >= G) continue;
-                const float px = dx[it >> 1][it & 1], py = dy[it >> 1][it & 1], pz = dz[it >> 1][it & 1];
-                const float pw = dw[it >> 1][it & 1], pq = q[it >> 1][it & 1];
-                for (int k = 0; k < K; ++k) {
-                    const BcmSvDev s = svw[k];
-                    float id;
-                    if (SECOND) {
-                        const float a = fmaf(pz, s.uu, fmaf(py, s.un, px * s.ue));
-                        float x = pw - a;
-                        x = fmaf(fmaf(-a, a, pq), s.h, x);
-                        id = fmaf(x, s.g, s.idx0);
-                    } else {   // the fast path's own expression, operation for operation
-                        id = fmaf(pz, -s.pad1, fmaf(py, -s.pad0, fmaf(px, -s.h, fmaf(pw, s.g, s.idx0))));
-                    }
-                    int ei;
-                    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ei) : "v"(id));
-                    nOob += (min((unsigned)ei, last) == last) ? 1u : 0u;
-                }
-            }
-        }
+        // recount only if this thread ever hit the zero slot (the ragged tile's padded points may have: they are skipped)
+        if (CLAMP && emax == last) scan_recount<SECOND, RAGGED>(pt, svw, K, last, base, G, [&](int, unsigned n) DPE_INLINE_LAMBDA { nOob += n; });
         if (WMEAN) {
 #pragma unroll
             for (int p = 0; p < kPairs; ++p) {
@@ -254,60 +152,22 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
                     if (base + (2 * p + 1) * 256 >= G) sc.y = 0.f;
                 }
                 w0 += sc;
-                w1 = __builtin_elementwise_fma(sc, dx[p], w1);
-                w2 = __builtin_elementwise_fma(sc, dy[p], w2);
-                w3 = __builtin_elementwise_fma(sc, dz[p], w3);
-                w4 = __builtin_elementwise_fma(sc, dw[p], w4);
+                w1 = __builtin_elementwise_fma(sc, pt.dx[p], w1);
+                w2 = __builtin_elementwise_fma(sc, pt.dy[p], w2);
+                w3 = __builtin_elementwise_fma(sc, pt.dz[p], w3);
+                w4 = __builtin_elementwise_fma(sc, pt.dw[p], w4);
             }
         }
-        // scores are written once and never read back on this path: non-temporal stores keep ~0.8 GB per 256-window
-        // call from lingering as dirty L2 / Infinity-Cache lines whose write-back would run into the NEXT call's
-        // first kernels (measured: the following DC-sum kernel 25 -> 13 us, step 0.863 -> 0.851 ms)
-        if (scores) {
-            float *srow = scores + (size_t)w * sd.pitch + (size_t)tile * kPtsPerBlock;   // wave-uniform
-#pragma unroll
-            for (int it = 0; it < kPtsPerThread; ++it)
-                if (!RAGGED || base + it * 256 < G) __builtin_nontemporal_store(score[it >> 1][it & 1], &srow[it * 256 + tid]);
-        }
+        if (scores) scan_store_row<RAGGED>(scores + (size_t)w * sd.pitch + (size_t)tile * kPtsPerBlock, score, base, G, tid);
         // the running maximum remembers (tile, it) of its point; the index is formed once, after the tile loop
-#pragma unroll
-        for (int it = 0; it < kPtsPerThread; ++it) {
-            const float sc = score[it >> 1][it & 1];
-            if ((!RAGGED || base + it * 256 < G) && sc > bestSc) { bestSc = sc; bestTile = tile; bestIt = (unsigned)it; }
-        }
+        scan_track_max<RAGGED>(score, base, G, tile, bestSc, bestTile, bestIt);
     };
-    // Full tiles, unrolled by two so that the prefetch alternates between the register sets (no moves carry a tile from one
-    // set to the other); the ragged tile, if this block owns it, comes last (it is the grid's last tile).
     unsigned tile = blockIdx.x;
-    for (;;) {
-        if (tile >= nFull) break;
-        const unsigned t1 = tile + nBlkX;
-        if (t1 < nTiles) load(bufB, t1);
-        tile_body(bufA, tile, std::false_type{});
-        tile = t1;
-        if (tile >= nFull) {
-#pragma unroll
-            for (int j = 0; j < 2 * kPairs; ++j) bufA[j] = bufB[j];   // (once per block, for the ragged tile below)
-            break;
-        }
-        const unsigned t2 = tile + nBlkX;
-        if (t2 < nTiles) load(bufA, t2);
-        tile_body(bufB, tile, std::false_type{});
-        tile = t2;
-    }
-    if (tile < nTiles) tile_body(bufA, tile, std::true_type{});
+    scan_walk_tiles(tile, nBlkX, nFull, nTiles, bufA, bufB, load, tile_body);
     // global index of the lane's best point (< 2^32, checked at create)
-    const unsigned int bestIdx = (unsigned int)indexOffset + bestTile * (unsigned int)kPtsPerBlock + bestIt * 256u + (unsigned int)tid;
-    unsigned long long best = bestSc < 0.f ? 0ull
-                                           : (((unsigned long long)__float_as_uint(bestSc) << 32) |
-                                              (unsigned long long)(0xFFFFFFFFu - bestIdx));
-    // block arg-max: larger score wins, ties -> smaller global index (thrust::max_element, :2589)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off, 64);
-        best = o > best ? o : best;
-        nOob += __shfl_xor(nOob, off, 64);
-    }
+    const unsigned int bestIdx = (unsigned int)indexOffset + scan_local_index(bestTile, bestIt, tid);
+    const unsigned long long best = wave_max_key(pack_key(bestSc, bestIdx));
+    nOob = wave_sum(nOob);
     double ws[5] = {(double)w0.x + (double)w0.y, (double)w1.x + (double)w1.y, (double)w2.x + (double)w2.y,
                     (double)w3.x + (double)w3.y, (double)w4.x + (double)w4.y};
     if (WMEAN) {
@@ -326,23 +186,14 @@ __device__ __forceinline__ void scan_body(const ScanSide &sd, int inl, int K, in
     }
     __syncthreads();
     if (tid == 0) {
-        unsigned long long b = sKey[0];
-        b = sKey[1] > b ? sKey[1] : b;
-        b = sKey[2] > b ? sKey[2] : b;
-        b = sKey[3] > b ? sKey[3] : b;
-        // integer max: order-independent.  RETURNING atomics: their results are waited for before this
-        // block takes its ticket (see the fused kernel), which orders them without a release fence -- on
-        // gfx950 an agent-scope fence writes back the XCD's whole L2 (all the dirty score lines)
-        unsigned long long seen = atomicMax(&keys[(size_t)w * keyStride + keySlot], b);
         // per-block partial of the weighted sums, reduced on the host in block order (deterministic)
         if (WMEAN) {
             double *o = wsum + ((size_t)w * nBlkX + blockIdx.x) * 5;   // wsum already points at this manifold's half
 #pragma unroll
             for (int j = 0; j < 5; ++j) o[j] = ((sW[0][j] + sW[1][j]) + sW[2][j]) + sW[3][j];
         }
-        const unsigned int n = sOob[0] + sOob[1] + sOob[2] + sOob[3];
-        if (n) seen += atomicAdd(&oob[(size_t)w * keyStride + keySlot], (unsigned long long)n);
-        asm volatile("" ::"v"(seen) : "memory");   // keep the returns (and the s_waitcnt they imply) alive, and the ticket below them
+        scan_post_key(&keys[(size_t)w * keyStride + keySlot], &oob[(size_t)w * keyStride + keySlot], block_max_key(sKey),
+                      sOob[0] + sOob[1] + sOob[2] + sOob[3]);
     }
 }
 
@@ -740,10 +591,9 @@ static unsigned scan_split(long long G, int nWindows, int forced)
     return (unsigned)s;
 }
 
-struct ScanLaunch {
-    dpe::BcmParamBlock pb;
-    int inl, K, maxK, lp;
-    dpe::ScanSide sp, sv;
+// What every scan launch carries behind its own arguments: the key / counter set it reduces into, the set it clears, the
+// publishing epilogue's pointers (scan_publish) and the launch geometry
+struct ScanTail {
     unsigned long long *keys, *oob, *clr;
     int clrN;
     unsigned int *done;
@@ -753,43 +603,64 @@ struct ScanLaunch {
     hipStream_t st;
 };
 
-template <int LP, bool WM>
-static void launch_scan_compact(const ScanLaunch &a)
+// The runtime (lPower, clampP, clampV, fourth flag) of a launch as template arguments: f(LP, CP, CV, X) is called once, with
+// std::integral_constant values (LP: 1, 2, or 0 for the general power).  clampP / clampV = false only when the host has proved
+// that every index of every (point, SV) pair of that manifold stays inside the bank (then the kernel drops the range clamp and
+// the out-of-window bookkeeping); the fourth flag is the family's own (weighted mean, own keys, subsets; unused by some).
+template <class F>
+static void scan_dispatch(int lp, bool clampP, bool clampV, bool x, const F &f)
 {
-    hipLaunchKernelGGL((dpe::bcm_scan_kernel<LP, true, true, WM, true>), a.grid, dim3(256), a.lds, a.st, a.pb, a.inl, a.sp, a.sv, a.K, a.maxK,
-                       a.lp, a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+    const auto pick = [](bool b, const auto &g) { if (b) g(std::true_type{}); else g(std::false_type{}); };
+    const auto with_lp = [&](auto LP) {
+        pick(clampP, [&](auto CP) { pick(clampV, [&](auto CV) { pick(x, [&](auto X) { f(LP, CP, CV, X); }); }); });
+    };
+    if (lp == 1) with_lp(std::integral_constant<int, 1>{});
+    else if (lp == 2) with_lp(std::integral_constant<int, 2>{});
+    else with_lp(std::integral_constant<int, 0>{});
 }
 
-template <int LP, bool CP, bool CV, bool WM>
-static void launch_scan4(const ScanLaunch &a)
+// f(LP, CP, CV, X) once for every variant of a family (fourth: the family has a fourth flag; without one X is always false);
+// big_lds lets one of them use the whole LDS (create calls it for all)
+template <class F>
+static void scan_every_variant(bool fourth, const F &f)
 {
-    hipLaunchKernelGGL((dpe::bcm_scan_kernel<LP, CP, CV, WM>), a.grid, dim3(256), a.lds, a.st, a.pb, a.inl, a.sp, a.sv, a.K, a.maxK,
-                       a.lp, a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+    for (int lp = 0; lp < 3; ++lp)
+        for (int m = 0; m < (fourth ? 8 : 4); ++m) scan_dispatch(lp, (m & 1) != 0, (m & 2) != 0, (m & 4) != 0, f);
 }
 
-template <bool CP, bool CV, bool WM>
-static void launch_scan3(const ScanLaunch &a)
+template <class Kernel>
+static void big_lds(Kernel *kernel)
 {
-    if (a.lp == 1) launch_scan4<1, CP, CV, WM>(a);
-    else if (a.lp == 2) launch_scan4<2, CP, CV, WM>(a);
-    else launch_scan4<0, CP, CV, WM>(a);
+    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024);
 }
 
-// clampP / clampV = false only when the host has proved that every index of every (point, SV) pair of
-// that manifold stays inside the bank (then the kernel drops the range clamp and the out-of-window
-// bookkeeping); wmean selects the variant that also accumulates the weighted-mean sums
+#define DPE_V(T) decltype(T)::value   // the value of a dispatch argument, as a template argument
+
+struct ScanLaunch : ScanTail {
+    dpe::BcmParamBlock pb;
+    int inl, K, maxK, lp;
+    dpe::ScanSide sp, sv;
+};
+
+// wmean selects the variant that also accumulates the weighted-mean sums; compact the 12-byte LDS entries (always clamped)
 static void launch_scan(bool clampP, bool clampV, bool wmean, bool compact, const ScanLaunch &a)
 {
-    if (compact) {
-#define DPE_SCAN_C(LPV) do { if (wmean) launch_scan_compact<LPV, true>(a); else launch_scan_compact<LPV, false>(a); } while (0)
-        if (a.lp == 1) DPE_SCAN_C(1); else if (a.lp == 2) DPE_SCAN_C(2); else DPE_SCAN_C(0);
-#undef DPE_SCAN_C
-        return;
-    }
-#define DPE_SCAN_PICK(CP, CV) do { if (wmean) launch_scan3<CP, CV, true>(a); else launch_scan3<CP, CV, false>(a); } while (0)
-    if (clampP) { if (clampV) DPE_SCAN_PICK(true, true); else DPE_SCAN_PICK(true, false); }
-    else { if (clampV) DPE_SCAN_PICK(false, true); else DPE_SCAN_PICK(false, false); }
-#undef DPE_SCAN_PICK
+    scan_dispatch(a.lp, clampP, clampV, wmean, [&](auto LP, auto CP, auto CV, auto WM) {
+        if (compact)
+            hipLaunchKernelGGL((dpe::bcm_scan_kernel<DPE_V(LP), true, true, DPE_V(WM), true>), a.grid, dim3(256), a.lds, a.st, a.pb, a.inl, a.sp, a.sv,
+                               a.K, a.maxK, a.lp, a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+        else
+            hipLaunchKernelGGL((dpe::bcm_scan_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV), DPE_V(WM)>), a.grid, dim3(256), a.lds, a.st, a.pb, a.inl, a.sp,
+                               a.sv, a.K, a.maxK, a.lp, a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+    });
+}
+
+static void allow_big_lds_scan()
+{
+    scan_every_variant(true, [](auto LP, auto CP, auto CV, auto WM) {
+        big_lds(dpe::bcm_scan_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV), DPE_V(WM)>);
+        if (DPE_V(CP) && DPE_V(CV)) big_lds(dpe::bcm_scan_kernel<DPE_V(LP), true, true, DPE_V(WM), true>);   // compact: always clamped
+    });
 }
 
 // Grids given by their axes (dpe_bcm_create_axes): the same launch with AxesSide in place of ScanSide
@@ -798,38 +669,18 @@ struct AxesLaunch {
     dpe::AxesSide sp, sv;
 };
 
-template <int LP, bool CP, bool CV, bool WM>
-static void launch_axes4(const AxesLaunch &x)
-{
-    const ScanLaunch &a = x.a;
-    hipLaunchKernelGGL((dpe::bcm_scan_axes_kernel<LP, CP, CV, WM>), a.grid, dim3(256), a.lds, a.st, a.pb, a.inl, x.sp, x.sv, a.K, a.maxK,
-                       a.lp, a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
-}
-
-template <bool CP, bool CV, bool WM>
-static void launch_axes3(const AxesLaunch &x)
-{
-    if (x.a.lp == 1) launch_axes4<1, CP, CV, WM>(x);
-    else if (x.a.lp == 2) launch_axes4<2, CP, CV, WM>(x);
-    else launch_axes4<0, CP, CV, WM>(x);
-}
-
 static void launch_axes(bool clampP, bool clampV, bool wmean, const AxesLaunch &x)
 {
-#define DPE_AXES_PICK(CP, CV) do { if (wmean) launch_axes3<CP, CV, true>(x); else launch_axes3<CP, CV, false>(x); } while (0)
-    if (clampP) { if (clampV) DPE_AXES_PICK(true, true); else DPE_AXES_PICK(true, false); }
-    else { if (clampV) DPE_AXES_PICK(false, true); else DPE_AXES_PICK(false, false); }
-#undef DPE_AXES_PICK
+    const ScanLaunch &a = x.a;
+    scan_dispatch(a.lp, clampP, clampV, wmean, [&](auto LP, auto CP, auto CV, auto WM) {
+        hipLaunchKernelGGL((dpe::bcm_scan_axes_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV), DPE_V(WM)>), a.grid, dim3(256), a.lds, a.st, a.pb, a.inl, x.sp, x.sv,
+                           a.K, a.maxK, a.lp, a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+    });
 }
 
-template <int LP>
 static void allow_big_lds_axes()
 {
-#define DPE_AXES_LDS(CP, CV, WM) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_axes_kernel<LP, CP, CV, WM>, \
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
-    DPE_AXES_LDS(true, true, false); DPE_AXES_LDS(true, false, false); DPE_AXES_LDS(false, true, false); DPE_AXES_LDS(false, false, false);
-    DPE_AXES_LDS(true, true, true); DPE_AXES_LDS(true, false, true); DPE_AXES_LDS(false, true, true); DPE_AXES_LDS(false, false, true);
-#undef DPE_AXES_LDS
+    scan_every_variant(true, [](auto LP, auto CP, auto CV, auto WM) { big_lds(dpe::bcm_scan_axes_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV), DPE_V(WM)>); });
 }
 
 // One manifold's AxesSide (m = 0 position, 1 velocity) for this handle's slice; the tile count comes back in *nTiles
@@ -852,188 +703,91 @@ static dpe::AxesSide axes_side(const dpe_bcm *h, int m, long long *nTiles)
     return s;
 }
 
-template <int LP, bool CP, bool CV>
-static void allow_big_lds()
-{
-    (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_kernel<LP, CP, CV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024);
-    (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_kernel<LP, CP, CV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024);
-    if (CP && CV) {
-        (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_kernel<LP, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024);
-        (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_kernel<LP, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024);
-    }
-}
-
 // Several receivers over one pair of grids (dpe_bcm_update_joint)
-struct JointLaunch {
+struct JointLaunch : ScanTail {
     dpe::ScanSide sp, sv;
     const dpe::JointRxDev *rx;
     int nRx, maxRx, maxKT, lp;
-    unsigned long long *keys, *oob, *ownKeys, *ownOob, *clr;
-    int clrN;
-    unsigned int *done;
-    unsigned long long *hostKeys, *hostOob, seq;
-    dim3 grid;
-    size_t lds;
-    hipStream_t st;
+    unsigned long long *ownKeys, *ownOob;
 };
-
-template <int LP, bool CP, bool CV, bool OWN>
-static void launch_joint4(const JointLaunch &a)
-{
-    hipLaunchKernelGGL((dpe::bcm_scan_joint_kernel<LP, CP, CV, OWN>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.rx, a.nRx, a.maxRx, a.maxKT, a.lp,
-                       a.keys, a.oob, a.ownKeys, a.ownOob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
-}
-
-template <bool CP, bool CV, bool OWN>
-static void launch_joint3(const JointLaunch &a)
-{
-    if (a.lp == 1) launch_joint4<1, CP, CV, OWN>(a);
-    else if (a.lp == 2) launch_joint4<2, CP, CV, OWN>(a);
-    else launch_joint4<0, CP, CV, OWN>(a);
-}
 
 static void launch_joint(bool clampP, bool clampV, bool own, const JointLaunch &a)
 {
-#define DPE_JOINT_PICK(CP, CV) do { if (own) launch_joint3<CP, CV, true>(a); else launch_joint3<CP, CV, false>(a); } while (0)
-    if (clampP) { if (clampV) DPE_JOINT_PICK(true, true); else DPE_JOINT_PICK(true, false); }
-    else { if (clampV) DPE_JOINT_PICK(false, true); else DPE_JOINT_PICK(false, false); }
-#undef DPE_JOINT_PICK
+    scan_dispatch(a.lp, clampP, clampV, own, [&](auto LP, auto CP, auto CV, auto OWN) {
+        hipLaunchKernelGGL((dpe::bcm_scan_joint_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV), DPE_V(OWN)>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.rx, a.nRx,
+                           a.maxRx, a.maxKT, a.lp, a.keys, a.oob, a.ownKeys, a.ownOob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+    });
 }
 
-template <int LP>
 static void allow_big_lds_joint()
 {
-#define DPE_JOINT_LDS(CP, CV, OWN) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_joint_kernel<LP, CP, CV, OWN>, \
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
-    DPE_JOINT_LDS(true, true, false); DPE_JOINT_LDS(true, false, false); DPE_JOINT_LDS(false, true, false); DPE_JOINT_LDS(false, false, false);
-    DPE_JOINT_LDS(true, true, true); DPE_JOINT_LDS(true, false, true); DPE_JOINT_LDS(false, true, true); DPE_JOINT_LDS(false, false, true);
-#undef DPE_JOINT_LDS
+    scan_every_variant(true, [](auto LP, auto CP, auto CV, auto OWN) { big_lds(dpe::bcm_scan_joint_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV), DPE_V(OWN)>); });
 }
 
 // N consecutive windows per score row (dpe_bcm_update_epochs)
-struct EpochsLaunch {
+struct EpochsLaunch : ScanTail {
     dpe::ScanSide sp, sv;
     int nEpochs, winPerPass, K, maxK, lp;
-    unsigned long long *keys, *oob, *clr;
-    int clrN;
-    unsigned int *done;
-    unsigned long long *hostKeys, *hostOob, seq;
-    dim3 grid;
-    size_t lds;
-    hipStream_t st;
 };
-
-template <int LP, bool CP, bool CV>
-static void launch_epochs3(const EpochsLaunch &a)
-{
-    hipLaunchKernelGGL((dpe::bcm_scan_epochs_kernel<LP, CP, CV>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.nEpochs, a.winPerPass, a.K, a.maxK, a.lp,
-                       a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
-}
 
 static void launch_epochs(bool clampP, bool clampV, const EpochsLaunch &a)
 {
-#define DPE_EPOCHS_PICK(CP, CV) do { if (a.lp == 1) launch_epochs3<1, CP, CV>(a); else if (a.lp == 2) launch_epochs3<2, CP, CV>(a); \
-                                     else launch_epochs3<0, CP, CV>(a); } while (0)
-    if (clampP) { if (clampV) DPE_EPOCHS_PICK(true, true); else DPE_EPOCHS_PICK(true, false); }
-    else { if (clampV) DPE_EPOCHS_PICK(false, true); else DPE_EPOCHS_PICK(false, false); }
-#undef DPE_EPOCHS_PICK
+    scan_dispatch(a.lp, clampP, clampV, false, [&](auto LP, auto CP, auto CV, auto) {
+        hipLaunchKernelGGL((dpe::bcm_scan_epochs_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV)>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.nEpochs, a.winPerPass,
+                           a.K, a.maxK, a.lp, a.keys, a.oob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+    });
 }
 
-template <int LP>
 static void allow_big_lds_epochs()
 {
-#define DPE_EPOCHS_LDS(CP, CV) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_epochs_kernel<LP, CP, CV>, \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
-    DPE_EPOCHS_LDS(true, true); DPE_EPOCHS_LDS(true, false); DPE_EPOCHS_LDS(false, true); DPE_EPOCHS_LDS(false, false);
-#undef DPE_EPOCHS_LDS
+    scan_every_variant(false, [](auto LP, auto CP, auto CV, auto) { big_lds(dpe::bcm_scan_epochs_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV)>); });
 }
 
 // Every SV subset's arg-max from one scan (dpe_bcm_update_subsets)
-struct SubsetsLaunch {
+struct SubsetsLaunch : ScanTail {
     dpe::ScanSide sp, sv;
     int K, maxK, lp, nSubsets, maxSubsets;
     const unsigned long long *masks;
-    unsigned long long *keys, *oob, *subKeys, *svOob, *clr;
-    int clrN;
-    unsigned int *done;
-    unsigned long long *hostKeys, *hostOob, seq;
-    dim3 grid;
-    size_t lds;
-    hipStream_t st;
+    unsigned long long *subKeys, *svOob;
 };
-
-template <int LP, bool CP, bool CV, bool SUBS>
-static void launch_subsets4(const SubsetsLaunch &a)
-{
-    hipLaunchKernelGGL((dpe::bcm_scan_subsets_kernel<LP, CP, CV, SUBS>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.K, a.maxK, a.lp, a.masks, a.nSubsets,
-                       a.maxSubsets, a.keys, a.oob, a.subKeys, a.svOob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
-}
-
-template <bool CP, bool CV, bool SUBS>
-static void launch_subsets3(const SubsetsLaunch &a)
-{
-    if (a.lp == 1) launch_subsets4<1, CP, CV, SUBS>(a);
-    else if (a.lp == 2) launch_subsets4<2, CP, CV, SUBS>(a);
-    else launch_subsets4<0, CP, CV, SUBS>(a);
-}
 
 static void launch_subsets(bool clampP, bool clampV, const SubsetsLaunch &a)
 {
-#define DPE_SUBSETS_PICK(CP, CV) do { if (a.nSubsets > 0) launch_subsets3<CP, CV, true>(a); else launch_subsets3<CP, CV, false>(a); } while (0)
-    if (clampP) { if (clampV) DPE_SUBSETS_PICK(true, true); else DPE_SUBSETS_PICK(true, false); }
-    else { if (clampV) DPE_SUBSETS_PICK(false, true); else DPE_SUBSETS_PICK(false, false); }
-#undef DPE_SUBSETS_PICK
+    scan_dispatch(a.lp, clampP, clampV, a.nSubsets > 0, [&](auto LP, auto CP, auto CV, auto SUBS) {
+        hipLaunchKernelGGL((dpe::bcm_scan_subsets_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV), DPE_V(SUBS)>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.K, a.maxK,
+                           a.lp, a.masks, a.nSubsets, a.maxSubsets, a.keys, a.oob, a.subKeys, a.svOob, a.clr, a.clrN, a.done, a.hostKeys, a.hostOob, a.seq);
+    });
 }
 
-template <int LP>
 static void allow_big_lds_subsets()
 {
-#define DPE_SUBSETS_LDS(CP, CV, SUBS) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_subsets_kernel<LP, CP, CV, SUBS>, \
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
-    DPE_SUBSETS_LDS(true, true, false); DPE_SUBSETS_LDS(true, false, false); DPE_SUBSETS_LDS(false, true, false); DPE_SUBSETS_LDS(false, false, false);
-    DPE_SUBSETS_LDS(true, true, true); DPE_SUBSETS_LDS(true, false, true); DPE_SUBSETS_LDS(false, true, true); DPE_SUBSETS_LDS(false, false, true);
-#undef DPE_SUBSETS_LDS
+    scan_every_variant(true, [](auto LP, auto CP, auto CV, auto SUBS) { big_lds(dpe::bcm_scan_subsets_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV), DPE_V(SUBS)>); });
 }
 
-// One level of a coarse-to-fine Update (dpe_bcm_update_refine)
-struct RefineLaunch {
+// One level of a coarse-to-fine Update (dpe_bcm_update_refine): nothing is published, so of the tail only keys, oob, clr, clrN
+// and the geometry are used
+struct RefineLaunch : ScanTail {
     dpe::RefineSide sp, sv;
     int level, K, maxK, lp;
-    unsigned long long *keys, *oob;
     const unsigned long long *prevKeys;
     float *centres;
     const float *prevCentres;
-    unsigned long long *clr;
-    int clrN;
-    dim3 grid;
-    size_t lds;
-    hipStream_t st;
 };
-
-template <int LP, bool CP, bool CV>
-static void launch_refine3(const RefineLaunch &a)
-{
-    hipLaunchKernelGGL((dpe::bcm_scan_refine_kernel<LP, CP, CV>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.level, a.K, a.maxK, a.lp, a.keys, a.oob,
-                       a.prevKeys, a.centres, a.prevCentres, a.clr, a.clrN);
-}
 
 static void launch_refine(bool clampP, bool clampV, const RefineLaunch &a)
 {
-#define DPE_REFINE_PICK(CP, CV) do { if (a.lp == 1) launch_refine3<1, CP, CV>(a); else if (a.lp == 2) launch_refine3<2, CP, CV>(a); \
-                                     else launch_refine3<0, CP, CV>(a); } while (0)
-    if (clampP) { if (clampV) DPE_REFINE_PICK(true, true); else DPE_REFINE_PICK(true, false); }
-    else { if (clampV) DPE_REFINE_PICK(false, true); else DPE_REFINE_PICK(false, false); }
-#undef DPE_REFINE_PICK
+    scan_dispatch(a.lp, clampP, clampV, false, [&](auto LP, auto CP, auto CV, auto) {
+        hipLaunchKernelGGL((dpe::bcm_scan_refine_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV)>), a.grid, dim3(256), a.lds, a.st, a.sp, a.sv, a.level, a.K, a.maxK, a.lp,
+                           a.keys, a.oob, a.prevKeys, a.centres, a.prevCentres, a.clr, a.clrN);
+    });
 }
 
-template <int LP>
 static void allow_big_lds_refine()
 {
-#define DPE_REFINE_LDS(CP, CV) (void)hipFuncSetAttribute((const void *)dpe::bcm_scan_refine_kernel<LP, CP, CV>, \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024)
-    DPE_REFINE_LDS(true, true); DPE_REFINE_LDS(true, false); DPE_REFINE_LDS(false, true); DPE_REFINE_LDS(false, false);
-#undef DPE_REFINE_LDS
+    scan_every_variant(false, [](auto LP, auto CP, auto CV, auto) { big_lds(dpe::bcm_scan_refine_kernel<DPE_V(LP), DPE_V(CP), DPE_V(CV)>); });
 }
+
+#undef DPE_V
 
 // ---- referencePair mode ---------------------------------------------------------------------
 // The reference forms the neighbour pair as floor(idx) and floor(idx + 1) on idx = base + S k (batchcorrmanifold.cu:1797-1799).
@@ -1204,10 +958,7 @@ static int bcm_finish_create(dpe_bcm *h, const dpe_bcm_config *cfg, dpe_bcm **ou
         return -1;
     }
     // dynamic LDS above 64 KB needs the opt-in attribute
-    allow_big_lds<0, true, true>();  allow_big_lds<1, true, true>();  allow_big_lds<2, true, true>();
-    allow_big_lds<0, false, true>(); allow_big_lds<1, false, true>(); allow_big_lds<2, false, true>();
-    allow_big_lds<0, true, false>();  allow_big_lds<1, true, false>();  allow_big_lds<2, true, false>();
-    allow_big_lds<0, false, false>(); allow_big_lds<1, false, false>(); allow_big_lds<2, false, false>();
+    allow_big_lds_scan();
     if (h->refPair &&
         hipHostMalloc((void **)&h->refBank_h, W * K * (size_t)(2 * cfg->lagHalfWidth + 1) * sizeof(float2), hipHostMallocDefault) != hipSuccess) {
         set_error("[BatchCorrManifold] create: host allocation failed");
@@ -1356,7 +1107,7 @@ int dpe_bcm_create_joint(const dpe_bcm_config *cfg, int32_t maxRx, int32_t maxCh
     }
     h->own_h.assign(4 * n, 0ull);
     h->jwin_h.resize(n);
-    allow_big_lds_joint<0>(); allow_big_lds_joint<1>(); allow_big_lds_joint<2>();
+    allow_big_lds_joint();
     *out = h;
     return 0;
 }
@@ -1391,7 +1142,7 @@ int dpe_bcm_create_epochs(const dpe_bcm_config *cfg, int32_t maxEpochs, int32_t 
     h->epochs = true;
     h->epMaxEpochs = maxEpochs;
     h->epPairsPerPass = (pairsPerPass > 0 && (size_t)pairsPerPass < budget) ? pairsPerPass : (int)budget;
-    allow_big_lds_epochs<0>(); allow_big_lds_epochs<1>(); allow_big_lds_epochs<2>();
+    allow_big_lds_epochs();
     *out = h;
     return 0;
 }
@@ -1432,7 +1183,7 @@ int dpe_bcm_create_subsets(const dpe_bcm_config *cfg, int32_t maxSubsets, dpe_bc
     h->subMax = maxSubsets;
     h->sub_h.assign(n, 0ull);
     h->subMask_h.assign(W * (size_t)maxSubsets, 0ull);
-    allow_big_lds_subsets<0>(); allow_big_lds_subsets<1>(); allow_big_lds_subsets<2>();
+    allow_big_lds_subsets();
     *out = h;
     return 0;
 }
@@ -1518,7 +1269,7 @@ int dpe_bcm_create_axes_sharing(const dpe_bcm_config *cfg, const dpe_grid_axes *
             return -1;
         }
     }
-    allow_big_lds_axes<0>(); allow_big_lds_axes<1>(); allow_big_lds_axes<2>();
+    allow_big_lds_axes();
     return bcm_finish_create(h, cfg, out);
 }
 
@@ -1635,7 +1386,7 @@ int dpe_bcm_create_refine(const dpe_bcm_config *cfg, int32_t nLevels, const dpe_
         return -1;
     }
     h->rfKeys_h.assign(4 * W * (size_t)nLevels, 0ull);
-    allow_big_lds_refine<0>(); allow_big_lds_refine<1>(); allow_big_lds_refine<2>();
+    allow_big_lds_refine();
     *out = h;
     return 0;
 }

@@ -13,6 +13,9 @@
 // scores stay in VGPRs across the SV loop.  A tile is 256 rows x one chunk; tiles are numbered row group major, so a lane meets
 // its points in increasing index order (a strict "greater" keeps the first maximum).  Score rows go out through a per-wave LDS
 // stage as runs of consecutive floats (non-temporal stores), not at the lane's dimT-float stride.
+// The bank fill, the row index, the recount test, the key and the reductions are scan_body's pieces (dpe_bcm_pieces.h;
+// DESIGN.md 2.4a); the per-point term stands in the SV loop as text (through scan_term the four general-power weighted-mean
+// variants take one more VGPR).
 #pragma once
 
 namespace dpe {
@@ -42,7 +45,6 @@ template <int LP, bool SECOND, bool CLAMP, bool WMEAN>
 __device__ __forceinline__ void axes_body(const AxesSide &sd, int inl, int K, int maxK, int lpower, unsigned long long *__restrict__ keys,
                                           unsigned long long *__restrict__ oob, int keyStride, int keySlot)
 {
-    const float2 *__restrict__ bank = sd.bank;
     const float *__restrict__ axX = sd.ax + sd.offX;
     const float *__restrict__ axY = sd.ax + sd.offY;
     const float *__restrict__ axZ = sd.ax + sd.offZ;
@@ -50,24 +52,14 @@ __device__ __forceinline__ void axes_body(const AxesSide &sd, int inl, int K, in
     const int nEnt = sd.nEnt, dimT = sd.dimT;
     const unsigned nBlkX = (unsigned)sd.split;
     extern __shared__ __align__(16) unsigned char smem[];
-    float4 *sE = reinterpret_cast<float4 *>(smem);   // [K][nEnt] {A, B, 0, C}, as scan_body
+    float4 *sE = reinterpret_cast<float4 *>(smem);   // [K][nEnt] {A, B, 0, C} (scan_fill_bank)
     __shared__ unsigned long long sKey[4];
     __shared__ unsigned int sOob[4];
     __shared__ double sW[4][5];
 
     const int w = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     float *stg = reinterpret_cast<float *>(smem + (size_t)K * nEnt * sizeof(float4)) + (tid >> 6) * 64 * kAxStage;   // this wave's stage
-    const float2 *bw = bank + (size_t)w * maxK * nEnt;
-    for (int i = tid; i < K * nEnt; i += 256) {
-        const int k = i / nEnt, j = i - k * nEnt;
-        if (j + 1 < nEnt) {   // |c0 + w (c1 - c0)|^2 = A + w (B + w C); entry nEnt - 1 is the all-zero clamp slot
-            const float2 c0 = bw[(size_t)k * nEnt + j], c1 = bw[(size_t)k * nEnt + j + 1];
-            const float dr = c1.x - c0.x, di = c1.y - c0.y;
-            sE[i] = make_float4(c0.x * c0.x + c0.y * c0.y, 2.f * (c0.x * dr + c0.y * di), 0.f, dr * dr + di * di);
-        } else {
-            sE[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
+    scan_fill_bank(sE, sd.bank + (size_t)w * maxK * nEnt, K * nEnt, nEnt, tid);
     __syncthreads();
 
     const unsigned last = (unsigned)(nEnt - 1);
@@ -102,13 +94,7 @@ __device__ __forceinline__ void axes_body(const AxesSide &sd, int inl, int K, in
         for (int k = 0; k < K; ++k) {
             const BcmSvDev s = svw[k];
             const float4 *bk = sE + k * nEnt;
-            float b;
-            if (SECOND) {
-                const float a = fmaf(z, s.uu, fmaf(y, s.un, x * s.ue));
-                b = fmaf(fmaf(fmaf(-a, a, q), s.h, -a), s.g, s.idx0);
-            } else {
-                b = fmaf(z, -s.pad1, fmaf(y, -s.pad0, fmaf(x, -s.h, s.idx0)));
-            }
+            const float b = axes_row_index<SECOND>(x, y, z, q, s);
 #pragma unroll
             for (int p = 0; p < kPairs; ++p) {
                 const f2 idx = __builtin_elementwise_fma(tp[p], f2{s.g, s.g}, f2{b, b});
@@ -142,17 +128,7 @@ __device__ __forceinline__ void axes_body(const AxesSide &sd, int inl, int K, in
                 const float t = axT[t0 + it];
                 for (int k = 0; k < K; ++k) {
                     const BcmSvDev s = svw[k];
-                    float b;
-                    if (SECOND) {
-                        const float a = fmaf(z, s.uu, fmaf(y, s.un, x * s.ue));
-                        b = fmaf(fmaf(fmaf(-a, a, q), s.h, -a), s.g, s.idx0);
-                    } else {
-                        b = fmaf(z, -s.pad1, fmaf(y, -s.pad0, fmaf(x, -s.h, s.idx0)));
-                    }
-                    const float id = fmaf(t, s.g, b);
-                    int ei;
-                    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ei) : "v"(id));
-                    nOob += (min((unsigned)ei, last) == last) ? 1u : 0u;
+                    nOob += scan_oob(fmaf(t, s.g, axes_row_index<SECOND>(x, y, z, q, s)), last) ? 1u : 0u;
                 }
             }
         }
@@ -183,15 +159,8 @@ __device__ __forceinline__ void axes_body(const AxesSide &sd, int inl, int K, in
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
     }
-    unsigned long long best = bestSc < 0.f ? 0ull
-                                           : (((unsigned long long)__float_as_uint(bestSc) << 32) | (unsigned long long)(0xFFFFFFFFu - bestIdx));
-    // block arg-max: larger score wins, ties -> smaller global index (thrust::max_element, :2589)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off, 64);
-        best = o > best ? o : best;
-        nOob += __shfl_xor(nOob, off, 64);
-    }
+    const unsigned long long best = wave_max_key(pack_key(bestSc, bestIdx));
+    nOob = wave_sum(nOob);
     double ws[5] = {(double)w0, (double)w1, (double)w2, (double)w3, (double)w4};
     if (WMEAN) {
 #pragma unroll
@@ -209,20 +178,13 @@ __device__ __forceinline__ void axes_body(const AxesSide &sd, int inl, int K, in
     }
     __syncthreads();
     if (tid == 0) {
-        unsigned long long b = sKey[0];
-        b = sKey[1] > b ? sKey[1] : b;
-        b = sKey[2] > b ? sKey[2] : b;
-        b = sKey[3] > b ? sKey[3] : b;
-        // returning atomics, waited for before the block's ticket (see scan_body)
-        unsigned long long seen = atomicMax(&keys[(size_t)w * keyStride + keySlot], b);
         if (WMEAN) {
             double *o = sd.wsum + ((size_t)w * nBlkX + blockIdx.x) * 5;
 #pragma unroll
             for (int j = 0; j < 5; ++j) o[j] = ((sW[0][j] + sW[1][j]) + sW[2][j]) + sW[3][j];
         }
-        const unsigned int n = sOob[0] + sOob[1] + sOob[2] + sOob[3];
-        if (n) seen += atomicAdd(&oob[(size_t)w * keyStride + keySlot], (unsigned long long)n);
-        asm volatile("" ::"v"(seen) : "memory");
+        scan_post_key(&keys[(size_t)w * keyStride + keySlot], &oob[(size_t)w * keyStride + keySlot], block_max_key(sKey),
+                      sOob[0] + sOob[1] + sOob[2] + sOob[3]);
     }
 }
 

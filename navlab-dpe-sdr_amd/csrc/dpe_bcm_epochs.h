@@ -7,9 +7,10 @@
 // own centre, ENU->ECEF matrix, receive time, channel ends and bank rows, laid out as dpe_bcm_update takes them, so the
 // (window, SV) coefficients and banks of group g are rows (g nEpochs + e) maxK + k of the arrays of a plain batch.
 //
-// What the kernel keeps from scan_body: both manifolds in one launch, the persistent tile loop with double-buffered buffer loads
-// of scan_grid_slot tiles, the {A, B, 0, C} LDS entries, the packed-fp32 index math, the clamp variants, the ragged last tile and
-// the fused first-maximum key.  What is new:
+// The kernel is scan_body's (both manifolds in one launch, the tile walk, the LDS entries, the index math, the clamp variants, the
+// ragged tile, the fused key).  The tile load, the tile walk, the bank fill, the key and the reductions are the shared pieces
+// (dpe_bcm_pieces.h); the tile body stands here as text, scan_body's operation for operation: written from
+// the pieces its tile loop waits for each of the four running-score loads on its own.  What is new:
 //  * the per-(window, SV) coefficients come from the device array through wave-uniform (scalar) loads, so the number of pairs
 //    is bounded by the LDS alone;
 //  * PASSES: the group's windows are cut into runs of winPerPass whole windows whose banks fit the LDS together.  A block fills
@@ -40,17 +41,10 @@ __device__ __forceinline__ void epochs_body(const ScanSide &sd, int nEpochs, int
 
     const int grp = blockIdx.y, tid = threadIdx.x;
     const int w0 = grp * nEpochs;                                            // the group's first window
-    constexpr int kPairs = kPtsPerThread / 2;
     const unsigned nFull = (unsigned)(G / kPtsPerBlock);
     const unsigned nTiles = (unsigned)((G + kPtsPerBlock - 1) / kPtsPerBlock);
     f4 bufA[2 * kPairs], bufB[2 * kPairs];
-    const auto load = [&](f4 (&g)[2 * kPairs], unsigned tile) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<f4 *>(grid + (size_t)tile * kPtsPerBlock), 0, kPtsPerBlock * (int)sizeof(f4), 0x00020000);
-#pragma unroll
-        for (int j = 0; j < 2 * kPairs; ++j)
-            g[j] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, tid * (int)sizeof(f4), j * 256 * (int)sizeof(f4), 0));
-    };
+    const auto load = [&](f4 (&g)[2 * kPairs], unsigned tile) { scan_load_tile(g, grid, tile, tid); };
     const unsigned last = (unsigned)(nEnt - 1);
     const float2 *__restrict__ bankG = sd.bank + (size_t)w0 * maxK * nEnt;   // the group's bank rows
     const BcmSvDev *__restrict__ svG = sd.sv + (size_t)w0 * maxK;            // wave-uniform -> scalar loads
@@ -66,21 +60,7 @@ __device__ __forceinline__ void epochs_body(const ScanSide &sd, int nEpochs, int
         if (blockIdx.x < nTiles) load(bufA, blockIdx.x);
         if (!first) __syncthreads();                                         // the previous pass's banks have been read by every wave
         const int rowLen = K * nEnt;
-        for (int e = 0; e < nw; ++e) {
-            const float2 *__restrict__ bw = bankG + (size_t)(e0 + e) * maxK * nEnt;
-            float4 *dst = sE + (size_t)e * rowLen;
-            for (int i = tid; i < rowLen; i += 256) {
-                const int k = i / nEnt, j = i - k * nEnt;
-                if (j + 1 < nEnt) {      // (entry nEnt - 1 is the all-zero slot out-of-window indices are clamped to)
-                    const float2 c0 = bw[(size_t)k * nEnt + j], c1 = bw[(size_t)k * nEnt + j + 1];
-                    const float dr = c1.x - c0.x, di = c1.y - c0.y;
-                    const float eA = c0.x * c0.x + c0.y * c0.y, eB = 2.f * (c0.x * dr + c0.y * di), eC = dr * dr + di * di;
-                    dst[i] = make_float4(eA, eB, 0.f, eC);
-                } else {
-                    dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            }
-        }
+        for (int e = 0; e < nw; ++e) scan_fill_bank(sE + (size_t)e * rowLen, bankG + (size_t)(e0 + e) * maxK * nEnt, rowLen, nEnt, tid);
         __syncthreads();
 
         const auto tile_body = [&](const f4 (&g)[2 * kPairs], unsigned tile, auto raggedTag) {
@@ -199,47 +179,14 @@ __device__ __forceinline__ void epochs_body(const ScanSide &sd, int nEpochs, int
         };
         // the tile walk of scan_body; tile n of this block is blockIdx.x + n nBlkX in every pass
         unsigned tile = blockIdx.x;
-        for (;;) {
-            if (tile >= nFull) break;
-            const unsigned t1 = tile + nBlkX;
-            if (t1 < nTiles) load(bufB, t1);
-            tile_body(bufA, tile, std::false_type{});
-            tile = t1;
-            if (tile >= nFull) {
-#pragma unroll
-                for (int j = 0; j < 2 * kPairs; ++j) bufA[j] = bufB[j];   // (once per pass, for the ragged tile below)
-                break;
-            }
-            const unsigned t2 = tile + nBlkX;
-            if (t2 < nTiles) load(bufA, t2);
-            tile_body(bufB, tile, std::false_type{});
-            tile = t2;
-        }
-        if (tile < nTiles) tile_body(bufA, tile, std::true_type{});
+        scan_walk_tiles(tile, nBlkX, nFull, nTiles, bufA, bufB, load, tile_body);
     }
 
-    const unsigned int bestIdx = bestTile * (unsigned int)kPtsPerBlock + bestIt * 256u + (unsigned int)tid;
-    unsigned long long best = bestSc < 0.f ? 0ull
-                                           : (((unsigned long long)__float_as_uint(bestSc) << 32) | (unsigned long long)(0xFFFFFFFFu - bestIdx));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off, 64);
-        best = o > best ? o : best;
-        nOob += __shfl_xor(nOob, off, 64);
-    }
+    const unsigned long long best = wave_max_key(pack_key(bestSc, scan_local_index(bestTile, bestIt, tid)));
+    nOob = wave_sum(nOob);
     if ((tid & 63) == 0) { sKey[tid >> 6] = best; sOob[tid >> 6] = nOob; }
     __syncthreads();
-    if (tid == 0) {
-        unsigned long long b = sKey[0];
-        b = sKey[1] > b ? sKey[1] : b;
-        b = sKey[2] > b ? sKey[2] : b;
-        b = sKey[3] > b ? sKey[3] : b;
-        // RETURNING atomics, waited for before this block takes its ticket (see scan_body / scan_publish)
-        unsigned long long seen = atomicMax(&keys[(size_t)grp * 2 + keySlot], b);
-        const unsigned int n = sOob[0] + sOob[1] + sOob[2] + sOob[3];
-        if (n) seen += atomicAdd(&oob[(size_t)grp * 2 + keySlot], (unsigned long long)n);
-        asm volatile("" ::"v"(seen) : "memory");
-    }
+    if (tid == 0) scan_post_key(&keys[(size_t)grp * 2 + keySlot], &oob[(size_t)grp * 2 + keySlot], block_max_key(sKey), sOob[0] + sOob[1] + sOob[2] + sOob[3]);
 }
 
 // Both manifolds in one launch, as bcm_scan_kernel: blockIdx.z = 0 position, 1 velocity, blockIdx.y = group; clears the next

@@ -6,9 +6,9 @@
 // offset j" (PyGNSS' multi receiver mode, receiver.py:266-274,337-345,385-388, with gX_r = X_r + offsets).  The joint score of a
 // point is the sum over receivers of the score scan_body would give that receiver there; its first maximum is the joint ML offset.
 //
-// What the kernel keeps from scan_body: both manifolds in one launch, the persistent tile loop with double-buffered buffer loads
-// of scan_grid_slot tiles, the {A, B, 0, C} LDS entries, the packed-fp32 index math, the clamp variants, the ragged last tile and
-// the fused first-maximum key.  What is new:
+// The kernel is scan_body's (both manifolds in one launch, the tile walk, the LDS entries, the index math, the clamp variants, the
+// ragged tile, the fused key), written from the same pieces (dpe_bcm_pieces.h) except the out-of-window
+// recount, which stands here as text (through scan_recount two general-power variants take 1 to 3 more VGPRs).  What is new:
 //  * the LDS fill reads each receiver's banks through that receiver's own pointers (JointRxDev), rows kOff .. kOff + nChan - 1;
 //  * the per-(receiver, SV) coefficients come from a device array through wave-uniform (scalar) loads -- 64 channels x 2
 //    manifolds x 32 B would be the whole kernel-argument segment;
@@ -44,41 +44,20 @@ __device__ __forceinline__ void joint_body(const ScanSide &sd, const JointRxDev 
     const int nEnt = sd.nEnt;
     const unsigned nBlkX = (unsigned)sd.split;
     extern __shared__ __align__(16) unsigned char smem[];
-    float4 *sE = reinterpret_cast<float4 *>(smem);                           // [sum K][nEnt] entries {A, B, 0, C} (see scan_body)
+    float4 *sE = reinterpret_cast<float4 *>(smem);                           // [sum K][nEnt] entries {A, B, 0, C} (scan_fill_bank)
     __shared__ unsigned long long sKey[4];
     __shared__ unsigned long long sOwnKey[4][kJointMaxRx];
     __shared__ unsigned int sOwnOob[4][kJointMaxRx];
 
     const int w = blockIdx.y, tid = threadIdx.x;
-    constexpr int kPairs = kPtsPerThread / 2;
     const unsigned nFull = (unsigned)(G / kPtsPerBlock);
     const unsigned nTiles = (unsigned)((G + kPtsPerBlock - 1) / kPtsPerBlock);
     f4 bufA[2 * kPairs], bufB[2 * kPairs];
-    const auto load = [&](f4 (&g)[2 * kPairs], unsigned tile) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<f4 *>(grid + (size_t)tile * kPtsPerBlock), 0, kPtsPerBlock * (int)sizeof(f4), 0x00020000);
-#pragma unroll
-        for (int j = 0; j < 2 * kPairs; ++j)
-            g[j] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, tid * (int)sizeof(f4), j * 256 * (int)sizeof(f4), 0));
-    };
+    const auto load = [&](f4 (&g)[2 * kPairs], unsigned tile) { scan_load_tile(g, grid, tile, tid); };
     if (blockIdx.x < nTiles) load(bufA, blockIdx.x);
     const JointRxDev *__restrict__ rxw = rx + (size_t)w * maxRx;             // wave-uniform -> scalar loads
-    for (int r = 0; r < nRx; ++r) {
-        const float2 *__restrict__ bw = SECOND ? rxw[r].code : rxw[r].carr;
-        float4 *dst = sE + (size_t)rxw[r].kOff * nEnt;
-        const int n = rxw[r].nChan * nEnt;
-        for (int i = tid; i < n; i += 256) {
-            const int k = i / nEnt, j = i - k * nEnt;
-            if (j + 1 < nEnt) {      // (entry nEnt - 1 is the all-zero slot out-of-window indices are clamped to)
-                const float2 c0 = bw[(size_t)k * nEnt + j], c1 = bw[(size_t)k * nEnt + j + 1];
-                const float dr = c1.x - c0.x, di = c1.y - c0.y;
-                const float eA = c0.x * c0.x + c0.y * c0.y, eB = 2.f * (c0.x * dr + c0.y * di), eC = dr * dr + di * di;
-                dst[i] = make_float4(eA, eB, 0.f, eC);
-            } else {
-                dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-    }
+    for (int r = 0; r < nRx; ++r)
+        scan_fill_bank(sE + (size_t)rxw[r].kOff * nEnt, SECOND ? rxw[r].code : rxw[r].carr, rxw[r].nChan * nEnt, nEnt, tid);
     __syncthreads();
 
     const unsigned last = (unsigned)(nEnt - 1);
@@ -94,13 +73,11 @@ __device__ __forceinline__ void joint_body(const ScanSide &sd, const JointRxDev 
     const auto tile_body = [&](const f4 (&g)[2 * kPairs], unsigned tile, auto raggedTag) {
         constexpr bool RAGGED = decltype(raggedTag)::value;
         const long long base = (long long)tile * kPtsPerBlock + tid;   // (ragged tile only)
-        f2 dx[kPairs], dy[kPairs], dz[kPairs], dw[kPairs], q[kPairs], score[kPairs];
+        ScanPts pt;
+        scan_unpack(pt, g);
+        f2 score[kPairs];
 #pragma unroll
-        for (int p = 0; p < kPairs; ++p) {
-            dx[p] = g[2 * p].xy; dy[p] = g[2 * p].zw; dz[p] = g[2 * p + 1].xy; dw[p] = g[2 * p + 1].zw;
-            q[p] = dx[p] * dx[p] + dy[p] * dy[p] + dz[p] * dz[p];
-            score[p] = f2{0.f, 0.f};
-        }
+        for (int p = 0; p < kPairs; ++p) score[p] = f2{0.f, 0.f};
 #pragma unroll
         for (int r = 0; r < kJointMaxRx; ++r) {
             if (r >= nRx) break;
@@ -114,49 +91,14 @@ __device__ __forceinline__ void joint_body(const ScanSide &sd, const JointRxDev 
                 const BcmSvDev s = svw[k0 + k];
                 const float4 *bk = sE + (k0 + k) * nEnt;
 #pragma unroll
-                for (int p = 0; p < kPairs; ++p) {
-                    f2 idx;
-                    if (SECOND) {
-                        f2 a = dx[p] * s.ue;
-                        a = __builtin_elementwise_fma(dy[p], f2{s.un, s.un}, a);
-                        a = __builtin_elementwise_fma(dz[p], f2{s.uu, s.uu}, a);
-                        f2 x = dw[p] - a;
-                        const f2 t = __builtin_elementwise_fma(-a, a, q[p]);          // q - a^2
-                        x = __builtin_elementwise_fma(t, f2{s.h, s.h}, x);             // + (q - a^2) / (2 range)
-                        idx = __builtin_elementwise_fma(x, f2{s.g, s.g}, f2{s.idx0, s.idx0});
-                    } else {
-                        idx = __builtin_elementwise_fma(dw[p], f2{s.g, s.g}, f2{s.idx0, s.idx0});
-                        idx = __builtin_elementwise_fma(dx[p], f2{-s.h, -s.h}, idx);
-                        idx = __builtin_elementwise_fma(dy[p], f2{-s.pad0, -s.pad0}, idx);
-                        idx = __builtin_elementwise_fma(dz[p], f2{-s.pad1, -s.pad1}, idx);
-                    }
-                    float c[2];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const float id = idx[j];
-                        const float wgt = __builtin_amdgcn_fractf(id);                 // id - floor(id)
-                        int ei;
-                        asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ei) : "v"(id));          // (int)floor(id), saturating
-                        unsigned e = (unsigned)ei;
-                        if (CLAMP) {                                                   // negative -> huge -> zero slot
-                            e = min(e, last);
-                            emax = max(emax, e);
-                        }
-                        const float2 ab = *reinterpret_cast<const float2 *>(&bk[e]);
-                        const float m2 = fmaf(wgt, fmaf(wgt, bk[e].w, ab.y), ab.x);
-                        if (LP == 1) c[j] = __builtin_amdgcn_sqrtf(__builtin_fabsf(m2));    // raw v_sqrt_f32 (1 ulp)
-                        else if (LP == 2) c[j] = m2;
-                        else c[j] = powf(__builtin_amdgcn_sqrtf(__builtin_fabsf(m2)), (float)lpower);
-                    }
-                    own[p] += f2{c[0], c[1]};
-                }
+                for (int p = 0; p < kPairs; ++p) own[p] += scan_pair_term<LP, SECOND, CLAMP>(pt, p, s, bk, last, emax, lpower);
             }
-            // out-of-window bookkeeping off the fast path, per receiver (see scan_body)
+            // out-of-window bookkeeping off the fast path, per receiver
             if (CLAMP && emax == last) {
                 for (int it = 0; it < kPtsPerThread; ++it) {
                     if (RAGGED && base + it * 256 >= G) continue;
-                    const float px = dx[it >> 1][it & 1], py = dy[it >> 1][it & 1], pz = dz[it >> 1][it & 1];
-                    const float pw = dw[it >> 1][it & 1], pq = q[it >> 1][it & 1];
+                    const float px = pt.dx[it >> 1][it & 1], py = pt.dy[it >> 1][it & 1], pz = pt.dz[it >> 1][it & 1];
+                    const float pw = pt.dw[it >> 1][it & 1], pq = pt.q[it >> 1][it & 1];
                     for (int k = 0; k < K; ++k) {
                         const BcmSvDev s = svw[k0 + k];
                         float id;
@@ -165,7 +107,7 @@ __device__ __forceinline__ void joint_body(const ScanSide &sd, const JointRxDev 
                             float x = pw - a;
                             x = fmaf(fmaf(-a, a, pq), s.h, x);
                             id = fmaf(x, s.g, s.idx0);
-                        } else {   // the fast path's own expression, operation for operation
+                        } else {
                             id = fmaf(pz, -s.pad1, fmaf(py, -s.pad0, fmaf(px, -s.h, fmaf(pw, s.g, s.idx0))));
                         }
                         int ei;
@@ -176,73 +118,27 @@ __device__ __forceinline__ void joint_body(const ScanSide &sd, const JointRxDev 
             }
 #pragma unroll
             for (int p = 0; p < kPairs; ++p) score[p] += own[p];
-            if (OWN) {
-#pragma unroll
-                for (int it = 0; it < kPtsPerThread; ++it) {
-                    const float sc = own[it >> 1][it & 1];
-                    if ((!RAGGED || base + it * 256 < G) && sc > ownSc[r]) { ownSc[r] = sc; ownAt[r] = tile * (unsigned)kPtsPerThread + (unsigned)it; }
-                }
-            }
+            if (OWN) scan_track_max<RAGGED>(own, base, G, tile, ownSc[r], ownAt[r]);
         }
-        if (scores) {   // written once, never read back on this path: non-temporal (see scan_body)
-            float *srow = scores + (size_t)w * sd.pitch + (size_t)tile * kPtsPerBlock;   // wave-uniform
-#pragma unroll
-            for (int it = 0; it < kPtsPerThread; ++it)
-                if (!RAGGED || base + it * 256 < G) __builtin_nontemporal_store(score[it >> 1][it & 1], &srow[it * 256 + tid]);
-        }
-#pragma unroll
-        for (int it = 0; it < kPtsPerThread; ++it) {
-            const float sc = score[it >> 1][it & 1];
-            if ((!RAGGED || base + it * 256 < G) && sc > bestSc) { bestSc = sc; bestTile = tile; bestIt = (unsigned)it; }
-        }
+        if (scores) scan_store_row<RAGGED>(scores + (size_t)w * sd.pitch + (size_t)tile * kPtsPerBlock, score, base, G, tid);
+        scan_track_max<RAGGED>(score, base, G, tile, bestSc, bestTile, bestIt);
     };
     unsigned tile = blockIdx.x;
-    for (;;) {
-        if (tile >= nFull) break;
-        const unsigned t1 = tile + nBlkX;
-        if (t1 < nTiles) load(bufB, t1);
-        tile_body(bufA, tile, std::false_type{});
-        tile = t1;
-        if (tile >= nFull) {
-#pragma unroll
-            for (int j = 0; j < 2 * kPairs; ++j) bufA[j] = bufB[j];   // (once per block, for the ragged tile below)
-            break;
-        }
-        const unsigned t2 = tile + nBlkX;
-        if (t2 < nTiles) load(bufA, t2);
-        tile_body(bufB, tile, std::false_type{});
-        tile = t2;
-    }
-    if (tile < nTiles) tile_body(bufA, tile, std::true_type{});
+    scan_walk_tiles(tile, nBlkX, nFull, nTiles, bufA, bufB, load, tile_body);
 
-    const auto make_key = [&](float sc, unsigned int localIdx) -> unsigned long long {
-        const unsigned int gi = (unsigned int)indexOffset + localIdx;
-        return sc < 0.f ? 0ull : (((unsigned long long)__float_as_uint(sc) << 32) | (unsigned long long)(0xFFFFFFFFu - gi));
-    };
-    unsigned long long best = make_key(bestSc, bestTile * (unsigned int)kPtsPerBlock + bestIt * 256u + (unsigned int)tid);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off, 64);
-        best = o > best ? o : best;
-    }
+    const unsigned int io = (unsigned int)indexOffset;
+    const unsigned long long best = wave_max_key(pack_key(bestSc, io + scan_local_index(bestTile, bestIt, tid)));
     if ((tid & 63) == 0) sKey[tid >> 6] = best;
 #pragma unroll
     for (int r = 0; r < kJointMaxRx; ++r) {
         if (r >= nRx) break;
         if (OWN) {
-            unsigned long long b = make_key(ownSc[r], (ownAt[r] / (unsigned)kPtsPerThread) * (unsigned int)kPtsPerBlock +
-                                                          (ownAt[r] % (unsigned)kPtsPerThread) * 256u + (unsigned int)tid);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long o = __shfl_xor(b, off, 64);
-                b = o > b ? o : b;
-            }
+            const unsigned long long b =
+                wave_max_key(pack_key(ownSc[r], io + scan_local_index(ownAt[r] / (unsigned)kPtsPerThread, ownAt[r] % (unsigned)kPtsPerThread, tid)));
             if ((tid & 63) == 0) sOwnKey[tid >> 6][r] = b;
         }
         if (CLAMP) {
-            unsigned int n = nOob[r];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+            const unsigned int n = wave_sum(nOob[r]);
             if ((tid & 63) == 0) sOwnOob[tid >> 6][r] = n;
         }
     }
@@ -252,13 +148,7 @@ __device__ __forceinline__ void joint_body(const ScanSide &sd, const JointRxDev 
     unsigned int nMine = 0;
     if (tid < nRx) {
         const size_t slot = ((size_t)w * 2 + keySlot) * maxRx + tid;
-        if (OWN) {
-            unsigned long long b = sOwnKey[0][tid];
-            b = sOwnKey[1][tid] > b ? sOwnKey[1][tid] : b;
-            b = sOwnKey[2][tid] > b ? sOwnKey[2][tid] : b;
-            b = sOwnKey[3][tid] > b ? sOwnKey[3][tid] : b;
-            atomicMax(&ownKeys[slot], b);
-        }
+        if (OWN) atomicMax(&ownKeys[slot], block_max_key(&sOwnKey[0][tid], kJointMaxRx));
         if (CLAMP) {
             nMine = sOwnOob[0][tid] + sOwnOob[1][tid] + sOwnOob[2][tid] + sOwnOob[3][tid];
             if (nMine) atomicAdd(&ownOob[slot], (unsigned long long)nMine);
@@ -268,16 +158,7 @@ __device__ __forceinline__ void joint_body(const ScanSide &sd, const JointRxDev 
 #pragma unroll
         for (int off = 4; off > 0; off >>= 1) nMine += __shfl_xor(nMine, off, 64);
     }
-    if (tid == 0) {
-        unsigned long long b = sKey[0];
-        b = sKey[1] > b ? sKey[1] : b;
-        b = sKey[2] > b ? sKey[2] : b;
-        b = sKey[3] > b ? sKey[3] : b;
-        // RETURNING atomics, waited for before this block takes its ticket (see scan_body / scan_publish)
-        unsigned long long seen = atomicMax(&keys[(size_t)w * 2 + keySlot], b);
-        if (CLAMP && nMine) seen += atomicAdd(&oob[(size_t)w * 2 + keySlot], (unsigned long long)nMine);
-        asm volatile("" ::"v"(seen) : "memory");
-    }
+    if (tid == 0) scan_post_key(&keys[(size_t)w * 2 + keySlot], &oob[(size_t)w * 2 + keySlot], block_max_key(sKey), CLAMP ? nMine : 0u);
 }
 
 // Both manifolds in one launch, as bcm_scan_kernel: blockIdx.z = 0 position, 1 velocity; clears the next Update's key set and

@@ -8,10 +8,8 @@
 //   3. forms the CENTRE, the fp32 point level l-1 scored there: level l-1's own centre (0 at level 0; kept in device memory by
 //      that level's launch) plus its axis values, each sum rounded once to fp32,
 //   4. scores its own axes grid at x = fl32(cx + axX[ix]), y, z, t likewise.
-// Everything behind the point is axes_body, operation for operation (the tile walk of 256 rows x one chunk of <= kAxT t entries,
-// q, a, B + g t, the {A, B, 0, C} lerp, |.|^L, the strict-greater first maximum, the recount of out-of-window pairs where a clamp
-// happened, the staged non-temporal score rows, returning atomics): level l of window w carries, bit for bit, the rows, key and
-// count of a dpe_bcm_create_axes handle whose axes are the fp32 values fl32(c + a_i).
+// Everything behind the point is axes_body, from the same pieces (dpe_bcm_pieces.h): level l of window w carries,
+// bit for bit, the rows, key and count of a dpe_bcm_create_axes handle whose axes are the fp32 values fl32(c + a_i).
 //
 // A key of 0 means that no point of the previous level had a score (every sum NaN); it would decode to index 2^32 - 1.  The
 // preamble tests for it (and for any index beyond the previous grid) before an axis is indexed: such a (window, manifold) is
@@ -68,7 +66,6 @@ __device__ __forceinline__ void refine_body(const RefineSide &sd, int level, int
         c[0] = cx; c[1] = cy; c[2] = cz; c[3] = ct;
     }
 
-    const float2 *__restrict__ bank = sd.bank;
     const float *__restrict__ axX = sd.ax + sd.offX;
     const float *__restrict__ axY = sd.ax + sd.offY;
     const float *__restrict__ axZ = sd.ax + sd.offZ;
@@ -76,22 +73,12 @@ __device__ __forceinline__ void refine_body(const RefineSide &sd, int level, int
     const int nEnt = sd.nEnt, dimT = sd.dimT;
     const unsigned nBlkX = (unsigned)sd.split;
     extern __shared__ __align__(16) unsigned char smem[];
-    float4 *sE = reinterpret_cast<float4 *>(smem);   // [K][nEnt] {A, B, 0, C}, as scan_body
+    float4 *sE = reinterpret_cast<float4 *>(smem);   // [K][nEnt] {A, B, 0, C} (scan_fill_bank)
     __shared__ unsigned long long sKey[4];
     __shared__ unsigned int sOob[4];
 
     float *stg = reinterpret_cast<float *>(smem + (size_t)K * nEnt * sizeof(float4)) + (tid >> 6) * 64 * kAxStage;   // this wave's stage
-    const float2 *bw = bank + (size_t)w * maxK * nEnt;
-    for (int i = tid; i < K * nEnt; i += 256) {
-        const int k = i / nEnt, j = i - k * nEnt;
-        if (j + 1 < nEnt) {   // |c0 + w (c1 - c0)|^2 = A + w (B + w C); entry nEnt - 1 is the all-zero clamp slot
-            const float2 c0 = bw[(size_t)k * nEnt + j], c1 = bw[(size_t)k * nEnt + j + 1];
-            const float dr = c1.x - c0.x, di = c1.y - c0.y;
-            sE[i] = make_float4(c0.x * c0.x + c0.y * c0.y, 2.f * (c0.x * dr + c0.y * di), 0.f, dr * dr + di * di);
-        } else {
-            sE[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
+    scan_fill_bank(sE, sd.bank + (size_t)w * maxK * nEnt, K * nEnt, nEnt, tid);
     __syncthreads();
 
     const unsigned last = (unsigned)(nEnt - 1);
@@ -125,35 +112,13 @@ __device__ __forceinline__ void refine_body(const RefineSide &sd, int level, int
         for (int k = 0; k < K; ++k) {
             const BcmSvDev s = svw[k];
             const float4 *bk = sE + k * nEnt;
-            float b;
-            if (SECOND) {
-                const float a = fmaf(z, s.uu, fmaf(y, s.un, x * s.ue));
-                b = fmaf(fmaf(fmaf(-a, a, q), s.h, -a), s.g, s.idx0);
-            } else {
-                b = fmaf(z, -s.pad1, fmaf(y, -s.pad0, fmaf(x, -s.h, s.idx0)));
-            }
+            const float b = axes_row_index<SECOND>(x, y, z, q, s);
 #pragma unroll
             for (int p = 0; p < kPairs; ++p) {
                 const f2 idx = __builtin_elementwise_fma(tp[p], f2{s.g, s.g}, f2{b, b});
-                float cc[2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const float id = idx[j];
-                    const float wgt = __builtin_amdgcn_fractf(id);
-                    int ei;
-                    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ei) : "v"(id));   // (int)floor(id), saturating
-                    unsigned e = (unsigned)ei;
-                    if (CLAMP) {
-                        e = min(e, last);
-                        emax = max(emax, e);
-                    }
-                    const float2 ab = *reinterpret_cast<const float2 *>(&bk[e]);
-                    const float m2 = fmaf(wgt, fmaf(wgt, bk[e].w, ab.y), ab.x);
-                    if (LP == 1) cc[j] = __builtin_amdgcn_sqrtf(__builtin_fabsf(m2));
-                    else if (LP == 2) cc[j] = m2;
-                    else cc[j] = powf(__builtin_amdgcn_sqrtf(__builtin_fabsf(m2)), (float)lpower);
-                }
-                score[p] += f2{cc[0], cc[1]};
+                const float c0 = scan_term<LP, CLAMP>(idx[0], bk, last, emax, lpower);
+                const float c1 = scan_term<LP, CLAMP>(idx[1], bk, last, emax, lpower);
+                score[p] += f2{c0, c1};
             }
         }
         const unsigned gi0 = row * (unsigned)dimT + t0;   // index of the lane's slot 0 (fits 32 bits, checked at create)
@@ -165,17 +130,7 @@ __device__ __forceinline__ void refine_body(const RefineSide &sd, int level, int
                 const float t = ct + axT[t0 + it];
                 for (int k = 0; k < K; ++k) {
                     const BcmSvDev s = svw[k];
-                    float b;
-                    if (SECOND) {
-                        const float a = fmaf(z, s.uu, fmaf(y, s.un, x * s.ue));
-                        b = fmaf(fmaf(fmaf(-a, a, q), s.h, -a), s.g, s.idx0);
-                    } else {
-                        b = fmaf(z, -s.pad1, fmaf(y, -s.pad0, fmaf(x, -s.h, s.idx0)));
-                    }
-                    const float id = fmaf(t, s.g, b);
-                    int ei;
-                    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ei) : "v"(id));
-                    nOob += (min((unsigned)ei, last) == last) ? 1u : 0u;
+                    nOob += scan_oob(fmaf(t, s.g, axes_row_index<SECOND>(x, y, z, q, s)), last) ? 1u : 0u;
                 }
             }
         }
@@ -203,28 +158,13 @@ __device__ __forceinline__ void refine_body(const RefineSide &sd, int level, int
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
     }
-    unsigned long long best = bestSc < 0.f ? 0ull
-                                           : (((unsigned long long)__float_as_uint(bestSc) << 32) | (unsigned long long)(0xFFFFFFFFu - bestIdx));
-    // block arg-max: larger score wins, ties -> smaller index (thrust::max_element, :2589)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off, 64);
-        best = o > best ? o : best;
-        nOob += __shfl_xor(nOob, off, 64);
-    }
+    const unsigned long long best = wave_max_key(pack_key(bestSc, bestIdx));
+    nOob = wave_sum(nOob);
     if (lane == 0) { sKey[tid >> 6] = best; sOob[tid >> 6] = nOob; }
     __syncthreads();
-    if (tid == 0) {
-        unsigned long long b = sKey[0];
-        b = sKey[1] > b ? sKey[1] : b;
-        b = sKey[2] > b ? sKey[2] : b;
-        b = sKey[3] > b ? sKey[3] : b;
-        // returning atomics, as axes_body (the next level reads the key behind the kernel boundary)
-        unsigned long long seen = atomicMax(&keys[(size_t)w * 2 + keySlot], b);
-        const unsigned int n = sOob[0] + sOob[1] + sOob[2] + sOob[3];
-        if (n) seen += atomicAdd(&oob[(size_t)w * 2 + keySlot], (unsigned long long)n);
-        asm volatile("" ::"v"(seen) : "memory");
-    }
+    // (the next level reads the key behind the kernel boundary)
+    if (tid == 0)
+        scan_post_key(&keys[(size_t)w * 2 + keySlot], &oob[(size_t)w * 2 + keySlot], block_max_key(sKey), sOob[0] + sOob[1] + sOob[2] + sOob[3]);
 }
 
 // One level, both manifolds (blockIdx.z = 0 position, 1 velocity).  Level 0 also clears the key set of the NEXT Update (the two

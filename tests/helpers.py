@@ -117,7 +117,8 @@ def pack_gpu_inputs(case):
     return iq, cs, ce, bw
 
 
-def run_gpu(case, L, B, lpower=1, write_scores=True, weighted_mean=True, repeats=1, reference_pair=False):
+def run_gpu(case, L, B, lpower=1, write_scores=True, weighted_mean=True, repeats=1, reference_pair=False, split=None):
+    """split: the (position, velocity) blocks per window the test needs scan_split to give, asserted through last_split()."""
     import torch
     iq, cs, ce, bw = pack_gpu_inputs(case)
     W, K = cs.shape
@@ -134,6 +135,8 @@ def run_gpu(case, L, B, lpower=1, write_scores=True, weighted_mean=True, repeats
         bcs.Update(iq_d, cs)
         bcm.Update(bcs.CodeScores, bcs.CarrScores, bw, ce)
     res = bcm.results()
+    if split is not None:
+        assert bcm.last_split() == split, "scan_split gave %s, the test needs %s" % (bcm.last_split(), split)
     code, carr = bcs.read_banks()
     idx_next, no_flip, mean = bcs.read_info()
     out = dict(code=list(code), carr=list(carr), res=res, idx_next=idx_next, no_flip=no_flip, mean=mean)

@@ -2,36 +2,19 @@
 gfx950 assembly of dpe_bcm.hip: no scratch, no spills, and register counts that leave the scan kernels' occupancy (two
 256-thread blocks per CU need <= 128 VGPRs per lane for the LPower 1 / 2 variants).  Compiles with hipcc -S (no GPU
 needed); skips where hipcc is absent."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "navlab-dpe-sdr_amd", "csrc", "dpe_bcm.hip")
+from tests.isa_asm import asm_of
+
 KERNEL = "_ZN3dpe22bcm_scan_epochs_kernelILi%dELb%dELb%dEEE"
 VGPR_MAX = {1: 96, 2: 96, 0: 160}      # measured when this budget was set: 76 .. 87 (LPower 1), 80 .. 89 (2), 121 .. 140 (general powf)
 
 
-def _hipcc():
-    for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    hipcc = _hipcc()
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "dpe_bcm.s")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed",
-                           "-S", "--cuda-device-only", SRC, "-o", out], cwd=os.path.dirname(SRC),
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return open(out).read()
+def asm():
+    return asm_of("dpe_bcm.hip")
 
 
 def _descriptor(text, prefix):

@@ -177,6 +177,38 @@ def test_lpower_3_on_the_walk(walk, oracle):
         assert_against_oracle(world, out, G32 - 2 + d, d, E1_N, tol=1e-5, lpower=3, what="LPower 3, ")
 
 
+@pytest.fixture(scope="module", params=[True, False], ids=["clean", "narrow"])
+def walk_banks(request):
+    """E1's 15^4 / 14^4 shape (two distinct groups of 4 windows dealt into 32 groups) with widened banks and with deliberately
+    narrow ones (both manifolds clamp and recount)."""
+    world = ew.build(N=2 * E1_N, K=E1_K, seed=5, widen=request.param, **WALK["15x14"])
+    assert (tiles(world["pos"].shape[0]), tiles(world["vel"].shape[0])) == (50, 38)
+    banks = Banks(world, G32 * E1_N)
+    yield world, banks, request.param
+    banks.close()
+
+
+@pytest.mark.parametrize("lpower", [1, 2, 3])
+def test_walk_every_lpower_clean_and_clamped(walk_banks, lpower):
+    """E3 (fourth part).  Every (LPower, clamp) variant on the walk, in two passes: 24 blocks walk 50 and 38 tiles (the ragged
+    tile by the even path and through the bufB -> bufA copy), the second pass reads the running score back.  Rows are the
+    ordered sums of dpe_bcm_update's rows at the same power, the key the first maximum of the group's row, the counts the sums
+    of dpe_bcm_update's per-window counts: non-zero on both manifolds with narrow banks, zero with clean ones."""
+    world, banks, widen = walk_banks
+    out = run_epochs(world, banks, E1_N, pairs_per_pass=8, lpower=lpower, split=(24, 24), passes=2)
+    single = run_single(world, banks, lpower=lpower)
+    assert np.isfinite(out["pos"]).all() and np.isfinite(out["vel"]).all()
+    assert_rows_are_ordered_sums(out, single, E1_N)
+    for g in range(G32):
+        assert_key_is_first_maximum(out, g)
+        per = single["res"][g * E1_N:(g + 1) * E1_N]
+        for k in ("posOutOfWindow", "velOutOfWindow"):
+            assert out["res"][g][k] == sum(r[k] for r in per), (g, k)
+            assert all((r[k] > 0) == (not widen) for r in per), (g, k)
+        if widen:
+            assert out["res"][g]["posIndex"] == world["pos_at"] and out["res"][g]["velIndex"] == world["vel_at"], g
+
+
 @pytest.mark.parametrize("cut", [None, (1500, 1025)])
 def test_fewer_channels_than_the_handles_hold(oracle, cut):
     """E2.  BatchCorrScores, EpochManifold and BatchCorrManifold all created for 8 channels and fed K = 5: the banks lie

@@ -292,6 +292,46 @@ def test_lpower_3_and_own_keys_off(walk, oracle):
         check_against_oracle(world, pr, ref, d, tol=1e-5)
 
 
+@pytest.fixture(scope="module", params=[True, False], ids=["clean", "narrow"])
+def walk_banks(request):
+    """J1's 15^4 / 14^4 shape with widened banks and with deliberately narrow ones (both manifolds clamp and recount)."""
+    world = jw.build((5, 8, 4), seed=3, W=2, widen=request.param, **WALK["15x14"])
+    assert (tiles(world["pos"].shape[0]), tiles(world["vel"].shape[0])) == (50, 38)
+    banks = Banks(world, W32)
+    yield world, banks, request.param
+    banks.close()
+
+
+@pytest.mark.parametrize("lpower", [1, 2, 3])
+def test_walk_every_lpower_clean_and_clamped(walk_banks, oracle, lpower):
+    """J4b.  Every (LPower, clamp) variant on the walk: 24 blocks walk 50 and 38 tiles (block 1 of the position manifold the
+    tiles 1, 25 and the ragged 49; block 13 of the velocity manifold tile 13 and the ragged 37 through the copy).  Per receiver
+    the own arg-max, score bits and out-of-window counts are dpe_bcm_update's on that receiver alone at the same power, the
+    joint count is their sum, the joint key is the first maximum of the joint row; narrow banks count on both manifolds, clean
+    ones on neither.  LPower 2 on clean banks is also held to the oracle at TOL (LPower 1: J1, LPower 3: J4)."""
+    world, banks, widen = walk_banks
+    out = run_joint(world, banks.rx(), lpower=lpower, split=(24, 24))
+    assert_twins(out, 2)
+    singles = [run_single(world, banks, r, lpower=lpower) for r in range(3)]
+    assert all(s["split"] == (24, 24) for s in singles)
+    assert np.isfinite(out["pos"]).all() and np.isfinite(out["vel"]).all()
+    for w in range(W32):
+        j = out["res"][w]
+        assert_key_is_first_maximum(out, w)
+        for r in range(3):
+            assert_own_is_single(j["rx"][r], singles[r]["res"][w], (w, r))
+        for k in ("posOutOfWindow", "velOutOfWindow"):
+            assert j[k] == sum(x[k] for x in j["rx"]), (w, k)
+            assert (j[k] > 0) == (not widen), (w, k, j[k])
+        if widen:
+            assert j["posIndex"] == world["pos_at"] and j["velIndex"] == world["vel_at"], w
+    if widen and lpower == 2:
+        ref = jw.oracle_rows(world, lpower=2)
+        pr = probe(out, last_twins(world))
+        for d in range(2):
+            check_against_oracle(world, pr, ref, d)
+
+
 def check_clamped_side(world, out, ref, d, name, rname_x, rows):
     """The narrow manifold of distinct window d (out: its probe) by test_narrow_banks_clamp_path_counts_per_receiver's rule."""
     G = ref[rname_x][d].size

@@ -51,6 +51,32 @@ def test_ragged_sizes_against_oracle(G):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("clamped", [False, True])
+@pytest.mark.parametrize("lpower", [1, 2, 3])
+def test_batch_walk_against_oracle(lpower, clamped):
+    """A block that walks several tiles.  32 windows make scan_split deal 24 blocks per window and manifold; the position grid
+    is 49 tiles and 5 points, the velocity grid 37 tiles and 5 points.  Position block 1 scores tiles 1 and 25 from the two
+    register sets and leaves the loop at its head for the ragged tile 49; velocity block 13 scores tile 13 and reaches the
+    ragged tile 37 through the copy of the second register set into the first; position block 0 walks three full tiles.  Two
+    SVs, banks of +-4 entries; clamped: the clock offsets of both grids reach beyond the banks, so the clamped variants and the
+    recount of out-of-window pairs run on every tile.  The first three windows are held to the oracle (LPower 3: the generic
+    powf variant at test_gpu_parity's 1e-5), every window to the first maximum of its own rows."""
+    case = make_case(seed=61, S=12500, K=2, G=49 * 1024 + 5, vel_G=37 * 1024 + 5, W=32)
+    if clamped:
+        case["pos"][:, 3] *= 20.0    # +-2.6 km: +-22 samples against +-4 lags
+        case["vel"][:, 3] *= 400.0   # +-1.2 km/s: +-32 bins against +-4
+    gpu = run_gpu(case, 4, 4, lpower=lpower, split=(24, 24))
+    ref = run_oracle(case, 4, 4, lpower=lpower, windows=(0, 1, 2))
+    assert_parity(gpu, ref, tol=1e-5 if lpower == 3 else 2e-5)
+    for w in range(3):
+        assert (ref["res"][w]["posOutOfWindow"] > 0) == clamped and (ref["res"][w]["velOutOfWindow"] > 0) == clamped
+    for w in range(case["W"]):
+        r = gpu["res"][w]
+        assert r["posIndex"] == _first_max(gpu["pos"][w]) and r["velIndex"] == _first_max(gpu["vel"][w])
+        assert (r["posOutOfWindow"] > 0) == clamped and (r["velOutOfWindow"] > 0) == clamped
+
+
+@pytest.mark.gpu
 def test_duplicated_points_keep_the_first_maximum():
     """The grid twice over (plus a ragged tail of its first points): every copy of a point sits in another lane, slot or
     tile and must score the same bits; the arg-max must name the first copy; out-of-window counts scale with the copies."""

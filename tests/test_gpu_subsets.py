@@ -288,6 +288,40 @@ def test_batch_walk_with_ties(oracle):
         banks.close()
 
 
+@pytest.mark.parametrize("lpower,widen", [(1, False), (2, True), (2, False), (3, True), (3, False)])
+def test_batch_walk_lpower_and_clamped_variants(lpower, widen):
+    """4a for the other (LPower, clamp) variants (LPower 1 on clean banks is 4a itself): 32 windows, 24 blocks per window walk
+    50 and 38 tiles.  The full rows, keys and fixes are dpe_bcm_update's at the same power on every window; on three windows
+    every subset is an Update on its channels and the per-SV out-of-window counts are those of an Update on that SV alone:
+    non-zero on both manifolds with narrow banks, zero with clean ones."""
+    world = ew.build(N=8, K=4, seed=5, widen=widen, pos_dim=15, vel_dim=14)
+    assert (tiles(world["pos"].shape[0]), tiles(world["vel"].shape[0])) == (50, 38)
+    banks = Banks(world, 32)
+    masks = np.stack([np.roll(WALK_MASKS, w % 3) for w in range(32)])
+    ref = SubsetRef(world, banks, lpower=lpower)
+    try:
+        out = run_subsets(world, banks, masks, lpower=lpower, split=(24, 24))
+        full = run_full(world, banks, lpower=lpower)
+        assert_full_is_update(out, full, 32)
+        assert np.isfinite(out["pos"]).all() and np.isfinite(out["vel"]).all()
+        for w in range(32):
+            assert key_index(out["keys"][w, 0]) == int(np.argmax(out["pos"][w])) == out["res"][w]["posIndex"], w
+            assert key_index(out["keys"][w, 1]) == int(np.argmax(out["vel"][w])) == out["res"][w]["velIndex"], w
+        for w in (0, 13, 31):
+            for m, mask in enumerate(masks[w]):
+                assert_same_fix(out["res"][w]["subs"][m], ref.run(w, mask), (w, m, hex(int(mask))))
+            per = np.zeros((2, 4), dtype=np.int64)
+            for k in range(4):
+                r = ref.run(w, 1 << k)
+                per[0, k], per[1, k] = r["posOutOfWindow"], r["velOutOfWindow"]
+            assert np.array_equal(out["res"][w]["oobPerSv"], per), w
+            assert out["res"][w]["posOutOfWindow"] == per[0].sum() and out["res"][w]["velOutOfWindow"] == per[1].sum()
+            assert (per[0].sum() > 0) == (not widen) and (per[1].sum() > 0) == (not widen), (w, per.tolist())
+    finally:
+        ref.close()
+        banks.close()
+
+
 @pytest.mark.parametrize("side", [True, "L"])
 def test_one_window_walk_with_unequal_splits(oracle, side):
     """4b.  One window on a 20^4 position grid (157 tiles for 128 blocks) and a 7^4 velocity grid (3 tiles: 125 velocity blocks

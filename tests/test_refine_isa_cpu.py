@@ -4,38 +4,21 @@ pinned a few above what the build shows; VGPRs stay at or below 128 (four waves 
 Measured when this budget was set, over the four clamp variants: VGPRs 89 .. 104 (LPower 1), 99 .. 113 (LPower 2), 69 (general
 powf); SGPRs 100; static LDS 96 bytes (wave keys and counts).  Only kernel descriptors are read.  Compiles with hipcc -S (no GPU
 needed); skips where hipcc is absent."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "navlab-dpe-sdr_amd", "csrc", "dpe_bcm.hip")
+from tests.isa_asm import asm_of
+
 KERNEL = "_ZN3dpe22bcm_scan_refine_kernelILi%dELb%dELb%dEEE"
 VGPR_MAX = {1: 108, 2: 117, 0: 73}
 SGPR_MAX = 104
 LDS_MAX = 128
 
 
-def _hipcc():
-    for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    hipcc = _hipcc()
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa_refine") / "dpe_bcm.s")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed",
-                           "-S", "--cuda-device-only", SRC, "-o", out], cwd=os.path.dirname(SRC),
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return open(out).read()
+def asm():
+    return asm_of("dpe_bcm.hip")
 
 
 def _descriptor(text, prefix):

@@ -2,37 +2,20 @@
 dpe_bcm.hip and set against the point-cloud headline (bcm_scan_kernel<1, false, false, false, false>) in the same assembly:
 vector instructions per (point, SV) in the innermost (SV) loop of each manifold, registers, scratch.  Compiles with hipcc -S
 (no GPU needed); skips where hipcc is absent."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "navlab-dpe-sdr_amd", "csrc", "dpe_bcm.hip")
+from tests.isa_asm import asm_of
+
 AXES = "_ZN3dpe20bcm_scan_axes_kernelILi1ELb0ELb0ELb0EEE"
 POINTS = "_ZN3dpe15bcm_scan_kernelILi1ELb0ELb0ELb0ELb0EEE"
 PER_POINT_SV_MAX = 7.5
 
 
-def _hipcc():
-    for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    hipcc = _hipcc()
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa_axes") / "dpe_bcm.s")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed",
-                           "-S", "--cuda-device-only", SRC, "-o", out], cwd=os.path.dirname(SRC),
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return open(out).read()
+def asm():
+    return asm_of("dpe_bcm.hip")
 
 
 def _kernel_blocks(text, prefix):

@@ -1,15 +1,12 @@
 """Instruction budget of the headline scan variant (bcm_scan_kernel<1, false, false, false, false>), read from the gfx950
 assembly of dpe_bcm.hip: the vector instructions a full tile spends outside the per-SV loop, and no 64-bit compare in
 the full-tile loop.  Compiles with hipcc -S (no GPU needed); skips where hipcc is absent."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "navlab-dpe-sdr_amd", "csrc", "dpe_bcm.hip")
+from tests.isa_asm import asm_of
+
 HEADLINE = "_ZN3dpe15bcm_scan_kernelILi1ELb0ELb0ELb0ELb0EEE"
 # full-tile loop, vector instructions outside the SV loop, counted statically over the loop body (the loop holds two tiles;
 # cold blocks such as the K = 0 path and the hand-over to the ragged tile are included): 27 (velocity) / 33 (position)
@@ -18,23 +15,9 @@ VALU_PER_TILE_MAX = 36
 SV_LOOP_VALU_MAX = 41   # one SV of four points (position side; the velocity side needs 35)
 
 
-def _hipcc():
-    for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    hipcc = _hipcc()
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "dpe_bcm.s")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed",
-                           "-S", "--cuda-device-only", SRC, "-o", out], cwd=os.path.dirname(SRC),
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return open(out).read()
+def asm():
+    return asm_of("dpe_bcm.hip")
 
 
 def _kernel_blocks(text, prefix):

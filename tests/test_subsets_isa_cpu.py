@@ -2,15 +2,12 @@
 assembly of dpe_bcm.hip: no scratch, no dynamic stack, every template variant emitted, and register counts inside the budget
 of a 256-thread block (512 VGPRs per lane at one block per CU; the LPower 1 / 2 variants with subsets stay below 170, which
 leaves three waves per SIMD, the plain variants below 80); SGPRs and static LDS are pinned a few above what was measured.  Compiles with hipcc -S (no GPU needed); skips where hipcc is absent."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "navlab-dpe-sdr_amd", "csrc", "dpe_bcm.hip")
+from tests.isa_asm import asm_of
+
 KERNEL = "_ZN3dpe23bcm_scan_subsets_kernelILi%dELb%dELb%dELb%dEEE"
 # (LPower variant, SUBS) -> VGPR budget.  Measured when this budget was set: with subsets 156 .. 158 (LPower 1), 162 .. 164 (2),
 # 231 .. 233 (general powf); without 65 .. 68 (1), 68 (2), 135 .. 137 (general powf)
@@ -22,23 +19,9 @@ SGPR_MAX = {(1, 1): 90, (2, 1): 90, (0, 1): 104, (1, 0): 84, (2, 0): 84, (0, 0):
 LDS_MAX = {1: 1792, 0: 448}
 
 
-def _hipcc():
-    for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    hipcc = _hipcc()
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "dpe_bcm.s")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed",
-                           "-S", "--cuda-device-only", SRC, "-o", out], cwd=os.path.dirname(SRC),
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return open(out).read()
+def asm():
+    return asm_of("dpe_bcm.hip")
 
 
 def _descriptor(text, prefix):
