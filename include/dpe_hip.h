@@ -674,6 +674,14 @@ int dpe_chm_dev_set_shard(dpe_chm_dev *h, dpe_comm *comm, const double *posGridG
  * status: S was singular in some window (state held).  After dpe_chm_dev_attach, before Start.  (dpe_ekf_config is declared below.) */
 struct dpe_ekf_config;
 int dpe_chm_dev_set_ekf(dpe_chm_dev *h, const struct dpe_ekf_config *cfg);
+/* The device filter's members, as dpe_ekf_state gives the host form's (host arrays, any pointer may be NULL; synchronises `stream`).
+ * Whether S was ever singular is bit 5 (32) of the status (dpe_fix_record, dpe_chm_dev_read).  Refused before dpe_chm_dev_set_ekf. */
+int dpe_chm_dev_ekf_state(dpe_chm_dev *h, double *xk1k1, double *xkk1, double *Pk1k1, double *Pkk1, double *Q, double *K,
+                          dpe_stream_t stream);
+/* x_k|k-1 [8] / P_k|k-1 [64] of the device filter overwritten from host arrays (either may be NULL), as dpe_ekf_load does for the
+ * host form; the state ports stay.  Valid only between windows: once dpe_chm_dev_fix has returned the fix of the last
+ * dpe_chm_dev_step.  Refused before dpe_chm_dev_set_ekf. */
+int dpe_chm_dev_ekf_load(dpe_chm_dev *h, const double *xkk1_host, const double *Pkk1_host, dpe_stream_t stream);
 /* The device port arrays, in the structs dpe_bcs_update_dev / dpe_bcm_update_dev take, plus rxTime and the two state ports
  * (any pointer may be NULL): what dpeflow.cpp:169-191,212 connects. */
 int dpe_chm_dev_ports(dpe_chm_dev *h, dpe_bcs_ports_dev *bcs, dpe_bcm_ports_dev *bcm, const double **rxTime_dev,
@@ -715,6 +723,8 @@ int dpe_ekf_destroy(dpe_ekf *h);
 int dpe_ekf_step_update(dpe_ekf *h, const double *z /* [8] */, const double *R /* [64] */);   /* StepUpdate :660-721 */
 int dpe_ekf_step_predict(dpe_ekf *h);                                                        /* StepPredict :626-656 */
 int dpe_ekf_state(dpe_ekf *h, double *xk1k1, double *xkk1, double *Pk1k1, double *Pkk1, double *Q, double *K);
+/* Tests / re-initialisation: x_k|k-1 [8] and P_k|k-1 [64] overwritten between two steps (either may be NULL). */
+int dpe_ekf_load(dpe_ekf *h, const double *xkk1, const double *Pkk1);
 
 /* ------------------------------------------------------------------ Acquisition ---- */
 /* Cold-start coarse acquisition.  Only the reference's Python twin implements it:

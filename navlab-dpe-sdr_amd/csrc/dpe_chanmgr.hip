@@ -414,6 +414,35 @@ int dpe_chm_dev_set_ekf(dpe_chm_dev *h, const dpe_ekf_config *cfg)
     return 0;
 }
 
+// The filter's members as dpe_ekf_state gives the host form's (tests, logging): synchronises `stream`.
+int dpe_chm_dev_ekf_state(dpe_chm_dev *h, double *xk1k1, double *xkk1, double *Pk1k1, double *Pkk1, double *Q, double *K, dpe_stream_t stream)
+{
+    using namespace dpe;
+    DPE_REQUIRE(h && h->ekf_d, "[cuChanMgr] ekf_state: no filter (dpe_chm_dev_set_ekf)");
+    DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    std::vector<EkfDev> e(1);
+    DPE_CHECK_HIP(hipMemcpy(&e[0], h->ekf_d, sizeof(EkfDev), hipMemcpyDeviceToHost));
+    if (xk1k1) memcpy(xk1k1, e[0].xk1k1, sizeof(e[0].xk1k1));
+    if (xkk1) memcpy(xkk1, e[0].xkk1, sizeof(e[0].xkk1));
+    if (Pk1k1) memcpy(Pk1k1, e[0].Pk1k1, sizeof(e[0].Pk1k1));
+    if (Pkk1) memcpy(Pkk1, e[0].Pkk1, sizeof(e[0].Pkk1));
+    if (Q) memcpy(Q, e[0].Q, sizeof(e[0].Q));
+    if (K) memcpy(K, e[0].K, sizeof(e[0].K));
+    return 0;
+}
+
+// Overwrites the filter's predicted state / covariance (either may be NULL) between two windows: the next measurement kernel reads
+// them.  The state PORTS are not touched -- the grids of the window already prepared stay centred where they are.
+int dpe_chm_dev_ekf_load(dpe_chm_dev *h, const double *xkk1, const double *Pkk1, dpe_stream_t stream)
+{
+    using namespace dpe;
+    DPE_REQUIRE(h && h->ekf_d, "[cuChanMgr] ekf_load: no filter (dpe_chm_dev_set_ekf)");
+    DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    if (xkk1) DPE_CHECK_HIP(hipMemcpy(h->ekf_d->xkk1, xkk1, sizeof(double) * 8, hipMemcpyHostToDevice));
+    if (Pkk1) DPE_CHECK_HIP(hipMemcpy(h->ekf_d->Pkk1, Pkk1, sizeof(double) * 64, hipMemcpyHostToDevice));
+    return 0;
+}
+
 int dpe_chm_dev_ports(dpe_chm_dev *h, dpe_bcs_ports_dev *bcs, dpe_bcm_ports_dev *bcm, const double **rxTime_dev, double **xk1k1_dev,
                       double **xkk1_dev, const double **zVal_dev)
 {

@@ -183,4 +183,13 @@ int dpe_ekf_state(dpe_ekf *h, double *xk1k1, double *xkk1, double *Pk1k1, double
     return 0;
 }
 
+// x_k|k-1 / P_k|k-1 overwritten between two steps (either may be NULL): the next StepUpdate reads them
+int dpe_ekf_load(dpe_ekf *h, const double *xkk1, const double *Pkk1)
+{
+    DPE_REQUIRE(h, "[cuEKF] load: null handle");
+    if (xkk1) memcpy(h->xkk1, xkk1, sizeof(h->xkk1));
+    if (Pkk1) memcpy(h->Pkk1, Pkk1, sizeof(h->Pkk1));
+    return 0;
+}
+
 }  // extern "C"

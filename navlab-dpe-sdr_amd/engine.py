@@ -25,14 +25,14 @@ EXPORTS = [
     "dpe_chm_update", "dpe_chm_outputs", "dpe_bcs_profile", "dpe_bcm_profile", "dpe_acq_create", "dpe_acq_destroy",
     "dpe_acq_search", "dpe_acq_results", "dpe_acq_surface", "dpe_bcs_set_graph", "dpe_bcm_set_graph",
     "dpe_acq_fine", "dpe_acq_scalar_acquisition",
-    "dpe_ekf_create", "dpe_ekf_destroy", "dpe_ekf_step_update", "dpe_ekf_step_predict", "dpe_ekf_state",
+    "dpe_ekf_create", "dpe_ekf_destroy", "dpe_ekf_step_update", "dpe_ekf_step_predict", "dpe_ekf_state", "dpe_ekf_load",
     "dpe_hbm_ceiling", "dpe_bcs_stage1_kernel",
     "dpe_set_device", "dpe_comm_create", "dpe_comm_wrap_nccl", "dpe_comm_destroy", "dpe_comm_rank", "dpe_comm_allreduce_max_u64",
     "dpe_comm_allgather", "dpe_bcm_exchange_keys", "dpe_bcs_allgather_banks",
     "dpe_bcs_update_dev", "dpe_bcs_dev_status", "dpe_bcm_update_dev", "dpe_bcm_export_scores_f64",
     "dpe_chm_dev_create", "dpe_chm_dev_destroy", "dpe_chm_dev_attach", "dpe_chm_dev_ports", "dpe_chm_dev_start", "dpe_chm_dev_update",
     "dpe_chm_dev_step", "dpe_chm_dev_fix", "dpe_chm_dev_read", "dpe_bcs_update_prepared", "dpe_bcm_update_prepared", "dpe_bcs_set_dev_hint",
-    "dpe_chm_dev_set_shard", "dpe_chm_dev_set_ekf",
+    "dpe_chm_dev_set_shard", "dpe_chm_dev_set_ekf", "dpe_chm_dev_ekf_state", "dpe_chm_dev_ekf_load",
     "dpe_pipe_create", "dpe_pipe_create_axes", "dpe_pipe_destroy", "dpe_pipe_in_flight", "dpe_pipe_submit", "dpe_pipe_acquire", "dpe_pipe_mark_stage1",
     "dpe_pipe_commit", "dpe_pipe_lane", "dpe_pipe_set_in_flight", "dpe_pipe_lane_at", "dpe_pipe_results", "dpe_pipe_samples_consumed", "dpe_pipe_join", "dpe_pipe_synchronize",
     "dpe_trk_create", "dpe_trk_destroy", "dpe_trk_set_params", "dpe_trk_track", "dpe_trk_correlate", "dpe_trk_read_log",
@@ -1257,6 +1257,23 @@ class ChanMgrDev:
         cfg.P0[:] = [float(v) for v in (np.eye(8) if P0 is None else np.asarray(P0, dtype=np.float64)).reshape(64)]
         _check(lib().dpe_chm_dev_set_ekf(self._h, C.byref(cfg)))
 
+    def ekf_state(self, stream=None):
+        """dpe_chm_dev_ekf_state: the device filter's members in the form of cuEKF.state()."""
+        a = {k: np.zeros(n) for k, n in (("xk1k1", 8), ("xkk1", 8), ("Pk1k1", 64), ("Pkk1", 64), ("Q", 64), ("K", 64))}
+        dp = C.POINTER(C.c_double)
+        _check(lib().dpe_chm_dev_ekf_state(self._h, *[a[k].ctypes.data_as(dp) for k in ("xk1k1", "xkk1", "Pk1k1", "Pkk1", "Q", "K")],
+                                           _stream(stream)))
+        return {k: (v if v.size == 8 else v.reshape(8, 8)) for k, v in a.items()}
+
+    def ekf_load(self, xkk1=None, Pkk1=None, stream=None):
+        """dpe_chm_dev_ekf_load: x_k|k-1 / P_k|k-1 of the device filter overwritten (None: left as it is).  Between windows only:
+        after fix(w) of the last step() has returned."""
+        x = None if xkk1 is None else np.ascontiguousarray(xkk1, dtype=np.float64).reshape(8)
+        P = None if Pkk1 is None else np.ascontiguousarray(Pkk1, dtype=np.float64).reshape(64)
+        dp = C.POINTER(C.c_double)
+        _check(lib().dpe_chm_dev_ekf_load(self._h, None if x is None else x.ctypes.data_as(dp), None if P is None else P.ctypes.data_as(dp),
+                                          _stream(stream)))
+
     def ports(self):
         """-> (BcsPortsDev, BcmPortsDev, rxTime_dev, xk1k1_dev, xkk1_dev, zVal_dev): raw device pointers."""
         b, m = BcsPortsDev(), BcmPortsDev()
@@ -1856,6 +1873,15 @@ class cuEKF:
         dp = C.POINTER(C.c_double)
         _check(lib().dpe_ekf_state(self._h, *[a[k].ctypes.data_as(dp) for k in ("xk1k1", "xkk1", "Pk1k1", "Pkk1", "Q", "K")]))
         return {k: (v if v.size == 8 else v.reshape(8, 8)) for k, v in a.items()}
+
+    def load(self, xkk1=None, Pkk1=None):
+        """dpe_ekf_load: x_k|k-1 / P_k|k-1 overwritten between two steps (None: left as it is)."""
+        x = None if xkk1 is None else np.ascontiguousarray(xkk1, dtype=np.float64).reshape(8)
+        P = None if Pkk1 is None else np.ascontiguousarray(Pkk1, dtype=np.float64).reshape(64)
+        dp = C.POINTER(C.c_double)
+        _check(lib().dpe_ekf_load(self._h, None if x is None else x.ctypes.data_as(dp), None if P is None else P.ctypes.data_as(dp)))
+        if x is not None:
+            self.xCurrkk1 = x.copy()
 
     def Stop(self):
         if self._h:
