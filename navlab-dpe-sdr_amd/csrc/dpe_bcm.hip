@@ -932,11 +932,83 @@ static int ref_pair_fixup(dpe_bcm *h, const float *codeBank_dev, int nWindows, i
     return 0;
 }
 
+// ---- host pieces the entry points of the six handle kinds share: plain functions, each written once; `who`
+// is the entry point's name as its messages spell it ------------------------------------------------
+static size_t sv_stride(const dpe_bcm *h)   // channels per window of sv_d / sv_h
+{
+    return h->joint ? (size_t)h->jointMaxK : (size_t)h->cfg.maxChannels;
+}
+
+static size_t sv_bytes(const dpe_bcm *h)   // both manifolds' coefficient blocks, [2][W][stride]
+{
+    return sizeof(dpe::BcmSvDev) * 2 * (size_t)h->cfg.maxWindows * sv_stride(h);
+}
+
+static size_t n_ent_max(const dpe_bcm_config &cfg)   // entries of the longer of a channel's two score banks: a bank row in LDS
+{
+    return (size_t)(2 * (cfg.lagHalfWidth > cfg.binHalfWidth ? cfg.lagHalfWidth : cfg.binHalfWidth) + 1);
+}
+
+static size_t lds_per_channel(const dpe_bcm_config &cfg)   // the LDS budget rule of dpe_bcm_config: 16-byte entries + 32 B
+{
+    return n_ent_max(cfg) * 16 + 32;
+}
+
+static int check_max_counts(const dpe_bcm_config *cfg, const char *who)
+{
+    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
+                "[BatchCorrManifold] %s: maxWindows/maxChannels out of range", who);
+    return 0;
+}
+
+static int check_cfg(const dpe_bcm_config *cfg, const char *who)
+{
+    DPE_REQUIRE(cfg->samplesPerWindow > 0 && (cfg->samplesPerWindow % 2) == 0, "[BatchCorrManifold] %s: samplesPerWindow must be even and positive", who);
+    DPE_REQUIRE(cfg->samplingFrequency > 0 && cfg->numFFTPoints > 0, "[BatchCorrManifold] %s: bad fs / numFFTPoints", who);
+    if (check_max_counts(cfg, who)) return -1;
+    DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1 && cfg->lPower >= 1, "[BatchCorrManifold] %s: bad L/B/LPower", who);
+    return 0;
+}
+
+static int check_no_shards(const dpe_bcm_config *cfg, const char *who)
+{
+    DPE_REQUIRE(cfg->posGridIndexOffset == 0 && cfg->velGridIndexOffset == 0,
+                "[BatchCorrManifold] %s: grid shards are not supported (the index offsets must be 0)", who);
+    return 0;
+}
+
+static int check_axes_lds(const dpe_bcm_config *cfg, const char *who)   // grid axes: the banks share the LDS with the score stage
+{
+    DPE_REQUIRE((size_t)cfg->maxChannels * lds_per_channel(*cfg) + (size_t)dpe::kAxStageBytes <= 150 * 1024,
+                "[BatchCorrManifold] %s: score banks (%zu B) and the score stage (%d B) exceed the LDS (no 12-byte bank entries with grid axes)", who,
+                (size_t)cfg->maxChannels * n_ent_max(*cfg) * 16, dpe::kAxStageBytes);
+    return 0;
+}
+
+// One manifold's four axes: dimension >= 1 with an array, finite entries, a product that fits 32 bits.  mx[c] comes back as the
+// largest |entry| of axis c, *prod as the number of points; `level` is "" or the "level %d " of the messages.
+static int check_axes(const char *who, const char *level, const char *name, const dpe_grid_axes *ga, double mx[4], int64_t *prod)
+{
+    *prod = 1;
+    for (int c = 0; c < 4; ++c) {
+        mx[c] = 0;
+        DPE_REQUIRE(ga->dim[c] >= 1 && ga->axis[c], "[BatchCorrManifold] %s: %s%s axis %d: dim %d < 1 or no array", who, level, name, c, ga->dim[c]);
+        for (int i = 0; i < ga->dim[c]; ++i) {
+            const double v = ga->axis[c][i];
+            DPE_REQUIRE(std::isfinite(v), "[BatchCorrManifold] %s: %s%s axis %d entry %d is not finite", who, level, name, c, i);
+            mx[c] = std::max(mx[c], std::fabs(v));
+        }
+        DPE_REQUIRE(*prod <= 0xFFFFFFFFll / ga->dim[c], "[BatchCorrManifold] %s: %s%s grid index does not fit 32 bits", who, level, name);
+        *prod *= ga->dim[c];
+    }
+    return 0;
+}
+
 // The buffers every handle has, whatever holds its grids (create and create_axes)
 static int bcm_finish_create(dpe_bcm *h, const dpe_bcm_config *cfg, dpe_bcm **out)
 {
     using namespace dpe;
-    const size_t W = cfg->maxWindows, K = h->joint ? h->jointMaxK : cfg->maxChannels;
+    const size_t W = cfg->maxWindows, K = sv_stride(h);
     // score rows start on 128-byte lines: a wave's 64 consecutive scores are then two whole lines instead of one whole and two
     // partial ones (config R, 390 625-point rows: 0.779 -> 0.755 ms per step, the write-back of a step's 0.8 GB drains faster)
     h->posPitch = (cfg->posGridSize + 31) / 32 * 32;
@@ -1002,19 +1074,13 @@ static int bcm_create_points(const dpe_bcm_config *cfg, dpe_bcm *donor, int maxR
     const int ldsChannels = joint ? maxKTotal : cfg->maxChannels;
     DPE_REQUIRE(!donor || ((int64_t)donor->posGrid_h.size() == 4 * cfg->posGridSize && (int64_t)donor->velGrid_h.size() == 4 * cfg->velGridSize &&
                            !donor->gridsBorrowed), "[BatchCorrManifold] create: the grids to share are not these grids");
-    DPE_REQUIRE(cfg->samplesPerWindow > 0 && (cfg->samplesPerWindow % 2) == 0,
-                "[BatchCorrManifold] create: samplesPerWindow must be even and positive");
-    DPE_REQUIRE(cfg->samplingFrequency > 0 && cfg->numFFTPoints > 0, "[BatchCorrManifold] create: bad fs / numFFTPoints");
-    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
-                "[BatchCorrManifold] create: maxWindows/maxChannels out of range");
-    DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1 && cfg->lPower >= 1, "[BatchCorrManifold] create: bad L/B/LPower");
+    if (check_cfg(cfg, "create")) return -1;
     DPE_REQUIRE(cfg->posGrid && cfg->velGrid && cfg->posGridSize > 0 && cfg->velGridSize > 0,
                 "[BatchCorrManifold] create: grids missing");
     DPE_REQUIRE(cfg->posGridSize + cfg->posGridIndexOffset < 0xFFFFFFFFll &&
                 cfg->velGridSize + cfg->velGridIndexOffset < 0xFFFFFFFFll,
                 "[BatchCorrManifold] create: global grid index exceeds 32 bits");
-    const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
-    const size_t ldsNeed = (size_t)ldsChannels * (nEntMax * 16 + 32);
+    const size_t nEntMax = n_ent_max(*cfg), ldsNeed = (size_t)ldsChannels * lds_per_channel(*cfg);
     const bool compact = ldsNeed > 150 * 1024;   // 12-byte entries (slower scan variant) when the 16-byte ones do not fit
     DPE_REQUIRE(!joint || !compact, "[BatchCorrManifold] create_joint: the score banks of %d (receiver, SV) pairs x %zu entries (%zu B) exceed the "
                                     "150 KB the joint scan keeps in LDS", ldsChannels, nEntMax, ldsNeed);
@@ -1089,8 +1155,7 @@ int dpe_bcm_create_joint(const dpe_bcm_config *cfg, int32_t maxRx, int32_t maxCh
                 cfg->maxChannels, maxChannelsTotal);
     DPE_REQUIRE(!cfg->weightedMean, "[BatchCorrManifold] create_joint: the weighted-mean estimator is not formed for several receivers (weightedMean must be 0)");
     DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_joint: referencePair is a single-receiver mode (it re-evaluates one receiver's first channel)");
-    DPE_REQUIRE(cfg->posGridIndexOffset == 0 && cfg->velGridIndexOffset == 0,
-                "[BatchCorrManifold] create_joint: grid shards are not supported (the index offsets must be 0)");
+    if (check_no_shards(cfg, "create_joint")) return -1;
     dpe_bcm *h = nullptr;
     if (bcm_create_points(cfg, nullptr, maxRx, maxChannelsTotal, &h)) return -1;
     const size_t W = cfg->maxWindows, n = W * (size_t)maxRx;
@@ -1118,20 +1183,17 @@ int dpe_bcm_create_epochs(const dpe_bcm_config *cfg, int32_t maxEpochs, int32_t 
 {
     using namespace dpe;
     DPE_REQUIRE(cfg && out, "[BatchCorrManifold] create_epochs: null argument");
-    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
-                "[BatchCorrManifold] create_epochs: maxWindows/maxChannels out of range");
+    if (check_max_counts(cfg, "create_epochs")) return -1;
     DPE_REQUIRE(maxEpochs >= 1 && maxEpochs <= cfg->maxWindows, "[BatchCorrManifold] create_epochs: maxEpochs %d out of range (1 .. maxWindows = %d)",
                 maxEpochs, cfg->maxWindows);
     DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1, "[BatchCorrManifold] create_epochs: bad L/B");
     DPE_REQUIRE(!cfg->weightedMean, "[BatchCorrManifold] create_epochs: the weighted-mean estimator is not formed for summed windows (weightedMean must be 0)");
     DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_epochs: referencePair is a single-window mode (it re-evaluates one window's first channel)");
-    DPE_REQUIRE(cfg->posGridIndexOffset == 0 && cfg->velGridIndexOffset == 0,
-                "[BatchCorrManifold] create_epochs: grid shards are not supported (the index offsets must be 0)");
-    const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
-    const size_t budget = (size_t)150 * 1024 / (nEntMax * 16 + 32);   // pairs * ((2 max(L, B) + 1) * 16 + 32) <= 150 KB
+    if (check_no_shards(cfg, "create_epochs")) return -1;
+    const size_t budget = (size_t)150 * 1024 / lds_per_channel(*cfg);   // pairs * ((2 max(L, B) + 1) * 16 + 32) <= 150 KB
     DPE_REQUIRE(budget >= (size_t)cfg->maxChannels, "[BatchCorrManifold] create_epochs: the score banks of one window (%d channels x %zu entries, %zu B) exceed "
                                                     "the 150 KB the epochs scan keeps in LDS (no 12-byte bank entries here)",
-                cfg->maxChannels, nEntMax, (size_t)cfg->maxChannels * (nEntMax * 16 + 32));
+                cfg->maxChannels, n_ent_max(*cfg), (size_t)cfg->maxChannels * lds_per_channel(*cfg));
     DPE_REQUIRE(pairsPerPass == 0 || pairsPerPass >= cfg->maxChannels,
                 "[BatchCorrManifold] create_epochs: pairsPerPass %d is below maxChannels %d (a pass holds whole windows; 0 = as many as the LDS holds)",
                 pairsPerPass, cfg->maxChannels);
@@ -1155,17 +1217,14 @@ int dpe_bcm_create_subsets(const dpe_bcm_config *cfg, int32_t maxSubsets, dpe_bc
     DPE_REQUIRE(cfg && out, "[BatchCorrManifold] create_subsets: null argument");
     DPE_REQUIRE(maxSubsets >= 1 && maxSubsets <= kSubsetMax, "[BatchCorrManifold] create_subsets: maxSubsets %d out of range (1 .. %d subsets per window)",
                 maxSubsets, kSubsetMax);
-    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
-                "[BatchCorrManifold] create_subsets: maxWindows/maxChannels out of range");
+    if (check_max_counts(cfg, "create_subsets")) return -1;
     DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1, "[BatchCorrManifold] create_subsets: bad L/B");
     DPE_REQUIRE(!cfg->weightedMean, "[BatchCorrManifold] create_subsets: the weighted-mean estimator is not formed per subset (weightedMean must be 0)");
     DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_subsets: referencePair re-evaluates the full set only (referencePair must be 0)");
-    DPE_REQUIRE(cfg->posGridIndexOffset == 0 && cfg->velGridIndexOffset == 0,
-                "[BatchCorrManifold] create_subsets: grid shards are not supported (the index offsets must be 0)");
-    const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
-    const size_t ldsNeed = (size_t)cfg->maxChannels * (nEntMax * 16 + 32);
+    if (check_no_shards(cfg, "create_subsets")) return -1;
+    const size_t ldsNeed = (size_t)cfg->maxChannels * lds_per_channel(*cfg);
     DPE_REQUIRE(ldsNeed <= 150 * 1024, "[BatchCorrManifold] create_subsets: the score banks of %d channels x %zu entries (%zu B) exceed the 150 KB the "
-                                       "subsets scan keeps in LDS (no 12-byte bank entries here)", cfg->maxChannels, nEntMax, ldsNeed);
+                                       "subsets scan keeps in LDS (no 12-byte bank entries here)", cfg->maxChannels, n_ent_max(*cfg), ldsNeed);
     dpe_bcm *h = nullptr;
     if (bcm_create_points(cfg, nullptr, 0, 0, &h)) return -1;
     const size_t W = cfg->maxWindows, n = W * (size_t)maxSubsets + 2 * W * (size_t)maxSubsets + 2 * W * (size_t)cfg->maxChannels;
@@ -1196,34 +1255,15 @@ int dpe_bcm_create_axes_sharing(const dpe_bcm_config *cfg, const dpe_grid_axes *
     DPE_REQUIRE(cfg && pos && vel && out, "[BatchCorrManifold] create_axes: null argument");
     DPE_REQUIRE(!cfg->posGrid && !cfg->velGrid, "[BatchCorrManifold] create_axes: posGrid / velGrid must be NULL (the grids are the axes)");
     DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_axes: referencePair is not supported with grid axes");
-    DPE_REQUIRE(cfg->samplesPerWindow > 0 && (cfg->samplesPerWindow % 2) == 0,
-                "[BatchCorrManifold] create_axes: samplesPerWindow must be even and positive");
-    DPE_REQUIRE(cfg->samplingFrequency > 0 && cfg->numFFTPoints > 0, "[BatchCorrManifold] create_axes: bad fs / numFFTPoints");
-    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
-                "[BatchCorrManifold] create_axes: maxWindows/maxChannels out of range");
-    DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1 && cfg->lPower >= 1, "[BatchCorrManifold] create_axes: bad L/B/LPower");
-    const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
-    DPE_REQUIRE((size_t)cfg->maxChannels * (nEntMax * 16 + 32) + (size_t)kAxStageBytes <= 150 * 1024,
-                "[BatchCorrManifold] create_axes: score banks (%zu B) and the score stage (%d B) exceed the LDS (no 12-byte bank entries with grid axes)",
-                (size_t)cfg->maxChannels * nEntMax * 16, kAxStageBytes);
+    if (check_cfg(cfg, "create_axes") || check_axes_lds(cfg, "create_axes")) return -1;
     const dpe_grid_axes *ga[2] = {pos, vel};
     const int64_t size[2] = {cfg->posGridSize, cfg->velGridSize}, offset[2] = {cfg->posGridIndexOffset, cfg->velGridIndexOffset};
     double ext[2], r2[2];
     for (int m = 0; m < 2; ++m) {
         const char *name = m ? "velocity" : "position";
-        double mx[4] = {0, 0, 0, 0};
-        int64_t prod = 1;
-        for (int c = 0; c < 4; ++c) {
-            DPE_REQUIRE(ga[m]->dim[c] >= 1 && ga[m]->axis[c], "[BatchCorrManifold] create_axes: %s axis %d: dim %d < 1 or no array", name, c,
-                        ga[m]->dim[c]);
-            for (int i = 0; i < ga[m]->dim[c]; ++i) {
-                const double v = ga[m]->axis[c][i];
-                DPE_REQUIRE(std::isfinite(v), "[BatchCorrManifold] create_axes: %s axis %d entry %d is not finite", name, c, i);
-                mx[c] = std::max(mx[c], std::fabs(v));
-            }
-            DPE_REQUIRE(prod <= 0xFFFFFFFFll / ga[m]->dim[c], "[BatchCorrManifold] create_axes: %s grid index does not fit 32 bits", name);
-            prod *= ga[m]->dim[c];
-        }
+        double mx[4];
+        int64_t prod;
+        if (check_axes("create_axes", "", name, ga[m], mx, &prod)) return -1;
         DPE_REQUIRE(size[m] > 0 && offset[m] >= 0 && offset[m] + size[m] <= prod,
                     "[BatchCorrManifold] create_axes: %s slice [%lld, %lld) beyond the axis product %lld", name, (long long)offset[m],
                     (long long)(offset[m] + size[m]), (long long)prod);
@@ -1289,37 +1329,18 @@ int dpe_bcm_create_refine(const dpe_bcm_config *cfg, int32_t nLevels, const dpe_
     DPE_REQUIRE(!cfg->posGrid && !cfg->velGrid, "[BatchCorrManifold] create_refine: posGrid / velGrid must be NULL (the grids are the levels' axes)");
     DPE_REQUIRE(!cfg->weightedMean, "[BatchCorrManifold] create_refine: the weighted-mean estimator is not formed per level (weightedMean must be 0)");
     DPE_REQUIRE(!cfg->referencePair, "[BatchCorrManifold] create_refine: referencePair is not supported with grid axes (referencePair must be 0)");
-    DPE_REQUIRE(cfg->posGridIndexOffset == 0 && cfg->velGridIndexOffset == 0,
-                "[BatchCorrManifold] create_refine: grid shards are not supported (the index offsets must be 0)");
-    DPE_REQUIRE(cfg->samplesPerWindow > 0 && (cfg->samplesPerWindow % 2) == 0,
-                "[BatchCorrManifold] create_refine: samplesPerWindow must be even and positive");
-    DPE_REQUIRE(cfg->samplingFrequency > 0 && cfg->numFFTPoints > 0, "[BatchCorrManifold] create_refine: bad fs / numFFTPoints");
-    DPE_REQUIRE(cfg->maxWindows >= 1 && cfg->maxChannels >= 1 && cfg->maxChannels <= DPE_MAX_CHAN,
-                "[BatchCorrManifold] create_refine: maxWindows/maxChannels out of range");
-    DPE_REQUIRE(cfg->lagHalfWidth >= 1 && cfg->binHalfWidth >= 1 && cfg->lPower >= 1, "[BatchCorrManifold] create_refine: bad L/B/LPower");
-    const size_t nEntMax = (size_t)(2 * (cfg->lagHalfWidth > cfg->binHalfWidth ? cfg->lagHalfWidth : cfg->binHalfWidth) + 1);
-    DPE_REQUIRE((size_t)cfg->maxChannels * (nEntMax * 16 + 32) + (size_t)kAxStageBytes <= 150 * 1024,
-                "[BatchCorrManifold] create_refine: score banks (%zu B) and the score stage (%d B) exceed the LDS (no 12-byte bank entries with grid axes)",
-                (size_t)cfg->maxChannels * nEntMax * 16, kAxStageBytes);
+    if (check_no_shards(cfg, "create_refine") || check_cfg(cfg, "create_refine") || check_axes_lds(cfg, "create_refine")) return -1;
     // the reach of a chain of levels: a point is a sum of one entry per level, so per-level corner distances and |t| maxima add up
     double corner[2] = {0, 0}, tmax[2] = {0, 0};
     for (int l = 0; l < nLevels; ++l) {
         const dpe_grid_axes *ga[2] = {pos + l, vel + l};
+        char level[24];
+        snprintf(level, sizeof(level), "level %d ", l);
         for (int m = 0; m < 2; ++m) {
             const char *name = m ? "velocity" : "position";
-            double mx[4] = {0, 0, 0, 0};
-            int64_t prod = 1;
-            for (int c = 0; c < 4; ++c) {
-                DPE_REQUIRE(ga[m]->dim[c] >= 1 && ga[m]->axis[c], "[BatchCorrManifold] create_refine: level %d %s axis %d: dim %d < 1 or no array", l, name, c,
-                            ga[m]->dim[c]);
-                for (int i = 0; i < ga[m]->dim[c]; ++i) {
-                    const double v = ga[m]->axis[c][i];
-                    DPE_REQUIRE(std::isfinite(v), "[BatchCorrManifold] create_refine: level %d %s axis %d entry %d is not finite", l, name, c, i);
-                    mx[c] = std::max(mx[c], std::fabs(v));
-                }
-                DPE_REQUIRE(prod <= 0xFFFFFFFFll / ga[m]->dim[c], "[BatchCorrManifold] create_refine: level %d %s grid index does not fit 32 bits", l, name);
-                prod *= ga[m]->dim[c];
-            }
+            double mx[4];
+            int64_t prod;
+            if (check_axes("create_refine", level, name, ga[m], mx, &prod)) return -1;
             // every index the scan forms, including those of the lanes that run past the last row, fits 32 bits
             const int64_t dimT = ga[m]->dim[3];
             DPE_REQUIRE((prod / dimT + 256) * dimT + kAxT < 0xFFFFFFFFll, "[BatchCorrManifold] create_refine: level %d %s grid index does not fit 32 bits", l,
@@ -1468,6 +1489,115 @@ static void bcm_expand(const dpe_bcm *h, const dpe_bcm_window &win, const dpe_ch
     }
 }
 
+// ---- the host pieces of an Update ------------------------------------------------------------
+static int check_kind(bool is, const char *who, const char *maker)
+{
+    DPE_REQUIRE(is, "[BatchCorrManifold] %s: the handle was not made by %s", who, maker);
+    return 0;
+}
+
+static int check_windows(const dpe_bcm *h, const char *who, int nWindows)
+{
+    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] %s: nWindows %d out of range", who, nWindows);
+    return 0;
+}
+
+static int check_chan(const dpe_bcm *h, const char *who, int nChan)
+{
+    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] %s: nChan %d out of range", who, nChan);
+    return 0;
+}
+
+static int check_sign(const char *who, const dpe_bcm_window *win, int n)
+{
+    for (int w = 0; w < n; ++w)
+        DPE_REQUIRE(win[w].dopplerSign == 1 || win[w].dopplerSign == -1, "[BatchCorrManifold] %s: dopplerSign must be +/-1", who);
+    return 0;
+}
+
+// Stage begin: the next block of the pinned ring (an Update kStaging calls ago may still be copying it) becomes sv_h.  Called
+// once every check has passed: a refused call takes no slot.
+static int stage_begin(dpe_bcm *h, bool dev)
+{
+    h->lastDev = dev;
+    h->slot = (h->slot + 1) % dpe_bcm::kStaging;
+    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
+    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * h->cfg.maxWindows * sv_stride(h);
+    return 0;
+}
+
+// One window's channels into both manifolds' rows of sv_h, from channel kOff on, each about that window's own centre
+static void expand_window(dpe_bcm *h, int w, const dpe_bcm_window &win, const dpe_chan_end *ch, int nChan, int kOff, bool &posInside, bool &velInside)
+{
+    dpe::BcmSvDev *p = h->sv_h + (size_t)w * sv_stride(h) + kOff, *v = p + (size_t)h->cfg.maxWindows * sv_stride(h);
+    for (int k = 0; k < nChan; ++k) bcm_expand(h, win, ch[k], p[k], v[k], posInside, velInside);
+}
+
+// Stage begin, then nWin windows of nChan channels kept in win_h and expanded (win == nullptr: a device-parameter Update,
+// whose coefficients bcm_prep_kernel writes)
+static int stage_windows(dpe_bcm *h, const dpe_bcm_window *win, const dpe_chan_end *chan, int nWin, int nChan, bool &posInside, bool &velInside)
+{
+    if (stage_begin(h, win == nullptr)) return -1;
+    for (int w = 0; win && w < nWin; ++w) {
+        h->win_h[w] = win[w];
+        expand_window(h, w, win[w], chan + (size_t)w * nChan, nChan, 0, posInside, velInside);
+    }
+    return 0;
+}
+
+// Two key / counter sets of setLen words ({keys, counts}) alternate between Updates: a call reduces into set `use` (zero since
+// the previous call's position scan, or create, cleared it) and clears `other`
+struct KeySet {
+    int use;
+    unsigned long long *keys, *oob, *other;
+};
+
+static KeySet next_key_set(const dpe_bcm *h, unsigned long long *base, size_t setLen)
+{
+    const int use = h->cur ^ 1;
+    return KeySet{use, base + (size_t)use * setLen, base + (size_t)use * setLen + setLen / 2, base + (size_t)(use ^ 1) * setLen};
+}
+
+// The two manifolds' ScanSides over the handle's point lists; the splits are h->lastSplit.  (The handle kinds that scan whole
+// grids and form no weighted mean were refused index offsets and weightedMean at create, so cfg says 0 for them.)
+static void scan_sides(const dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, dpe::ScanSide &sp, dpe::ScanSide &sv)
+{
+    const int nLag = 2 * h->cfg.lagHalfWidth + 1, nBin = 2 * h->cfg.binHalfWidth + 1;
+    sp = dpe::ScanSide{h->posGrid_d, reinterpret_cast<const float2 *>(codeBank_dev), h->sv_d, h->posScores_d,
+                       h->cfg.weightedMean ? h->wsum_d : nullptr, h->cfg.posGridSize, h->cfg.posGridIndexOffset, h->posPitch, nLag,
+                       (int)h->lastSplit[0]};
+    sv = dpe::ScanSide{h->velGrid_d, reinterpret_cast<const float2 *>(carrBank_dev), h->sv_d + (size_t)h->cfg.maxWindows * sv_stride(h), h->velScores_d,
+                       h->cfg.weightedMean ? h->wsum_d + h->wsumHalf : nullptr, h->cfg.velGridSize, h->cfg.velGridIndexOffset, h->velPitch, nBin,
+                       (int)h->lastSplit[1]};
+}
+
+// The tail of a publishing family's launch over `rows` windows (groups): key sets, publishing pointers (publish = false: the
+// scan leaves keys and counts in device memory only) and the geometry from h->lastSplit.  It also moves the handle's state that
+// goes with them: seq advances (the launch carries the new value), lastPublished = publish, pollable = false.
+static void fill_tail(dpe_bcm *h, ScanTail &t, const KeySet &ks, int clrN, bool publish, int rows, size_t lds, hipStream_t st)
+{
+    t.keys = ks.keys; t.oob = ks.oob; t.clr = ks.other; t.clrN = clrN;
+    t.done = publish ? h->done_d : nullptr; t.hostKeys = h->keys_hd; t.hostOob = h->keys_hd + 2 * h->cfg.maxWindows;
+    h->lastPublished = publish;
+    h->pollable = false;   // (the plain single-window Update sets it afterwards; the rest fetch behind a stream wait)
+    t.seq = ++h->seq;
+    t.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], rows, 2);
+    t.lds = lds; t.st = st;
+}
+
+// Launch finish: cur advances only after a launch that succeeded (a call that fails earlier must not skip a clearing)
+static int launch_finish(dpe_bcm *h, int use)
+{
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        h->pollable = false;   // nothing will ever write the sequence word of this Update
+        dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
+        return -1;
+    }
+    h->cur = use;
+    return 0;
+}
+
 // win_host == nullptr: one window whose coefficients bcm_prep_kernel has already written to h->sv_d on `stream`
 // (dpe_bcm_update_dev) -- nothing the host decides below may then depend on their values.
 static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *carrBank_dev, int32_t nWindows, int32_t nChan,
@@ -1480,24 +1610,11 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] Update: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_update_epochs");
     DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] Update: this handle scans SV subsets (dpe_bcm_create_subsets): use dpe_bcm_update_subsets");
     DPE_REQUIRE(!h->refine, "[BatchCorrManifold] Update: this handle scans coarse-to-fine levels (dpe_bcm_create_refine): use dpe_bcm_update_refine");
-    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] Update: nWindows %d out of range", nWindows);
-    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
+    if (check_windows(h, "Update", nWindows) || check_chan(h, "Update", nChan) || (!dev && check_sign("Update", win_host, nWindows))) return -1;
     hipStream_t stream = (hipStream_t)stream_;
-    const int L = h->cfg.lagHalfWidth, B = h->cfg.binHalfWidth;
     const int maxK = h->cfg.maxChannels, W = h->cfg.maxWindows;
     bool posInside = !dev, velInside = !dev;   // every index provably inside the banks?  (device parameters: not known here)
-    h->lastDev = dev;
-    h->slot = (h->slot + 1) % dpe_bcm::kStaging;          // next staging block; an Update kStaging calls ago may still be copying it
-    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
-    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * h->cfg.maxWindows * h->cfg.maxChannels;
-    for (int w = 0; !dev && w < nWindows; ++w) {
-        const dpe_bcm_window &win = win_host[w];
-        DPE_REQUIRE(win.dopplerSign == 1 || win.dopplerSign == -1, "[BatchCorrManifold] Update: dopplerSign must be +/-1");
-        h->win_h[w] = win;
-        for (int k = 0; k < nChan; ++k)
-            bcm_expand(h, win, chan_host[(size_t)w * nChan + k], h->sv_h[(size_t)(0 * W + w) * maxK + k],
-                       h->sv_h[(size_t)(1 * W + w) * maxK + k], posInside, velInside);
-    }
+    if (stage_windows(h, win_host, chan_host, nWindows, nChan, posInside, velInside)) return -1;
     h->lastW = nWindows;
     long long axTiles[2] = {0, 0};
     AxesLaunch ax{};
@@ -1508,20 +1625,15 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
     }
     h->lastSplit[0] = scan_split(h->axes ? axTiles[0] * kPtsPerBlock : h->cfg.posGridSize, nWindows, h->splitForce);
     h->lastSplit[1] = scan_split(h->axes ? axTiles[1] * kPtsPerBlock : h->cfg.velGridSize, nWindows, h->splitForce);
-    // Two key / counter sets alternate between Updates: this call reduces into set `cur` (zero since it
-    // was cleared by the previous call's position scan, or by create) and clears the other one.
-    // (h->cur only advances once the launch is enqueued: a call that fails earlier must not skip a clearing)
-    const int use = h->cur ^ 1;
-    unsigned long long *keys = h->keys_d + (size_t)use * 4 * W, *oob = keys + 2 * W;
-    unsigned long long *other = h->keys_d + (size_t)(use ^ 1) * 4 * W;
+    const KeySet ks = next_key_set(h, h->keys_d, 4 * (size_t)W);
     GraphCache::Guard graphGuard{h->graphs, stream};
     if (h->graphs.enabled && !h->prof.enabled && !h->refPair && !dev) {
         const int rc = h->graphs.begin({codeBank_dev, carrBank_dev, 0, nWindows, nChan,
-                                        (posInside ? 1 : 0) | (velInside ? 2 : 0) | (use << 2) | (h->slot << 8), stream}, stream);
+                                        (posInside ? 1 : 0) | (velInside ? 2 : 0) | (ks.use << 2) | (h->slot << 8), stream}, stream);
         DPE_REQUIRE(rc >= 0, "[BatchCorrManifold] Update: hipGraph capture/replay failed");
         if (rc == 1) {
             DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));   // the replayed graph reads this slot
-            h->cur = use;
+            h->cur = ks.use;
             h->pollable = false;
             return 0;
         }
@@ -1535,38 +1647,26 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
         memcpy(pb.s[0], h->sv_h, sizeof(BcmSvDev) * nChan);
         memcpy(pb.s[1], h->sv_h + (size_t)W * maxK, sizeof(BcmSvDev) * nChan);
     } else {
-        if (h->graphs.capturing) DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sizeof(BcmSvDev) * 2 * (size_t)W * maxK, hipMemcpyHostToDevice, stream));
-        else upload_params(h->sv_d, h->svBase_hd + (h->sv_h - h->svBase_h), sizeof(BcmSvDev) * 2 * (size_t)W * maxK, stream);
+        if (h->graphs.capturing) DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sv_bytes(h), hipMemcpyHostToDevice, stream));
+        else upload_params(h->sv_d, h->svBase_hd + (h->sv_h - h->svBase_h), sv_bytes(h), stream);
         if (!h->graphs.capturing) DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
     }
-    const int nLag = 2 * L + 1, nBin = 2 * B + 1;
     ScanLaunch a;
     a.pb = pb; a.inl = inlineParams ? 1 : 0; a.K = nChan; a.maxK = maxK; a.lp = h->cfg.lPower;
-    a.sp = ScanSide{h->posGrid_d, reinterpret_cast<const float2 *>(codeBank_dev), h->sv_d, h->posScores_d,
-                    h->cfg.weightedMean ? h->wsum_d : nullptr, h->cfg.posGridSize, h->cfg.posGridIndexOffset, h->posPitch, nLag,
-                    (int)h->lastSplit[0]};
-    a.sv = ScanSide{h->velGrid_d, reinterpret_cast<const float2 *>(carrBank_dev), h->sv_d + (size_t)W * maxK, h->velScores_d,
-                    h->cfg.weightedMean ? h->wsum_d + h->wsumHalf : nullptr, h->cfg.velGridSize, h->cfg.velGridIndexOffset, h->velPitch, nBin,
-                    (int)h->lastSplit[1]};
-    a.keys = keys; a.oob = oob; a.clr = other; a.clrN = 4 * W;
+    scan_sides(h, codeBank_dev, carrBank_dev, a.sp, a.sv);
     const bool publishNow = h->publish || !dev || h->cfg.weightedMean;   // (only the device-parameter forms may skip it)
-    a.done = publishNow ? h->done_d : nullptr; a.hostKeys = h->keys_hd; a.hostOob = h->keys_hd + 2 * W;
-    h->lastPublished = publishNow;
-    a.seq = ++h->seq;
+    fill_tail(h, a, ks, 4 * W, publishNow, nWindows, (size_t)nChan * n_ent_max(h->cfg) * (h->compact ? 12 : 16), stream);
     // (a replayed graph carries a stale sequence argument: polling only for eager single-window launches whose mirror
     //  has the sequence word right behind the results, i.e. maxWindows == 1)
     // (with the weighted-mean estimator the per-block sums are fetched with a copy after the results arrive: that copy must
     //  see the finished kernel, so the stream is waited for instead)
     h->pollable = nWindows == 1 && W == 1 && !h->graphs.capturing && h->pollAllowed && !h->cfg.weightedMean && publishNow;
-    a.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], nWindows, 2);
-    a.lds = (size_t)nChan * (nLag > nBin ? nLag : nBin) * (h->compact ? 12 : 16);
-    a.st = stream;
     // the kernel's last block writes keys and counts into the pinned host mirror: dpe_bcm_results only
     // has to synchronise
     h->prof.begin(0, stream);
     if (h->axes) {
         ax.a = a;
-        ax.a.lds = (size_t)nChan * (nLag > nBin ? nLag : nBin) * 16 + kAxStageBytes;
+        ax.a.lds = (size_t)nChan * n_ent_max(h->cfg) * 16 + kAxStageBytes;
         ax.sp.bank = a.sp.bank; ax.sp.sv = a.sp.sv; ax.sp.scores = a.sp.scores; ax.sp.wsum = a.sp.wsum;
         ax.sp.pitch = a.sp.pitch; ax.sp.nEnt = a.sp.nEnt; ax.sp.split = a.sp.split;
         ax.sv.bank = a.sv.bank; ax.sv.sv = a.sv.sv; ax.sv.scores = a.sv.scores; ax.sv.wsum = a.sv.wsum;
@@ -1579,18 +1679,10 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
     const bool captured = h->graphs.capturing;
     DPE_REQUIRE(h->graphs.end(stream) == 0, "[BatchCorrManifold] Update: hipGraph instantiate/launch failed");
     if (captured) DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
-    {
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) {
-            h->pollable = false;   // nothing will ever write the sequence word of this Update
-            dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
-            return -1;
-        }
-    }
-    h->cur = use;
+    if (launch_finish(h, ks.use)) return -1;
     if (h->refPair && !dev) {
         h->pollable = false;
-        if (ref_pair_fixup(h, codeBank_dev, nWindows, nChan, chan_host, keys, stream)) return -1;
+        if (ref_pair_fixup(h, codeBank_dev, nWindows, nChan, chan_host, ks.keys, stream)) return -1;
     } else if (h->refPair) {
         // device-parameter form (dpe_bcm_update_dev): candidates, re-evaluation, patch and arg-max all on the device, nothing read back
         h->pollable = false;
@@ -1609,11 +1701,11 @@ static int bcm_update_impl(dpe_bcm *h, const float *codeBank_dev, const float *c
                            h->cfg.maxChannels, h->cfg.lagHalfWidth, 5e-4, h->refCand_d, h->refCap);
         hipLaunchKernelGGL(bcm_refpair_eval_kernel, dim3(64), dim3(64), 0, stream, h->refPorts, (int)nChan, h->refRxTime, h->refRxTime_d, h->cfg.samplingFrequency,
                            h->cfg.samplesPerWindow, h->cfg.lagHalfWidth, h->cfg.lPower, h->posGrid64_d, reinterpret_cast<const float2 *>(codeBank_dev),
-                           h->cfg.maxChannels, h->refCand_d, h->refCap, h->posScores_d, h->posPitch, h->devWin_hd + use, h->refPatched_d);
-        hipLaunchKernelGGL(bcm_zero_pos_keys_kernel, dim3(1), dim3(64), 0, stream, keys, 1);
+                           h->cfg.maxChannels, h->refCand_d, h->refCap, h->posScores_d, h->posPitch, h->devWin_hd + ks.use, h->refPatched_d);
+        hipLaunchKernelGGL(bcm_zero_pos_keys_kernel, dim3(1), dim3(64), 0, stream, ks.keys, 1);
         const unsigned gr = (unsigned)((G + 256 * 16 - 1) / (256 * 16));
         hipLaunchKernelGGL(bcm_rekey_kernel, dim3(gr > 512 ? 512 : gr, 1), dim3(256), 0, stream, h->posScores_d, G, h->posPitch,
-                           (long long)h->cfg.posGridIndexOffset, keys);
+                           (long long)h->cfg.posGridIndexOffset, ks.keys);
         DPE_CHECK_HIP(hipGetLastError());
         h->lastPublished = false;   // (the pinned mirror holds the scan's keys from before the patch: the results call fetches the re-derived ones)
     }
@@ -1632,8 +1724,7 @@ int dpe_bcm_update_joint(dpe_bcm *h, int32_t nWindows, int32_t nRx, const dpe_bc
 {
     using namespace dpe;
     DPE_REQUIRE(h && rx, "[BatchCorrManifold] update_joint: null argument");
-    DPE_REQUIRE(h->joint, "[BatchCorrManifold] update_joint: the handle was not made by dpe_bcm_create_joint");
-    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] update_joint: nWindows %d out of range", nWindows);
+    if (check_kind(h->joint, "update_joint", "dpe_bcm_create_joint") || check_windows(h, "update_joint", nWindows)) return -1;
     DPE_REQUIRE(nRx >= 1 && nRx <= h->jointMaxRx, "[BatchCorrManifold] update_joint: nRx %d out of range (the handle holds %d receivers)", nRx, h->jointMaxRx);
     hipStream_t stream = (hipStream_t)stream_;
     const int W = h->cfg.maxWindows, maxRx = h->jointMaxRx, maxKT = h->jointMaxK;
@@ -1645,7 +1736,7 @@ int dpe_bcm_update_joint(dpe_bcm *h, int32_t nWindows, int32_t nRx, const dpe_bc
             DPE_REQUIRE(x.codeBank_dev && x.carrBank_dev && x.chan_host, "[BatchCorrManifold] update_joint: window %d receiver %d: null pointer", w, r);
             DPE_REQUIRE(x.nChan >= 1 && x.nChan <= h->cfg.maxChannels, "[BatchCorrManifold] update_joint: window %d receiver %d: nChan %d out of range (1 .. %d)",
                         w, r, x.nChan, h->cfg.maxChannels);
-            DPE_REQUIRE(x.win.dopplerSign == 1 || x.win.dopplerSign == -1, "[BatchCorrManifold] update_joint: dopplerSign must be +/-1");
+            if (check_sign("update_joint", &x.win, 1)) return -1;
             DPE_REQUIRE(memcmp(x.win.enu2ecef, rx[(size_t)w * nRx].win.enu2ecef, sizeof(x.win.enu2ecef)) == 0,
                         "[BatchCorrManifold] update_joint: window %d: receiver %d's enu2ecef differs from receiver 0's (one grid offset must mean one "
                         "ECEF displacement for every receiver: pass bit-equal matrices)", w, r);
@@ -1654,10 +1745,7 @@ int dpe_bcm_update_joint(dpe_bcm *h, int32_t nWindows, int32_t nRx, const dpe_bc
         DPE_REQUIRE(total <= maxKT, "[BatchCorrManifold] update_joint: window %d has %d (receiver, SV) pairs, the handle holds %d", w, total, maxKT);
     }
     bool posInside = true, velInside = true;
-    h->lastDev = false;
-    h->slot = (h->slot + 1) % dpe_bcm::kStaging;
-    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
-    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * W * maxKT;
+    if (stage_begin(h, false)) return -1;
     JointRxDev *jrx_h = h->jrxBase_h + (size_t)h->slot * W * maxRx;
     int ldsRows = 0;
     for (int w = 0; w < nWindows; ++w) {
@@ -1666,9 +1754,7 @@ int dpe_bcm_update_joint(dpe_bcm *h, int32_t nWindows, int32_t nRx, const dpe_bc
             const dpe_bcm_joint_rx &x = rx[(size_t)w * nRx + r];
             h->jwin_h[(size_t)w * maxRx + r] = x.win;
             // each expansion about its own receiver's centre, with that receiver's receive time
-            for (int k = 0; k < x.nChan; ++k)
-                bcm_expand(h, x.win, x.chan_host[k], h->sv_h[(size_t)(0 * W + w) * maxKT + kOff + k], h->sv_h[(size_t)(1 * W + w) * maxKT + kOff + k],
-                           posInside, velInside);
+            expand_window(h, w, x.win, x.chan_host, x.nChan, kOff, posInside, velInside);
             jrx_h[(size_t)w * maxRx + r] = JointRxDev{reinterpret_cast<const float2 *>(x.codeBank_dev), reinterpret_cast<const float2 *>(x.carrBank_dev),
                                                      x.nChan, kOff, 0, 0};
             kOff += x.nChan;
@@ -1680,39 +1766,21 @@ int dpe_bcm_update_joint(dpe_bcm *h, int32_t nWindows, int32_t nRx, const dpe_bc
     h->lastOwn = h->ownKeys;
     h->lastSplit[0] = scan_split(h->cfg.posGridSize, nWindows, h->splitForce);
     h->lastSplit[1] = scan_split(h->cfg.velGridSize, nWindows, h->splitForce);
-    const int use = h->cur ^ 1;
-    unsigned long long *keys = h->keys_d + (size_t)use * 4 * W, *oob = keys + 2 * W;
-    unsigned long long *other = h->keys_d + (size_t)(use ^ 1) * 4 * W;
-    DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sizeof(BcmSvDev) * 2 * (size_t)W * maxKT, hipMemcpyHostToDevice, stream));
+    const KeySet ks = next_key_set(h, h->keys_d, 4 * (size_t)W);
+    DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sv_bytes(h), hipMemcpyHostToDevice, stream));
     DPE_CHECK_HIP(hipMemcpyAsync(h->jrx_d, jrx_h, sizeof(JointRxDev) * (size_t)W * maxRx, hipMemcpyHostToDevice, stream));
     DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
     DPE_CHECK_HIP(hipMemsetAsync(h->own_d, 0, sizeof(unsigned long long) * 4 * (size_t)W * maxRx, stream));
-    const int nLag = 2 * h->cfg.lagHalfWidth + 1, nBin = 2 * h->cfg.binHalfWidth + 1;
     JointLaunch a;
-    a.sp = ScanSide{h->posGrid_d, nullptr, h->sv_d, h->posScores_d, nullptr, h->cfg.posGridSize, 0, h->posPitch, nLag, (int)h->lastSplit[0]};
-    a.sv = ScanSide{h->velGrid_d, nullptr, h->sv_d + (size_t)W * maxKT, h->velScores_d, nullptr, h->cfg.velGridSize, 0, h->velPitch, nBin,
-                    (int)h->lastSplit[1]};
+    scan_sides(h, nullptr, nullptr, a.sp, a.sv);   // (the banks are per receiver: a.rx)
     a.rx = h->jrx_d; a.nRx = nRx; a.maxRx = maxRx; a.maxKT = maxKT; a.lp = h->cfg.lPower;
-    a.keys = keys; a.oob = oob; a.ownKeys = h->own_d; a.ownOob = h->own_d + 2 * (size_t)W * maxRx; a.clr = other; a.clrN = 4 * W;
-    a.done = h->done_d; a.hostKeys = h->keys_hd; a.hostOob = h->keys_hd + 2 * W;
-    h->lastPublished = true;
-    a.seq = ++h->seq;
-    h->pollable = false;   // (the per-receiver results are fetched behind a stream wait)
-    a.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], nWindows, 2);
-    a.lds = (size_t)ldsRows * (nLag > nBin ? nLag : nBin) * 16;   // <= maxKT rows: inside the budget create checked
-    a.st = stream;
+    a.ownKeys = h->own_d; a.ownOob = h->own_d + 2 * (size_t)W * maxRx;
+    // (<= maxKT rows of LDS: inside the budget create checked)
+    fill_tail(h, a, ks, 4 * W, true, nWindows, (size_t)ldsRows * n_ent_max(h->cfg) * 16, stream);
     h->prof.begin(0, stream);
     launch_joint(!posInside, !velInside, h->lastOwn, a);
     h->prof.end(0, stream);
-    {
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) {
-            dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
-            return -1;
-        }
-    }
-    h->cur = use;
-    return 0;
+    return launch_finish(h, ks.use);
 }
 
 // N consecutive windows per group: one launch scores, per grid point, every (window, SV) pair of the group, in passes of whole
@@ -1722,68 +1790,36 @@ int dpe_bcm_update_epochs(dpe_bcm *h, const float *codeBank_dev, const float *ca
 {
     using namespace dpe;
     DPE_REQUIRE(h && codeBank_dev && carrBank_dev && win_host && chan_host, "[BatchCorrManifold] update_epochs: null argument");
-    DPE_REQUIRE(h->epochs, "[BatchCorrManifold] update_epochs: the handle was not made by dpe_bcm_create_epochs");
+    if (check_kind(h->epochs, "update_epochs", "dpe_bcm_create_epochs")) return -1;
     // everything is checked before anything is staged or launched
     DPE_REQUIRE(nEpochs >= 1 && nEpochs <= h->epMaxEpochs, "[BatchCorrManifold] update_epochs: nEpochs %d out of range (the handle holds %d windows per group)",
                 nEpochs, h->epMaxEpochs);
     DPE_REQUIRE(nGroups >= 1 && (long long)nGroups * nEpochs <= h->cfg.maxWindows,
                 "[BatchCorrManifold] update_epochs: %d groups of %d windows out of range (maxWindows %d)", nGroups, nEpochs, h->cfg.maxWindows);
-    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] update_epochs: nChan %d out of range", nChan);
     const int nWin = nGroups * nEpochs;
-    for (int w = 0; w < nWin; ++w)
-        DPE_REQUIRE(win_host[w].dopplerSign == 1 || win_host[w].dopplerSign == -1, "[BatchCorrManifold] update_epochs: dopplerSign must be +/-1");
+    if (check_chan(h, "update_epochs", nChan) || check_sign("update_epochs", win_host, nWin)) return -1;
     hipStream_t stream = (hipStream_t)stream_;
     const int maxK = h->cfg.maxChannels, W = h->cfg.maxWindows;
     bool posInside = true, velInside = true;
-    h->lastDev = false;
-    h->slot = (h->slot + 1) % dpe_bcm::kStaging;
-    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
-    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * W * maxK;
-    for (int w = 0; w < nWin; ++w) {
-        h->win_h[w] = win_host[w];
-        // each expansion about its own window's centre, with that window's matrix and receive time
-        for (int k = 0; k < nChan; ++k)
-            bcm_expand(h, win_host[w], chan_host[(size_t)w * nChan + k], h->sv_h[(size_t)(0 * W + w) * maxK + k], h->sv_h[(size_t)(1 * W + w) * maxK + k],
-                       posInside, velInside);
-    }
+    if (stage_windows(h, win_host, chan_host, nWin, nChan, posInside, velInside)) return -1;
     const int winPerPass = std::min(h->epPairsPerPass / nChan, (int)nEpochs);   // >= 1: epPairsPerPass >= maxChannels >= nChan
     h->lastW = nGroups;
     h->lastEpochs = nEpochs;
     h->lastPasses = (nEpochs + winPerPass - 1) / winPerPass;
     h->lastSplit[0] = scan_split(h->cfg.posGridSize, nGroups, h->splitForce);
     h->lastSplit[1] = scan_split(h->cfg.velGridSize, nGroups, h->splitForce);
-    const int use = h->cur ^ 1;
-    unsigned long long *keys = h->keys_d + (size_t)use * 4 * W, *oob = keys + 2 * W;
-    unsigned long long *other = h->keys_d + (size_t)(use ^ 1) * 4 * W;
-    DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sizeof(BcmSvDev) * 2 * (size_t)W * maxK, hipMemcpyHostToDevice, stream));
+    const KeySet ks = next_key_set(h, h->keys_d, 4 * (size_t)W);
+    DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sv_bytes(h), hipMemcpyHostToDevice, stream));
     DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
-    const int nLag = 2 * h->cfg.lagHalfWidth + 1, nBin = 2 * h->cfg.binHalfWidth + 1;
     EpochsLaunch a;
-    a.sp = ScanSide{h->posGrid_d, reinterpret_cast<const float2 *>(codeBank_dev), h->sv_d, h->posScores_d, nullptr, h->cfg.posGridSize, 0, h->posPitch, nLag,
-                    (int)h->lastSplit[0]};
-    a.sv = ScanSide{h->velGrid_d, reinterpret_cast<const float2 *>(carrBank_dev), h->sv_d + (size_t)W * maxK, h->velScores_d, nullptr, h->cfg.velGridSize, 0,
-                    h->velPitch, nBin, (int)h->lastSplit[1]};
+    scan_sides(h, codeBank_dev, carrBank_dev, a.sp, a.sv);
     a.nEpochs = nEpochs; a.winPerPass = winPerPass; a.K = nChan; a.maxK = maxK; a.lp = h->cfg.lPower;
-    a.keys = keys; a.oob = oob; a.clr = other; a.clrN = 4 * W;
-    a.done = h->done_d; a.hostKeys = h->keys_hd; a.hostOob = h->keys_hd + 2 * W;
-    h->lastPublished = true;
-    a.seq = ++h->seq;
-    h->pollable = false;
-    a.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], nGroups, 2);
-    a.lds = (size_t)winPerPass * nChan * (nLag > nBin ? nLag : nBin) * 16;   // <= epPairsPerPass pairs: inside the budget create checked
-    a.st = stream;
+    // (<= epPairsPerPass pairs in LDS: inside the budget create checked)
+    fill_tail(h, a, ks, 4 * W, true, nGroups, (size_t)winPerPass * nChan * n_ent_max(h->cfg) * 16, stream);
     h->prof.begin(0, stream);
     launch_epochs(!posInside, !velInside, a);
     h->prof.end(0, stream);
-    {
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) {
-            dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
-            return -1;
-        }
-    }
-    h->cur = use;
-    return 0;
+    return launch_finish(h, ks.use);
 }
 
 // One launch scores every (point, SV) pair once and reduces the full set and every subset to its own first maximum
@@ -1794,15 +1830,15 @@ int dpe_bcm_update_subsets(dpe_bcm *h, const float *codeBank_dev, const float *c
 {
     using namespace dpe;
     DPE_REQUIRE(h && codeBank_dev && carrBank_dev && win_host && chan_host, "[BatchCorrManifold] update_subsets: null argument");
-    DPE_REQUIRE(h->subsets, "[BatchCorrManifold] update_subsets: the handle was not made by dpe_bcm_create_subsets");
     // everything is checked before anything is staged or launched
-    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] update_subsets: nWindows %d out of range", nWindows);
-    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] update_subsets: nChan %d out of range", nChan);
+    if (check_kind(h->subsets, "update_subsets", "dpe_bcm_create_subsets") || check_windows(h, "update_subsets", nWindows) ||
+        check_chan(h, "update_subsets", nChan))
+        return -1;
     DPE_REQUIRE(nSubsets >= 0 && nSubsets <= h->subMax, "[BatchCorrManifold] update_subsets: nSubsets %d out of range (the handle holds %d subsets per window)",
                 nSubsets, h->subMax);
     DPE_REQUIRE(nSubsets == 0 || masks_host, "[BatchCorrManifold] update_subsets: null masks");
     for (int w = 0; w < nWindows; ++w) {
-        DPE_REQUIRE(win_host[w].dopplerSign == 1 || win_host[w].dopplerSign == -1, "[BatchCorrManifold] update_subsets: dopplerSign must be +/-1");
+        if (check_sign("update_subsets", win_host + w, 1)) return -1;
         for (int m = 0; m < nSubsets; ++m) {
             const uint64_t mask = masks_host[(size_t)w * nSubsets + m];
             DPE_REQUIRE(mask != 0, "[BatchCorrManifold] update_subsets: window %d subset %d: empty mask", w, m);
@@ -1813,16 +1849,9 @@ int dpe_bcm_update_subsets(dpe_bcm *h, const float *codeBank_dev, const float *c
     hipStream_t stream = (hipStream_t)stream_;
     const int maxK = h->cfg.maxChannels, W = h->cfg.maxWindows, maxS = h->subMax;
     bool posInside = true, velInside = true;
-    h->lastDev = false;
-    h->slot = (h->slot + 1) % dpe_bcm::kStaging;
-    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
-    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * W * maxK;
+    if (stage_windows(h, win_host, chan_host, nWindows, nChan, posInside, velInside)) return -1;
     unsigned long long *mask_h = h->subMaskBase_h + (size_t)h->slot * W * maxS;
     for (int w = 0; w < nWindows; ++w) {
-        h->win_h[w] = win_host[w];
-        for (int k = 0; k < nChan; ++k)
-            bcm_expand(h, win_host[w], chan_host[(size_t)w * nChan + k], h->sv_h[(size_t)(0 * W + w) * maxK + k], h->sv_h[(size_t)(1 * W + w) * maxK + k],
-                       posInside, velInside);
         for (int m = 0; m < maxS; ++m)
             h->subMask_h[(size_t)w * maxS + m] = mask_h[(size_t)w * maxS + m] = m < nSubsets ? masks_host[(size_t)w * nSubsets + m] : 0ull;
     }
@@ -1831,11 +1860,9 @@ int dpe_bcm_update_subsets(dpe_bcm *h, const float *codeBank_dev, const float *c
     h->lastChan = nChan;
     h->lastSplit[0] = scan_split(h->cfg.posGridSize, nWindows, h->splitForce);
     h->lastSplit[1] = scan_split(h->cfg.velGridSize, nWindows, h->splitForce);
-    const int use = h->cur ^ 1;
-    unsigned long long *keys = h->keys_d + (size_t)use * 4 * W, *oob = keys + 2 * W;
-    unsigned long long *other = h->keys_d + (size_t)(use ^ 1) * 4 * W;
+    const KeySet ks = next_key_set(h, h->keys_d, 4 * (size_t)W);
     unsigned long long *masks_d = h->sub_d, *subKeys_d = masks_d + (size_t)W * maxS, *svOob_d = subKeys_d + 2 * (size_t)W * maxS;
-    DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sizeof(BcmSvDev) * 2 * (size_t)W * maxK, hipMemcpyHostToDevice, stream));
+    DPE_CHECK_HIP(hipMemcpyAsync(h->sv_d, h->sv_h, sv_bytes(h), hipMemcpyHostToDevice, stream));
     // nSubsets = 0 with every index inside the banks is the plain scan on the launch side as well: no mask copy, nothing to clear
     // (the kernel then touches neither the subset keys nor the per-SV counters, which the results call reports as 0)
     if (nSubsets > 0) DPE_CHECK_HIP(hipMemcpyAsync(masks_d, mask_h, sizeof(unsigned long long) * (size_t)W * maxS, hipMemcpyHostToDevice, stream));
@@ -1843,34 +1870,16 @@ int dpe_bcm_update_subsets(dpe_bcm *h, const float *codeBank_dev, const float *c
     h->lastCounted = !posInside || !velInside;
     if (nSubsets > 0) DPE_CHECK_HIP(hipMemsetAsync(subKeys_d, 0, sizeof(unsigned long long) * (2 * (size_t)W * maxS + 2 * (size_t)W * maxK), stream));
     else if (h->lastCounted) DPE_CHECK_HIP(hipMemsetAsync(svOob_d, 0, sizeof(unsigned long long) * 2 * (size_t)W * maxK, stream));
-    const int nLag = 2 * h->cfg.lagHalfWidth + 1, nBin = 2 * h->cfg.binHalfWidth + 1;
     SubsetsLaunch a;
-    a.sp = ScanSide{h->posGrid_d, reinterpret_cast<const float2 *>(codeBank_dev), h->sv_d, h->posScores_d, nullptr, h->cfg.posGridSize, 0, h->posPitch, nLag,
-                    (int)h->lastSplit[0]};
-    a.sv = ScanSide{h->velGrid_d, reinterpret_cast<const float2 *>(carrBank_dev), h->sv_d + (size_t)W * maxK, h->velScores_d, nullptr, h->cfg.velGridSize, 0,
-                    h->velPitch, nBin, (int)h->lastSplit[1]};
+    scan_sides(h, codeBank_dev, carrBank_dev, a.sp, a.sv);
     a.K = nChan; a.maxK = maxK; a.lp = h->cfg.lPower; a.nSubsets = nSubsets; a.maxSubsets = maxS;
     a.masks = masks_d; a.subKeys = subKeys_d; a.svOob = svOob_d;
-    a.keys = keys; a.oob = oob; a.clr = other; a.clrN = 4 * W;
-    a.done = h->done_d; a.hostKeys = h->keys_hd; a.hostOob = h->keys_hd + 2 * W;
-    h->lastPublished = true;
-    a.seq = ++h->seq;
-    h->pollable = false;   // (the per-subset results are fetched behind a stream wait)
-    a.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], nWindows, 2);
-    a.lds = (size_t)nChan * (nLag > nBin ? nLag : nBin) * 16;   // <= maxChannels rows: inside the budget create checked
-    a.st = stream;
+    // (<= maxChannels rows of LDS: inside the budget create checked)
+    fill_tail(h, a, ks, 4 * W, true, nWindows, (size_t)nChan * n_ent_max(h->cfg) * 16, stream);
     h->prof.begin(0, stream);
     launch_subsets(!posInside, !velInside, a);
     h->prof.end(0, stream);
-    {
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) {
-            dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
-            return -1;
-        }
-    }
-    h->cur = use;
-    return 0;
+    return launch_finish(h, ks.use);
 }
 
 // One launch per level, in stream order; level l >= 1 takes its centre from level l-1's key in device memory (dpe_bcm_refine.h).
@@ -1880,31 +1889,18 @@ int dpe_bcm_update_refine(dpe_bcm *h, const float *codeBank_dev, const float *ca
 {
     using namespace dpe;
     DPE_REQUIRE(h && codeBank_dev && carrBank_dev && win_host && chan_host, "[BatchCorrManifold] update_refine: null argument");
-    DPE_REQUIRE(h->refine, "[BatchCorrManifold] update_refine: the handle was not made by dpe_bcm_create_refine");
     // everything is checked before anything is staged or launched
-    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrManifold] update_refine: nWindows %d out of range", nWindows);
-    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] update_refine: nChan %d out of range", nChan);
-    for (int w = 0; w < nWindows; ++w)
-        DPE_REQUIRE(win_host[w].dopplerSign == 1 || win_host[w].dopplerSign == -1, "[BatchCorrManifold] update_refine: dopplerSign must be +/-1");
+    if (check_kind(h->refine, "update_refine", "dpe_bcm_create_refine") || check_windows(h, "update_refine", nWindows) ||
+        check_chan(h, "update_refine", nChan) || check_sign("update_refine", win_host, nWindows))
+        return -1;
     hipStream_t stream = (hipStream_t)stream_;
     const int maxK = h->cfg.maxChannels, W = h->cfg.maxWindows, nL = h->rfLevels;
     bool posInside = true, velInside = true;
-    h->lastDev = false;
-    h->slot = (h->slot + 1) % dpe_bcm::kStaging;
-    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
-    h->sv_h = h->svBase_h + (size_t)h->slot * 2 * W * maxK;
-    for (int w = 0; w < nWindows; ++w) {
-        h->win_h[w] = win_host[w];
-        for (int k = 0; k < nChan; ++k)
-            bcm_expand(h, win_host[w], chan_host[(size_t)w * nChan + k], h->sv_h[(size_t)(0 * W + w) * maxK + k], h->sv_h[(size_t)(1 * W + w) * maxK + k],
-                       posInside, velInside);
-    }
+    if (stage_windows(h, win_host, chan_host, nWindows, nChan, posInside, velInside)) return -1;
     h->lastW = nWindows;
-    const int use = h->cur ^ 1;
     const size_t setLen = 4 * (size_t)W * nL;   // {keys [levels][W][2], counts [levels][W][2]}
-    unsigned long long *keys = h->rfKeys_d + (size_t)use * setLen, *oob = keys + 2 * (size_t)W * nL;
-    unsigned long long *other = h->rfKeys_d + (size_t)(use ^ 1) * setLen;
-    upload_params(h->sv_d, h->svBase_hd + (h->sv_h - h->svBase_h), sizeof(BcmSvDev) * 2 * (size_t)W * maxK, stream);
+    const KeySet ks = next_key_set(h, h->rfKeys_d, setLen);
+    upload_params(h->sv_d, h->svBase_hd + (h->sv_h - h->svBase_h), sv_bytes(h), stream);
     DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
     const int nLag = 2 * h->cfg.lagHalfWidth + 1, nBin = 2 * h->cfg.binHalfWidth + 1;
     h->pollable = false;
@@ -1942,26 +1938,20 @@ int dpe_bcm_update_refine(dpe_bcm *h, const float *codeBank_dev, const float *ca
             s.split = (int)h->lastSplit[m];
         }
         a.level = l; a.K = nChan; a.maxK = maxK; a.lp = h->cfg.lPower;
-        a.keys = keys + (size_t)l * 2 * W; a.oob = oob + (size_t)l * 2 * W;
-        a.prevKeys = l ? keys + (size_t)(l - 1) * 2 * W : nullptr;
+        a.prevKeys = l ? ks.keys + (size_t)(l - 1) * 2 * W : nullptr;
         a.centres = h->rfCentre_d + (size_t)l * W * 8;
         a.prevCentres = l ? h->rfCentre_d + (size_t)(l - 1) * W * 8 : nullptr;
-        a.clr = other; a.clrN = l == 0 ? (int)setLen : 0;
+        // this level's rows of the set; nothing is published (no fill_tail: of the tail only these are used, and seq stays);
+        // the whole other set is cleared once, by level 0
+        a.keys = ks.keys + (size_t)l * 2 * W; a.oob = ks.oob + (size_t)l * 2 * W;
+        a.clr = ks.other; a.clrN = l == 0 ? (int)setLen : 0;
         a.grid = dim3(h->lastSplit[0] > h->lastSplit[1] ? h->lastSplit[0] : h->lastSplit[1], nWindows, 2);
-        a.lds = (size_t)nChan * (nLag > nBin ? nLag : nBin) * 16 + kAxStageBytes;
+        a.lds = (size_t)nChan * n_ent_max(h->cfg) * 16 + kAxStageBytes;
         a.st = stream;
         launch_refine(!posInside, !velInside, a);
     }
     h->prof.end(0, stream);
-    {
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) {
-            dpe::set_error("%s:%d: launch failed -> %s", __FILE__, __LINE__, hipGetErrorString(le));
-            return -1;
-        }
-    }
-    h->cur = use;
-    return 0;
+    return launch_finish(h, ks.use);
 }
 
 int dpe_bcm_joint_set_own_keys(dpe_bcm *h, int32_t enable)
@@ -1980,7 +1970,7 @@ int dpe_bcm_update_dev(dpe_bcm *h, const float *codeBank_dev, const float *carrB
     DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] Update: this handle sums consecutive windows (dpe_bcm_create_epochs): use dpe_bcm_update_epochs");
     DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] Update: this handle scans SV subsets (dpe_bcm_create_subsets): use dpe_bcm_update_subsets");
     DPE_REQUIRE(!h->refine, "[BatchCorrManifold] Update: this handle scans coarse-to-fine levels (dpe_bcm_create_refine): use dpe_bcm_update_refine");   // (before the prep kernel)
-    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
+    if (check_chan(h, "Update", nChan)) return -1;
     DPE_REQUIRE(!h->refPair || (h->cfg.writeScores && !h->cfg.weightedMean),
                 "[BatchCorrManifold] Update: referencePair with the device ports patches the scores on the device: it needs writeScores and no weightedMean "
                 "(the weighted sums are corrected on the host in the host form only)");
@@ -2004,7 +1994,7 @@ int dpe_bcm_update_prepared(dpe_bcm *h, const float *codeBank_dev, const float *
     DPE_REQUIRE(h, "[BatchCorrManifold] Update: null argument");
     DPE_REQUIRE(!h->joint, "[BatchCorrManifold] Update: this handle scans several receivers (dpe_bcm_create_joint): use dpe_bcm_update_joint");
     DPE_REQUIRE(!h->refine, "[BatchCorrManifold] Update: this handle scans coarse-to-fine levels (dpe_bcm_create_refine): use dpe_bcm_update_refine");
-    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrManifold] Update: nChan %d out of range", nChan);
+    if (check_chan(h, "Update", nChan)) return -1;
     // referencePair (batchcorrmanifold.cu:1798-1812): the prepared blocks hold expansion coefficients only, so the fp64 re-evaluation
     // reads the port arrays of the channel manager that wrote them (handed over at dpe_chm_dev_attach) -- the same device-side
     // candidates / re-evaluation / patch / arg-max kernels as dpe_bcm_update_dev, nothing read back
@@ -2141,6 +2131,31 @@ static void decode_key(unsigned long long key, float *score, int64_t *index)
     *index = (int64_t)(0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull));
 }
 
+// The arg-max fields the five result structs spell alike, from a key pair and its pair of out-of-window counts
+extern "C++" {   // (a template inside the C-ABI block)
+template <class R>
+static void fill_argmax(R &r, unsigned long long posKey, unsigned long long velKey, unsigned long long posOob, unsigned long long velOob)
+{
+    decode_key(posKey, &r.posScore, &r.posIndex);
+    decode_key(velKey, &r.velScore, &r.velIndex);
+    r.posOutOfWindow = (int64_t)posOob;
+    r.velOutOfWindow = (int64_t)velOob;
+}
+}
+
+// The point-list rows of an arg-max pair, range-checked (index -1, which only the subsets results form: no point of the row
+// had a score, a row of NaN), and the offset[8] they make
+static int fill_offset(const dpe_bcm *h, const char *who, int64_t posIndex, int64_t velIndex, double offset[8], const double **pp, const double **vp)
+{
+    static const double nan4[4] = {NAN, NAN, NAN, NAN};
+    DPE_REQUIRE(posIndex >= -1 && posIndex < h->cfg.posGridSize && velIndex >= -1 && velIndex < h->cfg.velGridSize,
+                "[BatchCorrManifold] %s: arg-max index outside the grids", who);
+    *pp = posIndex < 0 ? nan4 : h->posGrid_h.data() + 4 * posIndex;
+    *vp = velIndex < 0 ? nan4 : h->velGrid_h.data() + 4 * velIndex;
+    for (int c = 0; c < 4; ++c) { offset[c] = (*pp)[c]; offset[4 + c] = (*vp)[c]; }
+    return 0;
+}
+
 // Device-parameter Updates: the window's frame (xCurrkk1, ENU2ECEFMat, DopplerSign) came from device arrays; bcm_prep_kernel
 // left a copy in pinned memory ahead of the scan, valid once the stream has been waited for (or the result polled).
 static int fetch_device_frame(dpe_bcm *h)
@@ -2209,10 +2224,7 @@ int dpe_bcm_results(dpe_bcm *h, dpe_bcm_result *results, dpe_stream_t stream)
             const double vm[4] = {m[1][1] / m[1][0], m[1][2] / m[1][0], m[1][3] / m[1][0], m[1][4] / m[1][0]};
             make_meas(h->win_h[w], pm, vm, r.zValMean);
         }
-        decode_key(keys[2 * w], &r.posScore, &r.posIndex);
-        decode_key(keys[2 * w + 1], &r.velScore, &r.velIndex);
-        r.posOutOfWindow = (int64_t)oob[2 * w];
-        r.velOutOfWindow = (int64_t)oob[2 * w + 1];
+        fill_argmax(r, keys[2 * w], keys[2 * w + 1], oob[2 * w], oob[2 * w + 1]);
         const int64_t pl = r.posIndex - h->cfg.posGridIndexOffset, vl = r.velIndex - h->cfg.velGridIndexOffset;
         DPE_REQUIRE(pl >= 0 && pl < h->cfg.posGridSize && vl >= 0 && vl < h->cfg.velGridSize,
                     "[BatchCorrManifold] results: arg-max index outside the local shard");
@@ -2233,27 +2245,18 @@ int dpe_bcm_results_joint(dpe_bcm *h, dpe_bcm_joint_result *joint, dpe_bcm_joint
     const unsigned long long *keys = h->keys_h, *oob = h->oob_h;
     for (int w = 0; w < W; ++w) {
         dpe_bcm_joint_result &j = joint[w];
-        decode_key(keys[2 * w], &j.posScore, &j.posIndex);
-        decode_key(keys[2 * w + 1], &j.velScore, &j.velIndex);
-        j.posOutOfWindow = (int64_t)oob[2 * w];
-        j.velOutOfWindow = (int64_t)oob[2 * w + 1];
-        DPE_REQUIRE(j.posIndex >= 0 && j.posIndex < h->cfg.posGridSize && j.velIndex >= 0 && j.velIndex < h->cfg.velGridSize,
-                    "[BatchCorrManifold] results_joint: arg-max index outside the grids");
-        const double *pp = h->posGrid_h.data() + 4 * j.posIndex, *vp = h->velGrid_h.data() + 4 * j.velIndex;
-        for (int c = 0; c < 4; ++c) { j.offset[c] = pp[c]; j.offset[4 + c] = vp[c]; }
+        fill_argmax(j, keys[2 * w], keys[2 * w + 1], oob[2 * w], oob[2 * w + 1]);
+        const double *pp, *vp;
+        if (fill_offset(h, "results_joint", j.posIndex, j.velIndex, j.offset, &pp, &vp)) return -1;
         for (int r = 0; r < nRx; ++r) {
             dpe_bcm_joint_rx_result &o = perRx[(size_t)w * nRx + r];
             make_meas(h->jwin_h[(size_t)w * maxRx + r], pp, vp, o.zVal);   // this receiver's centre moved by the joint offset
             const size_t ps = ((size_t)w * 2 + 0) * maxRx + r, vs = ((size_t)w * 2 + 1) * maxRx + r;
-            if (h->lastOwn) {
-                decode_key(h->own_h[ps], &o.posScore, &o.posIndex);
-                decode_key(h->own_h[vs], &o.velScore, &o.velIndex);
-            } else {
+            fill_argmax(o, h->own_h[ps], h->own_h[vs], h->own_h[half + ps], h->own_h[half + vs]);
+            if (!h->lastOwn) {
                 o.posIndex = o.velIndex = -1;
                 o.posScore = o.velScore = 0.f;
             }
-            o.posOutOfWindow = (int64_t)h->own_h[half + ps];
-            o.velOutOfWindow = (int64_t)h->own_h[half + vs];
         }
     }
     return 0;
@@ -2262,22 +2265,17 @@ int dpe_bcm_results_joint(dpe_bcm *h, dpe_bcm_joint_result *joint, dpe_bcm_joint
 int dpe_bcm_results_epochs(dpe_bcm *h, dpe_bcm_epochs_result *results, dpe_stream_t stream)
 {
     DPE_REQUIRE(h && results, "[BatchCorrManifold] results_epochs: null argument");
-    DPE_REQUIRE(h->epochs, "[BatchCorrManifold] results_epochs: the handle was not made by dpe_bcm_create_epochs");
+    if (check_kind(h->epochs, "results_epochs", "dpe_bcm_create_epochs")) return -1;
     DPE_REQUIRE(h->lastW > 0 && h->lastEpochs > 0, "[BatchCorrManifold] results_epochs: no epochs update yet");
     DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
     const unsigned long long *keys = h->keys_h, *oob = h->oob_h;
     for (int g = 0; g < h->lastW; ++g) {
         dpe_bcm_epochs_result &r = results[g];
-        decode_key(keys[2 * g], &r.posScore, &r.posIndex);
-        decode_key(keys[2 * g + 1], &r.velScore, &r.velIndex);
-        r.posOutOfWindow = (int64_t)oob[2 * g];
-        r.velOutOfWindow = (int64_t)oob[2 * g + 1];
+        fill_argmax(r, keys[2 * g], keys[2 * g + 1], oob[2 * g], oob[2 * g + 1]);
         r.nPasses = h->lastPasses;
         r.reserved = 0;
-        DPE_REQUIRE(r.posIndex >= 0 && r.posIndex < h->cfg.posGridSize && r.velIndex >= 0 && r.velIndex < h->cfg.velGridSize,
-                    "[BatchCorrManifold] results_epochs: arg-max index outside the grids");
-        const double *pp = h->posGrid_h.data() + 4 * r.posIndex, *vp = h->velGrid_h.data() + 4 * r.velIndex;
-        for (int c = 0; c < 4; ++c) { r.offset[c] = pp[c]; r.offset[4 + c] = vp[c]; }
+        const double *pp, *vp;
+        if (fill_offset(h, "results_epochs", r.posIndex, r.velIndex, r.offset, &pp, &vp)) return -1;
         make_meas(h->win_h[(size_t)g * h->lastEpochs + h->lastEpochs - 1], pp, vp, r.zVal);   // the LAST window's centre moved by the ML offset
     }
     return 0;
@@ -2286,7 +2284,7 @@ int dpe_bcm_results_epochs(dpe_bcm *h, dpe_bcm_epochs_result *results, dpe_strea
 int dpe_bcm_results_subsets(dpe_bcm *h, dpe_bcm_subset_result *full, dpe_bcm_subset_result *subs, int64_t *oobPerSv, dpe_stream_t stream)
 {
     DPE_REQUIRE(h && full, "[BatchCorrManifold] results_subsets: null argument");
-    DPE_REQUIRE(h->subsets, "[BatchCorrManifold] results_subsets: the handle was not made by dpe_bcm_create_subsets");
+    if (check_kind(h->subsets, "results_subsets", "dpe_bcm_create_subsets")) return -1;
     DPE_REQUIRE(h->lastW > 0, "[BatchCorrManifold] results_subsets: no subsets update yet");
     DPE_REQUIRE(subs || h->lastSubsets == 0, "[BatchCorrManifold] results_subsets: null argument (the last Update ran %d subsets)", h->lastSubsets);
     DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
@@ -2302,35 +2300,28 @@ int dpe_bcm_results_subsets(dpe_bcm *h, dpe_bcm_subset_result *full, dpe_bcm_sub
     const unsigned long long *keys = h->keys_h, *oob = h->oob_h;
     // A key of 0 means that no point of the row had a score (every sum NaN: a channel with NaN banks in the set): index -1,
     // score 0 and NaN offsets / zVal for that manifold -- the other subsets of the window, which leave that channel out, stand.
-    const auto fill = [&](dpe_bcm_subset_result &r, int w, unsigned long long pk, unsigned long long vk) -> int {
-        const double nan4[4] = {NAN, NAN, NAN, NAN};
-        decode_key(pk, &r.posScore, &r.posIndex);
-        decode_key(vk, &r.velScore, &r.velIndex);
+    const auto fill = [&](dpe_bcm_subset_result &r, int w, unsigned long long pk, unsigned long long vk, unsigned long long pc, unsigned long long vc) -> int {
+        fill_argmax(r, pk, vk, pc, vc);
         if (!pk) { r.posIndex = -1; r.posScore = 0.f; }
         if (!vk) { r.velIndex = -1; r.velScore = 0.f; }
-        DPE_REQUIRE((!pk || (r.posIndex >= 0 && r.posIndex < h->cfg.posGridSize)) && (!vk || (r.velIndex >= 0 && r.velIndex < h->cfg.velGridSize)),
-                    "[BatchCorrManifold] results_subsets: arg-max index outside the grids");
-        const double *pp = pk ? h->posGrid_h.data() + 4 * r.posIndex : nan4, *vp = vk ? h->velGrid_h.data() + 4 * r.velIndex : nan4;
-        for (int c = 0; c < 4; ++c) { r.offset[c] = pp[c]; r.offset[4 + c] = vp[c]; }
+        const double *pp, *vp;
+        if (fill_offset(h, "results_subsets", r.posIndex, r.velIndex, r.offset, &pp, &vp)) return -1;
         make_meas(h->win_h[w], pp, vp, r.zVal);
         return 0;
     };
     for (int w = 0; w < W; ++w) {
-        if (fill(full[w], w, keys[2 * w], keys[2 * w + 1])) return -1;
-        full[w].posOutOfWindow = (int64_t)oob[2 * w];
-        full[w].velOutOfWindow = (int64_t)oob[2 * w + 1];
+        if (fill(full[w], w, keys[2 * w], keys[2 * w + 1], oob[2 * w], oob[2 * w + 1])) return -1;
         const unsigned long long *po = svOob + ((size_t)w * 2 + 0) * maxK, *vo = svOob + ((size_t)w * 2 + 1) * maxK;
         for (int k = 0; oobPerSv && k < K; ++k) {
             oobPerSv[((size_t)w * 2 + 0) * K + k] = (int64_t)po[k];
             oobPerSv[((size_t)w * 2 + 1) * K + k] = (int64_t)vo[k];
         }
         for (int m = 0; m < M; ++m) {
-            dpe_bcm_subset_result &r = subs[(size_t)w * M + m];
-            if (fill(r, w, subKeys[((size_t)w * 2 + 0) * maxS + m], subKeys[((size_t)w * 2 + 1) * maxS + m])) return -1;
             const unsigned long long mask = h->subMask_h[(size_t)w * maxS + m];
-            r.posOutOfWindow = r.velOutOfWindow = 0;
+            unsigned long long pc = 0, vc = 0;
             for (int k = 0; k < K; ++k)
-                if ((mask >> k) & 1ull) { r.posOutOfWindow += (int64_t)po[k]; r.velOutOfWindow += (int64_t)vo[k]; }   // a subset's count: the sum of its SVs'
+                if ((mask >> k) & 1ull) { pc += po[k]; vc += vo[k]; }   // a subset's count: the sum of its SVs'
+            if (fill(subs[(size_t)w * M + m], w, subKeys[((size_t)w * 2 + 0) * maxS + m], subKeys[((size_t)w * 2 + 1) * maxS + m], pc, vc)) return -1;
         }
     }
     return 0;
@@ -2339,7 +2330,7 @@ int dpe_bcm_results_subsets(dpe_bcm *h, dpe_bcm_subset_result *full, dpe_bcm_sub
 int dpe_bcm_results_refine(dpe_bcm *h, dpe_bcm_refine_result *results, dpe_stream_t stream)
 {
     DPE_REQUIRE(h && results, "[BatchCorrManifold] results_refine: null argument");
-    DPE_REQUIRE(h->refine, "[BatchCorrManifold] results_refine: the handle was not made by dpe_bcm_create_refine");
+    if (check_kind(h->refine, "results_refine", "dpe_bcm_create_refine")) return -1;
     DPE_REQUIRE(h->lastW > 0, "[BatchCorrManifold] results_refine: no refine update yet");
     DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
     const int W = h->lastW, nL = h->rfLevels;
@@ -2378,11 +2369,17 @@ int dpe_bcm_results_refine(dpe_bcm *h, dpe_bcm_refine_result *results, dpe_strea
     return 0;
 }
 
+static int check_refine_level(const dpe_bcm *h, const char *who, int level)
+{
+    if (check_kind(h->refine, who, "dpe_bcm_create_refine")) return -1;
+    DPE_REQUIRE(level >= 0 && level < h->rfLevels, "[BatchCorrManifold] %s: level %d out of range (the handle holds %d levels)", who, level, h->rfLevels);
+    return 0;
+}
+
 int dpe_bcm_refine_scores(dpe_bcm *h, int32_t level, const float **pos_dev, const float **vel_dev, int64_t *posPitch, int64_t *velPitch)
 {
     DPE_REQUIRE(h, "[BatchCorrManifold] refine_scores: null handle");
-    DPE_REQUIRE(h->refine, "[BatchCorrManifold] refine_scores: the handle was not made by dpe_bcm_create_refine");
-    DPE_REQUIRE(level >= 0 && level < h->rfLevels, "[BatchCorrManifold] refine_scores: level %d out of range (the handle holds %d levels)", level, h->rfLevels);
+    if (check_refine_level(h, "refine_scores", level)) return -1;
     DPE_REQUIRE(h->cfg.writeScores, "[BatchCorrManifold] refine_scores: created with writeScores=0");
     if (pos_dev) *pos_dev = h->rf[level].scores[0];
     if (vel_dev) *vel_dev = h->rf[level].scores[1];
@@ -2394,8 +2391,7 @@ int dpe_bcm_refine_scores(dpe_bcm *h, int32_t level, const float **pos_dev, cons
 int dpe_bcm_refine_keys(dpe_bcm *h, int32_t level, const uint64_t **keys_dev)
 {
     DPE_REQUIRE(h && keys_dev, "[BatchCorrManifold] refine_keys: null argument");
-    DPE_REQUIRE(h->refine, "[BatchCorrManifold] refine_keys: the handle was not made by dpe_bcm_create_refine");
-    DPE_REQUIRE(level >= 0 && level < h->rfLevels, "[BatchCorrManifold] refine_keys: level %d out of range (the handle holds %d levels)", level, h->rfLevels);
+    if (check_refine_level(h, "refine_keys", level)) return -1;
     const size_t W = h->cfg.maxWindows;
     *keys_dev = reinterpret_cast<const uint64_t *>(h->rfKeys_d + (size_t)h->cur * 4 * W * h->rfLevels + (size_t)level * 2 * W);
     return 0;

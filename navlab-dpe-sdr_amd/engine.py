@@ -465,6 +465,15 @@ class Comm:
             pass
 
 
+def _win_chan(win, chan):
+    """The win / chan arguments of a manifold's Update as contiguous arrays [W] and [W, K] -> (win, chan, W, K)."""
+    win = np.ascontiguousarray(np.atleast_1d(win))
+    chan = np.ascontiguousarray(chan)
+    if chan.ndim == 1:
+        chan = chan[None, :]
+    return (win, chan) + chan.shape
+
+
 class BatchCorrManifold:
     """Module "BatchCorrManifold" (batchcorrmanifold.cu:2247-2303): params PosGrid/VelGrid (host
     [G,4] ENU offsets, i.e. the LoadPosGrid path :2422-2448 generalised to both manifolds), LPower."""
@@ -502,19 +511,13 @@ class BatchCorrManifold:
         """win: BCM_WINDOW_DTYPE [W]; chan: CHAN_END_DTYPE [W,K]; banks: device pointers from BCS."""
         if not self.Started:
             raise DpeError("[BatchCorrManifold] Error: Update() Failed due to module not initialized")
-        win = np.ascontiguousarray(np.atleast_1d(win))
-        chan = np.ascontiguousarray(chan)
-        if chan.ndim == 1:
-            chan = chan[None, :]
-        W, K = chan.shape
+        win, chan, W, K = _win_chan(win, chan)
         assert win.shape[0] == W
         _check(lib().dpe_bcm_update(self._h, _ptr(CodeScores), _ptr(CarrScores), C.c_int32(W), C.c_int32(K),
                                     win.ctypes.data_as(C.POINTER(BcmWindow)),
                                     chan.ctypes.data_as(C.POINTER(ChanEnd)), _stream(stream)))
         self._W = W
-        keys = C.c_void_p()   # the key sets alternate between Updates: refresh the device pointer
-        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
-        self.Keys = keys.value
+        self._refresh_keys()
         return 0
 
     def UpdateDev(self, CodeScores, CarrScores, n_chan, ports, dim_t, rx_time, stream=None):
@@ -526,9 +529,7 @@ class BatchCorrManifold:
         _check(lib().dpe_bcm_update_dev(self._h, _ptr(CodeScores), _ptr(CarrScores), C.c_int32(n_chan), C.byref(p),
                                         C.c_double(rx_time), _stream(stream)))
         self._W = 1
-        keys = C.c_void_p()
-        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
-        self.Keys = keys.value
+        self._refresh_keys()
         return 0
 
     def UpdatePrepared(self, CodeScores, CarrScores, n_chan, stream=None):
@@ -610,6 +611,11 @@ class BatchCorrManifold:
             self.Started = False
         return 0
 
+    def _refresh_keys(self):
+        keys = C.c_void_p()   # the key sets alternate between Updates: refresh the device pointer
+        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
+        self.Keys = keys.value
+
     def _bind_outputs(self):
         self.PosScores = self.VelScores = None
         if self.write_scores:
@@ -619,9 +625,7 @@ class BatchCorrManifold:
         pp, vp = C.c_int64(), C.c_int64()
         _check(lib().dpe_bcm_scores_pitch(self._h, C.byref(pp), C.byref(vp)))
         self.PosScoresPitch, self.VelScoresPitch = pp.value, vp.value     # floats between the rows of consecutive windows
-        keys = C.c_void_p()
-        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
-        self.Keys = keys.value
+        self._refresh_keys()
         self.Started = True
         self._W = 0
 
@@ -701,9 +705,7 @@ class JointManifold(BatchCorrManifold):
         arr, _keep, W, nRx = rx if isinstance(rx, tuple) else self.pack(rx)
         _check(lib().dpe_bcm_update_joint(self._h, C.c_int32(W), C.c_int32(nRx), arr, _stream(stream)))
         self._W, self._nRx = W, nRx
-        keys = C.c_void_p()
-        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
-        self.Keys = keys.value
+        self._refresh_keys()
         return 0
 
     def results(self, stream=None):
@@ -761,11 +763,7 @@ class EpochManifold(BatchCorrManifold):
         of a BatchCorrScores updated with the same windows."""
         if not self.Started:
             raise DpeError("[BatchCorrManifold] Error: Update() Failed due to module not initialized")
-        win = np.ascontiguousarray(np.atleast_1d(win))
-        chan = np.ascontiguousarray(chan)
-        if chan.ndim == 1:
-            chan = chan[None, :]
-        W, K = chan.shape
+        win, chan, W, K = _win_chan(win, chan)
         n_epochs = int(n_epochs)
         if win.shape[0] != W or n_epochs < 1 or W % n_epochs:
             raise DpeError("[BatchCorrManifold] update_epochs: %d windows are not whole groups of %d" % (W, n_epochs))
@@ -773,9 +771,7 @@ class EpochManifold(BatchCorrManifold):
                                            C.c_int32(K), win.ctypes.data_as(C.POINTER(BcmWindow)),
                                            chan.ctypes.data_as(C.POINTER(ChanEnd)), _stream(stream)))
         self._W, self.n_epochs = W // n_epochs, n_epochs          # rows, keys and results are per GROUP
-        keys = C.c_void_p()
-        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
-        self.Keys = keys.value
+        self._refresh_keys()
         return 0
 
     def results(self, stream=None):
@@ -838,11 +834,7 @@ class SubsetManifold(BatchCorrManifold):
         None or empty: the plain scan."""
         if not self.Started:
             raise DpeError("[BatchCorrManifold] Error: Update() Failed due to module not initialized")
-        win = np.ascontiguousarray(np.atleast_1d(win))
-        chan = np.ascontiguousarray(chan)
-        if chan.ndim == 1:
-            chan = chan[None, :]
-        W, K = chan.shape
+        win, chan, W, K = _win_chan(win, chan)
         assert win.shape[0] == W
         masks = np.zeros((W, 0), dtype=np.uint64) if masks is None else np.asarray(masks, dtype=np.uint64)
         if masks.ndim == 1:
@@ -855,9 +847,7 @@ class SubsetManifold(BatchCorrManifold):
                                             win.ctypes.data_as(C.POINTER(BcmWindow)), chan.ctypes.data_as(C.POINTER(ChanEnd)),
                                             C.c_int32(M), masks.ctypes.data_as(C.POINTER(C.c_uint64)) if M else None, _stream(stream)))
         self._W, self._M, self._K = W, M, K
-        keys = C.c_void_p()
-        _check(lib().dpe_bcm_keys(self._h, C.byref(keys)))
-        self.Keys = keys.value
+        self._refresh_keys()
         return 0
 
     @staticmethod
@@ -925,11 +915,7 @@ class RefineManifold:
         """win: BCM_WINDOW_DTYPE [W]; chan: CHAN_END_DTYPE [W, K]; banks: device pointers from BatchCorrScores."""
         if not self.Started:
             raise DpeError("[BatchCorrManifold] Error: Update() Failed due to module not initialized")
-        win = np.ascontiguousarray(np.atleast_1d(win))
-        chan = np.ascontiguousarray(chan)
-        if chan.ndim == 1:
-            chan = chan[None, :]
-        W, K = chan.shape
+        win, chan, W, K = _win_chan(win, chan)
         assert win.shape[0] == W
         _check(lib().dpe_bcm_update_refine(self._h, _ptr(CodeScores), _ptr(CarrScores), C.c_int32(W), C.c_int32(K),
                                            win.ctypes.data_as(C.POINTER(BcmWindow)), chan.ctypes.data_as(C.POINTER(ChanEnd)),

@@ -1,6 +1,10 @@
 """Closed-loop DPE iteration on top of the C-ABI -- the Python twin of host/dpe_flow_main.cpp and of
 Flow::FlowThread's module order (cudarecv/dsp/src/flow.cu:122-137; dpeflow.cpp:55-62):
 SampleBlock -> BatchCorrScores -> BatchCorrManifold -> cuEKF(pass-through) -> cuChanMgr."""
+import contextlib
+import types
+from functools import partial
+
 import numpy as np
 
 from . import engine
@@ -26,6 +30,43 @@ def bank_half_widths_refine(levels, fs, nfft):
     return L, B
 
 
+@contextlib.contextmanager
+def _single_rx_loop(iq_windows, ho, fs, K, init_delta, half_widths, make_bcm, make_cm=None, lag_half_width=None, bin_half_width=None,
+                    max_windows=1):
+    """What the single-receiver closed loops open and close with.  half_widths(fs, nfft) -> (L, B) is the caller's rule (the
+    overrides win); make_bcm(S, nfft, L, B, K) constructs the manifold; make_cm(bcs, bcm, T, K) the channel manager once both
+    modules have started (default: the host ChanMgr from the handoff).  Yields a namespace: W, S, K, bcs, bcm, cm, iq_d (the
+    samples on the device) and x (X_ECEF + init_delta, 4 entries or all 8).  nfft is engine.carr_fft_len(S), the value a started
+    BatchCorrScores reports as NumFFTPoints.  Everything is stopped on the way out -- channel
+    manager, manifold, correlator -- whether or not the body raised."""
+    import torch
+    iq_windows = np.ascontiguousarray(iq_windows)
+    W, S2 = iq_windows.shape
+    S = S2 // 2
+    K = len(ho["prn_list"]) if K is None else K
+    nfft = engine.carr_fft_len(S)
+    L, B = half_widths(fs, nfft)
+    L = L if lag_half_width is None else int(lag_half_width)
+    B = B if bin_half_width is None else int(bin_half_width)
+    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_windows=max_windows, max_channels=K)
+    bcm = make_bcm(S, nfft, L, B, K)
+    cm = None
+    try:
+        bcs.Start()
+        bcm.Start()
+        cm = engine.ChanMgr.from_handoff(ho, S / fs, K) if make_cm is None else make_cm(bcs, bcm, S / fs, K)
+        x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
+        d0 = np.asarray(init_delta, dtype=np.float64)
+        x[:d0.shape[0]] += d0
+        iq_d = torch.from_numpy(iq_windows).to("cuda:0")
+        yield types.SimpleNamespace(W=W, S=S, K=K, bcs=bcs, bcm=bcm, cm=cm, iq_d=iq_d, x=x)
+    finally:      # an error in the middle of the loop must not leave device handles behind
+        if cm is not None:
+            cm.Stop()
+        bcm.Stop()
+        bcs.Stop()
+
+
 def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), init_delta=(0, 0, 0, 0), K=None,
                     lpower=1, enable_ekf=False, reference_pair=False, keep_scores=False, couple_velocity=True, doppler_sign=1):
     """iq_windows: int16 [W, 2S] (host).  Returns fixes [W, 8] (= xCurrk1k1 per window) and the raw
@@ -34,42 +75,34 @@ def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
     reference_pair: dpe_bcm_config.referencePair; keep_scores: every result dict also carries the window's position and velocity scores;
     couple_velocity: the filter's F couples position and velocity over one window (cuekf.cu:111-143) or is the identity (ekf.py:47).
     doppler_sign: the channel manager's DopplerSign (+1 / -1); the handoff's fi is the front end's own, the handoff names no sign."""
-    import torch
-    iq_windows = np.ascontiguousarray(iq_windows)
-    W, S2 = iq_windows.shape
-    S = S2 // 2
-    K = len(ho["prn_list"]) if K is None else K
-    nfft = engine.carr_fft_len(S)
-    L, B = bank_half_widths(pos_grid, vel_grid, fs, nfft)
-    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_channels=K)
-    bcs.Start()
-    bcm = engine.BatchCorrManifold(fs, S, bcs.NumFFTPoints, pos_grid, vel_grid, LPower=lpower, lag_half_width=L,
-                                   bin_half_width=B, max_channels=K, reference_pair=reference_pair)
-    bcm.Start()
-    cm = engine.ChanMgr.from_handoff(ho, S / fs, K, DopplerSign=doppler_sign)
-    x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
-    x[:4] += np.asarray(init_delta, dtype=np.float64)
-    iq_d = torch.from_numpy(iq_windows).to("cuda:0")
-    fixes, results = np.zeros((W, 8)), []
-    ekf = engine.cuEKF(x, SampleLength=S / fs, EnableEKF=enable_ekf, couple_velocity=couple_velocity)
-    xk1k1, xkk1 = x, x
-    for w in range(W):
-        (cm.Start if w == 0 else cm.Update)(xk1k1, xkk1, time_grid)
-        cs, ce, bw = cm.outputs()
-        bcs.Update(iq_d[w], cs)
-        bcm.Update(bcs.CodeScores, bcs.CarrScores, bw, ce)
-        r = bcm.results()[0]
-        if keep_scores:
-            ps, vs = bcm.read_scores()
-            r["posScores"], r["velScores"] = ps[0].copy(), vs[0].copy()
-        ekf.Update(r["zVal"], r["RVal"])    # EKF_PassMeas (the ML point is the new state) or the filter
-        xk1k1, xkk1 = ekf.xCurrk1k1.copy(), ekf.xCurrkk1.copy()
-        fixes[w] = xk1k1
-        results.append(r)
-    ekf.Stop()
-    cm.Stop()
-    bcm.Stop()
-    bcs.Stop()
+    def make_bcm(S, nfft, L, B, K):
+        return engine.BatchCorrManifold(fs, S, nfft, pos_grid, vel_grid, LPower=lpower, lag_half_width=L, bin_half_width=B,
+                                        max_channels=K, reference_pair=reference_pair)
+
+    def make_cm(bcs, bcm, T, K):
+        return engine.ChanMgr.from_handoff(ho, T, K, DopplerSign=doppler_sign)
+
+    with _single_rx_loop(iq_windows, ho, fs, K, init_delta, partial(bank_half_widths, pos_grid, vel_grid), make_bcm, make_cm) as lp:
+        bcs, bcm, cm = lp.bcs, lp.bcm, lp.cm
+        fixes, results = np.zeros((lp.W, 8)), []
+        ekf = engine.cuEKF(lp.x, SampleLength=lp.S / fs, EnableEKF=enable_ekf, couple_velocity=couple_velocity)
+        try:
+            xk1k1, xkk1 = lp.x, lp.x
+            for w in range(lp.W):
+                (cm.Start if w == 0 else cm.Update)(xk1k1, xkk1, time_grid)
+                cs, ce, bw = cm.outputs()
+                bcs.Update(lp.iq_d[w], cs)
+                bcm.Update(bcs.CodeScores, bcs.CarrScores, bw, ce)
+                r = bcm.results()[0]
+                if keep_scores:
+                    ps, vs = bcm.read_scores()
+                    r["posScores"], r["velScores"] = ps[0].copy(), vs[0].copy()
+                ekf.Update(r["zVal"], r["RVal"])    # EKF_PassMeas (the ML point is the new state) or the filter
+                xk1k1, xkk1 = ekf.xCurrk1k1.copy(), ekf.xCurrkk1.copy()
+                fixes[w] = xk1k1
+                results.append(r)
+        finally:
+            ekf.Stop()
     return fixes, results
 
 
@@ -85,53 +118,48 @@ def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
     window was scored with (`inputs` = ChanMgrDev.outputs() before the window) -- the loop then does read back.
     enable_ekf: cuEKF's filter inside the measurement kernel (dpe_chm_dev_set_ekf) instead of the pass-through; the fixes are then x_k|k.
     doppler_sign: the channel manager's DopplerSign, as in run_closed_loop."""
-    import torch
-    iq_windows = np.ascontiguousarray(iq_windows)
-    W, S2 = iq_windows.shape
-    S = S2 // 2
-    K = len(ho["prn_list"]) if K is None else K
-    nfft = engine.carr_fft_len(S)
-    L, B = bank_half_widths(pos_grid, vel_grid, fs, nfft)
-    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_channels=K)
-    bcs.Start()
-    bcm = engine.BatchCorrManifold(fs, S, bcs.NumFFTPoints, pos_grid, vel_grid, LPower=lpower, lag_half_width=L,
-                                   bin_half_width=B, max_channels=K, reference_pair=reference_pair)
-    bcm.Start()
-    cm = engine.ChanMgrDev.from_handoff(ho, S / fs, K, time_grid, DopplerSign=doppler_sign)
-    cm.attach(bcs, bcm, ring_depth)
-    x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
-    x[:4] += np.asarray(init_delta, dtype=np.float64)
-    iq_d = torch.from_numpy(iq_windows).to("cuda:0")
-    if enable_ekf:
-        cm.set_ekf(S / fs, x, couple_velocity=couple_velocity)
-    cm.Start(x, stream)
-    fixes, results, got = np.zeros((W, 8)), [], 0
-    for w in range(W):
-        while w - got >= ring_depth - 1:          # never more than the ring holds ahead of the fixes already collected
-            results.append(cm.fix(got))
-            got += 1
-        inputs = cm.outputs(stream=stream) if keep_scores else None     # (the previous window's time update has run: fix() flushed it)
-        bcs.UpdatePrepared(iq_d[w], K, stream)
-        bcm.UpdatePrepared(bcs.CodeScores, bcs.CarrScores, K, stream)
-        cm.step(stream)
-        if keep_scores:
-            while got <= w:
+    def make_bcm(S, nfft, L, B, K):
+        return engine.BatchCorrManifold(fs, S, nfft, pos_grid, vel_grid, LPower=lpower, lag_half_width=L, bin_half_width=B,
+                                        max_channels=K, reference_pair=reference_pair)
+
+    def make_cm(bcs, bcm, T, K):
+        cm = engine.ChanMgrDev.from_handoff(ho, T, K, time_grid, DopplerSign=doppler_sign)
+        try:
+            cm.attach(bcs, bcm, ring_depth)
+        except Exception:      # (the helper only stops a manager that make_cm returned)
+            cm.Stop()
+            raise
+        return cm
+
+    with _single_rx_loop(iq_windows, ho, fs, K, init_delta, partial(bank_half_widths, pos_grid, vel_grid), make_bcm, make_cm) as lp:
+        bcs, bcm, cm, W, K = lp.bcs, lp.bcm, lp.cm, lp.W, lp.K
+        if enable_ekf:
+            cm.set_ekf(lp.S / fs, lp.x, couple_velocity=couple_velocity)
+        cm.Start(lp.x, stream)
+        fixes, results, got = np.zeros((W, 8)), [], 0
+        for w in range(W):
+            while w - got >= ring_depth - 1:          # never more than the ring holds ahead of the fixes already collected
                 results.append(cm.fix(got))
                 got += 1
-            ps, vs = bcm.read_scores(stream)
-            results[w]["posScores"], results[w]["velScores"] = ps[0].copy(), vs[0].copy()
-            results[w]["codeBank"] = bcs.read_banks(stream)[0][0].copy()
-            results[w]["inputs"] = inputs
-    while got < W:
-        results.append(cm.fix(got))
-        got += 1
-    for w, r in enumerate(results):
-        fixes[w] = r["zVal"]
-    cm.outputs()
-    status = cm.status
-    cm.Stop()
-    bcm.Stop()
-    bcs.Stop()
+            inputs = cm.outputs(stream=stream) if keep_scores else None     # (the previous window's time update has run: fix() flushed it)
+            bcs.UpdatePrepared(lp.iq_d[w], K, stream)
+            bcm.UpdatePrepared(bcs.CodeScores, bcs.CarrScores, K, stream)
+            cm.step(stream)
+            if keep_scores:
+                while got <= w:
+                    results.append(cm.fix(got))
+                    got += 1
+                ps, vs = bcm.read_scores(stream)
+                results[w]["posScores"], results[w]["velScores"] = ps[0].copy(), vs[0].copy()
+                results[w]["codeBank"] = bcs.read_banks(stream)[0][0].copy()
+                results[w]["inputs"] = inputs
+        while got < W:
+            results.append(cm.fix(got))
+            got += 1
+        for w, r in enumerate(results):
+            fixes[w] = r["zVal"]
+        cm.outputs()
+        status = cm.status
     return fixes, results, status
 
 
@@ -217,37 +245,26 @@ def run_epoch_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, n_epochs, time
     arg-max.  The group's zVal -- its last window's centre moved by the ML offset -- is the state the next group starts from
     (pass-through filter).  A trailing group may be shorter.  n_epochs = 1 is run_closed_loop, bit for bit.
     Returns fixes [ceil(W / n_epochs), 8] and the per-group result dicts."""
-    import torch
-    iq_windows = np.ascontiguousarray(iq_windows)
-    W, S2 = iq_windows.shape
-    S, n = S2 // 2, int(n_epochs)
-    K = len(ho["prn_list"]) if K is None else K
-    nfft = engine.carr_fft_len(S)
-    L, B = bank_half_widths(pos_grid, vel_grid, fs, nfft)
-    L = L if lag_half_width is None else int(lag_half_width)
-    B = B if bin_half_width is None else int(bin_half_width)
-    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_windows=n, max_channels=K)
-    bcm = engine.EpochManifold(fs, S, nfft, pos_grid, vel_grid, n, pairs_per_pass, LPower=lpower, lag_half_width=L, bin_half_width=B,
-                               max_channels=K)
-    cm = None
-    try:
-        bcs.Start()
-        bcm.Start()
-        cm = engine.ChanMgr.from_handoff(ho, S / fs, K)
-        x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
-        x[:4] += np.asarray(init_delta, dtype=np.float64)
-        iq_d = torch.from_numpy(iq_windows).to("cuda:0")
+    n = int(n_epochs)
+
+    def make_bcm(S, nfft, L, B, K):
+        return engine.EpochManifold(fs, S, nfft, pos_grid, vel_grid, n, pairs_per_pass, LPower=lpower, lag_half_width=L, bin_half_width=B,
+                                    max_channels=K)
+
+    with _single_rx_loop(iq_windows, ho, fs, K, init_delta, partial(bank_half_widths, pos_grid, vel_grid), make_bcm,
+                         lag_half_width=lag_half_width, bin_half_width=bin_half_width, max_windows=n) as lp:
+        bcs, bcm, cm, x = lp.bcs, lp.bcm, lp.cm, lp.x
         fixes, results = [], []
-        for g0 in range(0, W, n):
-            m = min(n, W - g0)
+        for g0 in range(0, lp.W, n):
+            m = min(n, lp.W - g0)
             cs, ce, bw = [], [], []
             for e in range(m):
                 if e:
-                    x = predict_state(x, S / fs)
+                    x = predict_state(x, lp.S / fs)
                 (cm.Start if g0 + e == 0 else cm.Update)(x, x, time_grid)
                 s_, e_, w_ = cm.outputs()
                 cs.append(s_); ce.append(e_); bw.append(w_)
-            bcs.Update(iq_d[g0:g0 + m], np.stack(cs))
+            bcs.Update(lp.iq_d[g0:g0 + m], np.stack(cs))
             bcm.Update(bcs.CodeScores, bcs.CarrScores, np.concatenate(bw), np.stack(ce), m)
             r = bcm.results()[0]
             if keep_scores:
@@ -256,11 +273,6 @@ def run_epoch_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, n_epochs, time
             x = r["zVal"].copy()
             fixes.append(x)
             results.append(r)
-    finally:
-        if cm is not None:
-            cm.Stop()
-        bcm.Stop()
-        bcs.Stop()
     return np.stack(fixes), results
 
 
@@ -272,30 +284,17 @@ def run_refine_closed_loop(iq_windows, ho, fs, levels, time_grid=(0.0,), init_de
     (DESIGN.md 2.4g).  keep_scores: every result dict carries posScores / velScores, lists of the levels' rows; keep_banks: also
     the window's codeBank / carrBank [K, 2L+1] / [K, 2B+1] complex64 and `inputs` = the channel manager's outputs it was scored with.
     Returns fixes [W, 8] and the per-window result dicts."""
-    import torch
-    iq_windows = np.ascontiguousarray(iq_windows)
-    W, S2 = iq_windows.shape
-    S = S2 // 2
-    K = len(ho["prn_list"]) if K is None else K
-    nfft = engine.carr_fft_len(S)
-    L, B = bank_half_widths_refine(levels, fs, nfft)
-    L = L if lag_half_width is None else int(lag_half_width)
-    B = B if bin_half_width is None else int(bin_half_width)
-    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_channels=K)
-    bcm = engine.RefineManifold(fs, S, nfft, levels, LPower=lpower, lag_half_width=L, bin_half_width=B, max_channels=K)
-    cm = None
-    try:
-        bcs.Start()
-        bcm.Start()
-        cm = engine.ChanMgr.from_handoff(ho, S / fs, K)
-        x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
-        x[:4] += np.asarray(init_delta, dtype=np.float64)
-        iq_d = torch.from_numpy(iq_windows).to("cuda:0")
-        fixes, results = np.zeros((W, 8)), []
-        for w in range(W):
+    def make_bcm(S, nfft, L, B, K):
+        return engine.RefineManifold(fs, S, nfft, levels, LPower=lpower, lag_half_width=L, bin_half_width=B, max_channels=K)
+
+    with _single_rx_loop(iq_windows, ho, fs, K, init_delta, partial(bank_half_widths_refine, levels), make_bcm,
+                         lag_half_width=lag_half_width, bin_half_width=bin_half_width) as lp:
+        bcs, bcm, cm, x = lp.bcs, lp.bcm, lp.cm, lp.x
+        fixes, results = np.zeros((lp.W, 8)), []
+        for w in range(lp.W):
             (cm.Start if w == 0 else cm.Update)(x, x, time_grid)
             cs, ce, bw = cm.outputs()
-            bcs.Update(iq_d[w], cs)
+            bcs.Update(lp.iq_d[w], cs)
             bcm.Update(bcs.CodeScores, bcs.CarrScores, bw, ce)
             r = bcm.results()[0]
             if keep_scores:
@@ -307,11 +306,6 @@ def run_refine_closed_loop(iq_windows, ho, fs, levels, time_grid=(0.0,), init_de
             x = r["zVal"].copy()
             fixes[w] = x
             results.append(r)
-    finally:
-        if cm is not None:
-            cm.Stop()
-        bcm.Stop()
-        bcs.Stop()
     return fixes, results
 
 
@@ -350,32 +344,18 @@ def run_fde_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, threshold_m, tim
     chosen fix; nothing is remembered from one window to the next (exclude=False: suspects are logged, the fix stays the full
     set's).  init_delta: ECEF / clock offset of the initial state, 4 entries, or 8 with the velocity and drift.
     Returns fixes [W, 8], suspects int [W], separations [W, K] and the per-window result dicts."""
-    import torch
-    iq_windows = np.ascontiguousarray(iq_windows)
-    W, S2 = iq_windows.shape
-    S = S2 // 2
-    K = len(ho["prn_list"]) if K is None else K
-    nfft = engine.carr_fft_len(S)
-    L, B = bank_half_widths(pos_grid, vel_grid, fs, nfft)
-    L = L if lag_half_width is None else int(lag_half_width)
-    B = B if bin_half_width is None else int(bin_half_width)
-    masks = engine.leave_one_out_masks(K)
-    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_channels=K)
-    bcm = engine.SubsetManifold(fs, S, nfft, pos_grid, vel_grid, K, LPower=lpower, lag_half_width=L, bin_half_width=B, max_channels=K)
-    cm = None
-    try:
-        bcs.Start()
-        bcm.Start()
-        cm = engine.ChanMgr.from_handoff(ho, S / fs, K)
-        x = np.array(ho["X_ECEF"], dtype=np.float64).copy()
-        d0 = np.asarray(init_delta, dtype=np.float64)
-        x[:d0.shape[0]] += d0                                  # 4 entries (position, clock) or all 8 of the state
-        iq_d = torch.from_numpy(iq_windows).to("cuda:0")
+    def make_bcm(S, nfft, L, B, K):
+        return engine.SubsetManifold(fs, S, nfft, pos_grid, vel_grid, K, LPower=lpower, lag_half_width=L, bin_half_width=B, max_channels=K)
+
+    with _single_rx_loop(iq_windows, ho, fs, K, init_delta, partial(bank_half_widths, pos_grid, vel_grid), make_bcm,
+                         lag_half_width=lag_half_width, bin_half_width=bin_half_width) as lp:
+        bcs, bcm, cm, x, W, K = lp.bcs, lp.bcm, lp.cm, lp.x, lp.W, lp.K
+        masks = engine.leave_one_out_masks(K)
         fixes, suspects, seps, results = np.zeros((W, 8)), np.full(W, -1, dtype=np.int64), np.zeros((W, K)), []
         for w in range(W):
             (cm.Start if w == 0 else cm.Update)(x, x, time_grid)
             cs, ce, bw = cm.outputs()
-            bcs.Update(iq_d[w], cs)
+            bcs.Update(lp.iq_d[w], cs)
             bcm.Update(bcs.CodeScores, bcs.CarrScores, bw, ce, masks)
             r = bcm.results()[0]
             if keep_scores:
@@ -387,11 +367,6 @@ def run_fde_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, threshold_m, tim
             x = chosen["zVal"].copy()
             fixes[w] = x
             results.append(r)
-    finally:
-        if cm is not None:
-            cm.Stop()
-        bcm.Stop()
-        bcs.Stop()
     return fixes, suspects, seps, results
 
 
