@@ -514,6 +514,53 @@ int dpe_bcm_refine_scores(dpe_bcm *h, int32_t level, const float **pos_dev, cons
 /* Level `level`'s packed keys of the LAST Update (the two sets alternate: query after every Update), device uint64 [maxWindows][2]. */
 int dpe_bcm_refine_keys(dpe_bcm *h, int32_t level, const uint64_t **keys_dev);
 
+/* ---- manifold moments: thresholded mean and covariance from the score rows (csrc/dpe_bcm_moments.h) ----
+ * The reference reports the identity as RVal (batchcorrmanifold.cu:2003-2011).  This stage, a launch of its own BEHIND the scan on the
+ * same stream, turns each window's score rows into the zeroth, first and second moments of the thresholded weights
+ *     w_i = s_i > tau ? (double)s_i - (double)tau : 0,   tau = (float)rho[m] * smax  (one fp32 multiply),
+ * smax = the fp32 in the high word of the window's key (the row's maximum, already on the device: no read-back).  A NaN score fails the
+ * compare and contributes nothing.  sums[m] = sum_i w_i {1, x, y, z, t, xx, xy, xz, xt, yy, yz, yt, zz, zt, tt} over the LOCAL points, with
+ * (x, y, z, t) the fp32 offsets the scan scored, about the grid origin (the window centre): sums of shards add.  Every product and
+ * accumulation is fp64; the reduction order is fixed by the launch geometry (no atomics), so a repeated call returns the same bits.
+ * Supported: point-list and axes handles (dpe_bcm_create / _create_axes and their dpe_pipe lanes), after dpe_bcm_update, _update_dev
+ * or _update_prepared.  Refused, each with a message: a call before the first Update; rho outside [0, 1) or not finite; the handle's own
+ * rows on a writeScores = 0 handle; nWindows beyond the last Update's count (beyond maxWindows when rows AND keys are overridden); an
+ * override with a pitch below the grid size; joint, epochs, subsets and refine handles; a stream that is being captured.
+ * The call reads keys, counts and scores and writes none of them, nor the mirror dpe_bcm_results reads; its own buffers are allocated
+ * on first use. */
+typedef struct dpe_bcm_moments_config {
+    double rho[2];                 /* 0 <= rho < 1 per manifold; 0 = raw-score weights */
+    const uint64_t *keys_dev;      /* [nWindows][2] keys to take each row's maximum from; NULL = the last Update's own
+                                      (after dpe_bcm_exchange_keys: the exchanged set, so shards share one threshold) */
+    const float *posScores_dev, *velScores_dev;   /* rows to read instead of the handle's own; NULL = own (needs writeScores) */
+    int64_t posPitch, velPitch;    /* floats between rows of the override; ignored where the pointer is NULL */
+    int32_t nWindows;              /* 0 = the last Update's count */
+    int32_t reserved;
+} dpe_bcm_moments_config;
+
+typedef struct dpe_bcm_moments_result {
+    double sums[2][15];
+    int64_t nAbove[2];             /* points with s_i > tau */
+    float threshold[2];            /* tau */
+    double zValMom[8];             /* centre + J mu, as zValMean is formed; NaN where S0 == 0 */
+    double RValMom[64];            /* row-major, blockdiag(J C_pos J^T, J C_vel J^T), J = blockdiag(enu2ecef, 1),
+                                      C = S2/S0 - mu mu^T, both triangles written from one value; NaN block where S0 == 0 */
+} dpe_bcm_moments_result;
+
+/* Asynchronous, behind the Update on the same stream: one launch over (blocks per row, nWindows, 2) and a one-pass reduction. */
+int dpe_bcm_moments(dpe_bcm *h, const dpe_bcm_moments_config *cfg, dpe_stream_t stream);
+/* Waits for `stream` and decodes the pinned mirror of the last dpe_bcm_moments; out: [its nWindows].  The window frames (centre,
+ * enu2ecef) are those of the last Update: collect before the next one.  A window beyond the last Update's count (rows and keys
+ * overridden) has sums but no frame: its zValMom and RValMom are NaN (use dpe_bcm_moments_from_sums with a frame of your own). */
+int dpe_bcm_moments_results(dpe_bcm *h, dpe_bcm_moments_result *out, dpe_stream_t stream);
+/* The device copies: double [maxWindows][2][15] and int64 [maxWindows][2] (valid behind the call on its stream; all-reduce the sums of
+ * shards from here). */
+int dpe_bcm_moments_dev(dpe_bcm *h, const double **sums_dev, const int64_t **nAbove_dev);
+/* Host only, for all-reduced shard sums: mean and covariance of both manifolds from their sums, moved into the frame of zVal.
+ * C is evaluated as (S2 - mu S1^T) / S0, which equals S2/S0 - mu mu^T and is exactly 0 for a single point. */
+int dpe_bcm_moments_from_sums(const double sums[2][15], const double centre[8], const double enu2ecef[9],
+                              double zValMom[8], double RValMom[64]);
+
 /* ------------------------------------------------------------------ batches in flight ------ */
 /* Several batches of the path on the device at once -- what the reference gets from SampleBlock's 32-slot ring and reader thread
  * (sampleblock.cu:327-447) and from the side streams of BatchCorrScores / BatchCorrManifold (batchcorrscores.h:60-64,

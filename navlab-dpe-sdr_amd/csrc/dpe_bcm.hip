@@ -279,6 +279,7 @@ __global__ __launch_bounds__(256) void bcm_scan_kernel(BcmParamBlock pb, int inl
 #include "dpe_bcm_joint.h"
 #include "dpe_bcm_epochs.h"
 #include "dpe_bcm_subsets.h"
+#include "dpe_bcm_moments.h"
 
 namespace dpe {
 
@@ -548,6 +549,12 @@ struct dpe_bcm {
     unsigned long long *rfKeys_d = nullptr;   // [2 sets][{keys [levels][W][2], counts [levels][W][2]}], alternating between Updates
     float *rfCentre_d = nullptr;              // [levels][W][2][4]: the fp32 centre each level scanned around
     std::vector<unsigned long long> rfKeys_h; // one set: the last Update's keys and counts (dpe_bcm_results_refine)
+    // thresholded moments of the score rows (dpe_bcm_moments): everything here is allocated by the first call, not at create
+    double *momPartial_d = nullptr;           // [W][2][blocks per row][kMomSlots] per-block partials of the last call
+    double *momSums_d = nullptr;              // [maxWindows][2][15]
+    long long *momAbove_d = nullptr;          // [maxWindows][2]
+    dpe::MomMirror *momMirror_h = nullptr, *momMirror_hd = nullptr;   // pinned [maxWindows][2], filled on the stream
+    int momW = 0;                             // windows of the last call
     dpe::KernelProfiler prof;  // slot 0: the fused position + velocity scan
     dpe::GraphCache graphs;
 };
@@ -1433,6 +1440,8 @@ int dpe_bcm_destroy(dpe_bcm *h)
     (void)hipFree(h->rfKeys_d); (void)hipFree(h->rfCentre_d);
     for (auto &lv : h->rf) { (void)hipFree(lv.scores[0]); (void)hipFree(lv.scores[1]); }
     (void)hipFree(h->refCand_d); (void)hipFree(h->refWhere_d); (void)hipFree(h->refValue_d); (void)hipFree(h->refOld_d);
+    (void)hipFree(h->momPartial_d); (void)hipFree(h->momSums_d); (void)hipFree(h->momAbove_d);
+    if (h->momMirror_h) (void)hipHostFree(h->momMirror_h);
     for (hipEvent_t e : h->stagingFree)
         if (e) (void)hipEventDestroy(e);
     h->graphs.clear();
@@ -2512,6 +2521,174 @@ int dpe_bcm_results_from_keys(dpe_bcm *h, const uint64_t *keys_host, int32_t nWi
         make_meas(h->win_h[w], posGridGlobal ? posGridGlobal + 4 * r.posIndex : grid_point(h, 0, r.posIndex, pt),
                   velGridGlobal ? velGridGlobal + 4 * r.velIndex : grid_point(h, 1, r.velIndex, vt), r.zVal);
     }
+    return 0;
+}
+
+// ---- thresholded moments of the score rows (dpe_bcm_moments.h) ----------------
+// Blocks along x per row, by scan_split's rule of thumb: 128 for one or two windows (latency), 24 for batches, never more than
+// the row's 1024-point tiles
+static unsigned moments_split(long long G, int nWindows)
+{
+    const long long nTiles = (G + dpe::kPtsPerBlock - 1) / dpe::kPtsPerBlock;
+    const long long s = nWindows <= 2 ? 128 : 24;
+    return (unsigned)(s < nTiles ? s : nTiles);
+}
+
+static size_t moments_partial_len(int maxWindows)   // doubles: >= nWindows * 2 * blocks per row * kMomSlots of any launch
+{
+    const size_t rows = (size_t)std::max(2 * 128, 24 * maxWindows);
+    return 2 * rows * dpe::kMomSlots;
+}
+
+int dpe_bcm_moments(dpe_bcm *h, const dpe_bcm_moments_config *cfg, dpe_stream_t stream_)
+{
+    using namespace dpe;
+    DPE_REQUIRE(cfg, "[BatchCorrManifold] moments: null config");
+    for (int m = 0; m < 2; ++m)
+        DPE_REQUIRE(std::isfinite(cfg->rho[m]) && cfg->rho[m] >= 0.0 && cfg->rho[m] < 1.0,
+                    "[BatchCorrManifold] moments: rho[%d] = %g outside [0, 1) (%s manifold)", m, cfg->rho[m], m ? "velocity" : "position");
+    DPE_REQUIRE(h, "[BatchCorrManifold] moments: null handle");
+    DPE_REQUIRE(!h->joint, "[BatchCorrManifold] moments: a joint handle (dpe_bcm_create_joint) is not supported (its rows sum several receivers)");
+    DPE_REQUIRE(!h->epochs, "[BatchCorrManifold] moments: an epochs handle (dpe_bcm_create_epochs) is not supported (its rows sum several windows)");
+    DPE_REQUIRE(!h->subsets, "[BatchCorrManifold] moments: a subsets handle (dpe_bcm_create_subsets) is not supported (its keys are per subset)");
+    DPE_REQUIRE(!h->refine, "[BatchCorrManifold] moments: a refine handle (dpe_bcm_create_refine) is not supported (its rows and grids are per level)");
+    DPE_REQUIRE(h->lastW > 0, "[BatchCorrManifold] moments: no update yet");
+    hipStream_t stream = (hipStream_t)stream_;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (stream) (void)hipStreamIsCapturing(stream, &cap);
+    DPE_REQUIRE(!h->graphs.capturing && cap == hipStreamCaptureStatusNone,
+                "[BatchCorrManifold] moments: the stream is being captured (the call allocates on first use and is not part of the Update's graph)");
+    DPE_REQUIRE(h->cfg.writeScores || (cfg->posScores_dev && cfg->velScores_dev),
+                "[BatchCorrManifold] moments: created with writeScores=0 (the handle has no score rows: pass posScores_dev and velScores_dev)");
+    const int maxW = h->cfg.maxWindows;
+    const bool allOver = cfg->keys_dev && cfg->posScores_dev && cfg->velScores_dev;
+    const int nW = cfg->nWindows ? cfg->nWindows : h->lastW, limit = allOver ? maxW : h->lastW;
+    DPE_REQUIRE(nW >= 1 && nW <= limit, "[BatchCorrManifold] moments: nWindows %d out of range (1 .. %d: %s)", nW, limit,
+                allOver ? "maxWindows, rows and keys overridden" : "the last Update's count");
+    const long long G[2] = {h->cfg.posGridSize, h->cfg.velGridSize};
+    DPE_REQUIRE(!cfg->posScores_dev || cfg->posPitch >= G[0], "[BatchCorrManifold] moments: posPitch %lld is below the position grid size %lld",
+                (long long)cfg->posPitch, G[0]);
+    DPE_REQUIRE(!cfg->velScores_dev || cfg->velPitch >= G[1], "[BatchCorrManifold] moments: velPitch %lld is below the velocity grid size %lld",
+                (long long)cfg->velPitch, G[1]);
+    if (!h->momPartial_d) {   // first use
+        double *partial = dev_alloc<double>(moments_partial_len(maxW)), *sums = dev_alloc<double>((size_t)maxW * 2 * kMomSums);
+        long long *above = dev_alloc<long long>((size_t)maxW * 2);
+        MomMirror *mirror = nullptr, *mirrorDev = nullptr;
+        if (!partial || !sums || !above || hipHostMalloc((void **)&mirror, sizeof(MomMirror) * 2 * maxW, hipHostMallocDefault) != hipSuccess ||
+            hipHostGetDevicePointer((void **)&mirrorDev, mirror, 0) != hipSuccess) {
+            (void)hipFree(partial); (void)hipFree(sums); (void)hipFree(above);
+            if (mirror) (void)hipHostFree(mirror);
+            set_error("[BatchCorrManifold] moments: allocation failed");
+            return -1;
+        }
+        memset(mirror, 0, sizeof(MomMirror) * 2 * maxW);
+        h->momPartial_d = partial; h->momSums_d = sums; h->momAbove_d = above; h->momMirror_h = mirror; h->momMirror_hd = mirrorDev;
+    }
+    const unsigned long long *keys = cfg->keys_dev ? reinterpret_cast<const unsigned long long *>(cfg->keys_dev)
+                                                   : h->keys_d + (size_t)h->cur * 4 * maxW;
+    MomSide sd[2] = {};
+    for (int m = 0; m < 2; ++m) {
+        MomSide &s = sd[m];
+        const float *over = m ? cfg->velScores_dev : cfg->posScores_dev;
+        s.scores = over ? over : (m ? h->velScores_d : h->posScores_d);
+        s.pitch = over ? (long long)(m ? cfg->velPitch : cfg->posPitch) : (m ? h->velPitch : h->posPitch);
+        s.G = G[m];
+        s.vec = ((uintptr_t)s.scores % 16 == 0 && s.pitch % 4 == 0) ? 1 : 0;
+        s.rho = (float)cfg->rho[m];
+        s.split = (int)moments_split(G[m], nW);
+        if (h->axes) {
+            const dpe_bcm::Axes &ax = m ? h->velAx : h->posAx;
+            s.ax = h->axes_d;
+            s.offX = h->axOff[m][0]; s.offY = h->axOff[m][1]; s.offZ = h->axOff[m][2]; s.offT = h->axOff[m][3];
+            s.dimY = (unsigned)ax.dim[1]; s.dimZ = (unsigned)ax.dim[2]; s.dimT = (unsigned)ax.dim[3];
+            s.gBegin = (unsigned)(m ? h->cfg.velGridIndexOffset : h->cfg.posGridIndexOffset);
+        } else {
+            s.grid = m ? h->velGrid_d : h->posGrid_d;
+        }
+    }
+    const unsigned nBlk = (unsigned)std::max(sd[0].split, sd[1].split);
+    const dim3 grid(nBlk, (unsigned)nW, 2);
+    if (h->axes) hipLaunchKernelGGL(bcm_moments_kernel<true>, grid, dim3(256), 0, stream, sd[0], sd[1], keys, h->momPartial_d);
+    else hipLaunchKernelGGL(bcm_moments_kernel<false>, grid, dim3(256), 0, stream, sd[0], sd[1], keys, h->momPartial_d);
+    hipLaunchKernelGGL(bcm_moments_finish_kernel, dim3((unsigned)((2 * nW * kMomSlots + 255) / 256)), dim3(256), 0, stream, h->momPartial_d, (int)nBlk,
+                       sd[0].split, sd[1].split, keys, sd[0].rho, sd[1].rho, nW, h->momSums_d, h->momAbove_d, h->momMirror_hd);
+    DPE_CHECK_HIP(hipGetLastError());
+    h->momW = nW;
+    return 0;
+}
+
+int dpe_bcm_moments_from_sums(const double sums[2][15], const double centre[8], const double enu2ecef[9], double zValMom[8], double RValMom[64])
+{
+#pragma clang fp contract(off)   // (S2 - mu S1 must cancel to an exact 0 for a single point: no fused multiply-add)
+    DPE_REQUIRE(sums && centre && enu2ecef && zValMom && RValMom, "[BatchCorrManifold] moments_from_sums: null argument");
+    // order of a manifold's sums: 1 | x y z t | xx xy xz xt yy yz yt zz zt tt
+    static const int second[4][4] = {{5, 6, 7, 8}, {6, 9, 10, 11}, {7, 10, 12, 13}, {8, 11, 13, 14}};
+    const double *R = enu2ecef;
+    const double J[4][4] = {{R[0], R[1], R[2], 0}, {R[3], R[4], R[5], 0}, {R[6], R[7], R[8], 0}, {0, 0, 0, 1}};
+    for (int i = 0; i < 64; ++i) RValMom[i] = 0.0;
+    for (int m = 0; m < 2; ++m) {
+        const double *S = sums[m], S0 = S[0];
+        double mu[4], Cm[4][4], JC[4][4];
+        const bool empty = !(S0 != 0.0);   // (S0 == 0: no point above the threshold; a NaN sum goes the same way)
+        for (int a = 0; a < 4; ++a) mu[a] = empty ? (double)NAN : S[1 + a] / S0;
+        // C = S2 / S0 - mu mu^T as (S2 - mu S1^T) / S0: exactly 0 for a single point; one value per pair, both triangles
+        for (int a = 0; a < 4; ++a)
+            for (int b = a; b < 4; ++b) Cm[a][b] = Cm[b][a] = empty ? (double)NAN : (S[second[a][b]] - mu[a] * S[1 + b]) / S0;
+        for (int a = 0; a < 4; ++a) {
+            double z = centre[4 * m + a];
+            for (int b = 0; b < 4; ++b) z += J[a][b] * mu[b];   // (J is exact 0 / 1 outside the rotation: dt adds as it is)
+            zValMom[4 * m + a] = z;
+        }
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                double v = 0.0;
+                for (int c = 0; c < 4; ++c) v += J[a][c] * Cm[c][b];
+                JC[a][b] = v;
+            }
+        for (int a = 0; a < 4; ++a)
+            for (int b = a; b < 4; ++b) {
+                double v = 0.0;
+                for (int c = 0; c < 4; ++c) v += JC[a][c] * J[b][c];
+                if (empty) v = (double)NAN;
+                RValMom[(4 * m + a) * 8 + 4 * m + b] = RValMom[(4 * m + b) * 8 + 4 * m + a] = v;
+            }
+    }
+    return 0;
+}
+
+int dpe_bcm_moments_results(dpe_bcm *h, dpe_bcm_moments_result *out, dpe_stream_t stream)
+{
+    DPE_REQUIRE(h && out, "[BatchCorrManifold] moments_results: null argument");
+    DPE_REQUIRE(h->momW > 0 && h->momMirror_h, "[BatchCorrManifold] moments_results: no moments call yet");
+    DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    for (int w = 0; w < h->momW; ++w) {
+        dpe_bcm_moments_result &r = out[w];
+        for (int m = 0; m < 2; ++m) {
+            const dpe::MomMirror &mm = h->momMirror_h[2 * w + m];
+            for (int j = 0; j < dpe::kMomSums; ++j) r.sums[m][j] = mm.sums[j];
+            r.nAbove[m] = (int64_t)mm.nAbove;
+            r.threshold[m] = mm.tau;
+        }
+        // the window's frame: a device-parameter Update left it in the pinned frame of its key set (bcm_prep_kernel)
+        if (w >= h->lastW) {   // overridden rows beyond the last Update's windows: sums, but no frame to move them into
+            for (double &v : r.zValMom) v = (double)NAN;
+            for (double &v : r.RValMom) v = (double)NAN;
+            continue;
+        }
+        const bool devFrame = h->lastDev && w == 0;
+        const double *centre = devFrame ? h->devWin_h[h->cur].xCurrkk1 : h->win_h[w].xCurrkk1;
+        const double *R = devFrame ? h->devWin_h[h->cur].enu2ecef : h->win_h[w].enu2ecef;
+        if (dpe_bcm_moments_from_sums(r.sums, centre, R, r.zValMom, r.RValMom)) return -1;
+    }
+    return 0;
+}
+
+int dpe_bcm_moments_dev(dpe_bcm *h, const double **sums_dev, const int64_t **nAbove_dev)
+{
+    DPE_REQUIRE(h, "[BatchCorrManifold] moments_dev: null handle");
+    DPE_REQUIRE(h->momW > 0 && h->momSums_d, "[BatchCorrManifold] moments_dev: no moments call yet");
+    if (sums_dev) *sums_dev = h->momSums_d;
+    if (nAbove_dev) *nAbove_dev = reinterpret_cast<const int64_t *>(h->momAbove_d);
     return 0;
 }
 

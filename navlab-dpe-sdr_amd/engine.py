@@ -41,6 +41,7 @@ EXPORTS = [
     "dpe_bcm_create_epochs", "dpe_bcm_update_epochs", "dpe_bcm_results_epochs", "dpe_bcm_last_split",
     "dpe_bcm_create_subsets", "dpe_bcm_update_subsets", "dpe_bcm_results_subsets",
     "dpe_bcm_create_refine", "dpe_bcm_update_refine", "dpe_bcm_results_refine", "dpe_bcm_refine_scores", "dpe_bcm_refine_keys",
+    "dpe_bcm_moments", "dpe_bcm_moments_results", "dpe_bcm_moments_dev", "dpe_bcm_moments_from_sums",
     "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
     "dpe_vt_create", "dpe_vt_destroy", "dpe_vt_set_ephemerides", "dpe_vt_init", "dpe_vt_init_from_trk", "dpe_vt_track", "dpe_vt_read_log",
     "dpe_vt_read_corr", "dpe_vt_state", "dpe_vt_dev_status", "dpe_vt_filter_step_host",
@@ -135,6 +136,19 @@ class BcmRefineResult(C.Structure):  # dpe_bcm_refine_result
                 ("velIndex", C.c_int64 * REFINE_MAX_LEVELS), ("posScore", C.c_float * REFINE_MAX_LEVELS),
                 ("velScore", C.c_float * REFINE_MAX_LEVELS), ("posOutOfWindow", C.c_int64 * REFINE_MAX_LEVELS),
                 ("velOutOfWindow", C.c_int64 * REFINE_MAX_LEVELS)]
+
+
+class BcmMomentsConfig(C.Structure):  # dpe_bcm_moments_config
+    _fields_ = [("rho", C.c_double * 2), ("keys_dev", C.c_void_p), ("posScores_dev", C.c_void_p), ("velScores_dev", C.c_void_p),
+                ("posPitch", C.c_int64), ("velPitch", C.c_int64), ("nWindows", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BcmMomentsResult(C.Structure):  # dpe_bcm_moments_result
+    _fields_ = [("sums", (C.c_double * 15) * 2), ("nAbove", C.c_int64 * 2), ("threshold", C.c_float * 2),
+                ("zValMom", C.c_double * 8), ("RValMom", C.c_double * 64)]
+
+
+MOMENT_NAMES = ("1", "x", "y", "z", "t", "xx", "xy", "xz", "xt", "yy", "yz", "yt", "zz", "zt", "tt")   # the order of sums[m]
 
 
 CHAN_START_DTYPE = np.dtype([("codePhaseStart", "<f8"), ("carrierPhaseStart", "<f8"), ("codeFrequency", "<f8"),
@@ -474,6 +488,19 @@ def _win_chan(win, chan):
     return (win, chan) + chan.shape
 
 
+def moments_from_sums(sums, centre, enu2ecef):
+    """dpe_bcm_moments_from_sums (host only): sums [2, 15] -- one handle's, or the all-reduced sums of shards -- to
+    (zValMom [8], RValMom [8, 8]) about `centre` [8] in the frame of zVal (enu2ecef: the window's 3x3 matrix, row-major)."""
+    s = np.ascontiguousarray(sums, dtype=np.float64).reshape(2, 15)
+    c = np.ascontiguousarray(centre, dtype=np.float64).reshape(8)
+    R = np.ascontiguousarray(enu2ecef, dtype=np.float64).reshape(9)
+    z, Rv = np.zeros(8), np.zeros(64)
+    dp = C.POINTER(C.c_double)
+    _check(lib().dpe_bcm_moments_from_sums(s.ctypes.data_as(dp), c.ctypes.data_as(dp), R.ctypes.data_as(dp), z.ctypes.data_as(dp),
+                                           Rv.ctypes.data_as(dp)))
+    return z, Rv.reshape(8, 8)
+
+
 class BatchCorrManifold:
     """Module "BatchCorrManifold" (batchcorrmanifold.cu:2247-2303): params PosGrid/VelGrid (host
     [G,4] ENU offsets, i.e. the LoadPosGrid path :2422-2448 generalised to both manifolds), LPower."""
@@ -582,6 +609,41 @@ class BatchCorrManifold:
         split = (C.c_int32 * 2)()
         _check(lib().dpe_bcm_last_split(self._h, split))
         return (int(split[0]), int(split[1]))
+
+    def moments(self, rho, keys=None, pos_scores=None, vel_scores=None, n_windows=None, stream=None):
+        """Thresholded moments of the last Update's score rows (dpe_bcm_moments + dpe_bcm_moments_results): weights
+        max(score - rho * max, 0) per manifold, rho = (rho_pos, rho_vel) or one value for both.  keys: device uint64 [W, 2] to take
+        the rows' maxima from (default: the last Update's own, exchanged if exchange_keys ran); pos_scores / vel_scores: rows to
+        read instead of the handle's own -- a 2-D float32 device tensor (pitch = its row stride) or (device pointer, pitch).
+        Returns one dict per window: sums [2, 15] (order MOMENT_NAMES), nAbove [2], threshold [2], zValMom [8], RValMom [8, 8]."""
+        if not self.Started:
+            raise DpeError("[BatchCorrManifold] Error: moments() Failed due to module not initialized")
+        rp, rv = (rho, rho) if np.isscalar(rho) else rho
+
+        def rows(x):
+            if x is None:
+                return None, 0
+            if hasattr(x, "data_ptr"):
+                if x.dim() != 2 or x.stride(1) != 1 or x.element_size() != 4:
+                    raise DpeError("[BatchCorrManifold] moments: override rows must be a 2-D float32 tensor with contiguous rows")
+                return x.data_ptr(), x.stride(0)
+            return _ptr(x[0]).value, int(x[1])
+        (pp, ppitch), (vp, vpitch) = rows(pos_scores), rows(vel_scores)
+        cfg = BcmMomentsConfig((C.c_double * 2)(float(rp), float(rv)), None if keys is None else _ptr(keys).value, pp, vp, ppitch, vpitch,
+                               0 if n_windows is None else int(n_windows), 0)
+        _check(lib().dpe_bcm_moments(self._h, C.byref(cfg), _stream(stream)))
+        W = self._W if n_windows is None else int(n_windows)
+        res = (BcmMomentsResult * W)()
+        _check(lib().dpe_bcm_moments_results(self._h, res, _stream(stream)))
+        return [dict(sums=np.array([list(r.sums[0]), list(r.sums[1])]), nAbove=np.array(r.nAbove, dtype=np.int64),
+                     threshold=np.array(r.threshold, dtype=np.float32), zValMom=np.array(r.zValMom),
+                     RValMom=np.array(r.RValMom).reshape(8, 8)) for r in res]
+
+    def moments_dev(self):
+        """Device pointers of the last moments call's sums (double [max_windows, 2, 15]) and counts (int64 [max_windows, 2])."""
+        s, n = C.c_void_p(), C.c_void_p()
+        _check(lib().dpe_bcm_moments_dev(self._h, C.byref(s), C.byref(n)))
+        return s.value, n.value
 
     def read_scores(self, stream=None):
         Gp, Gv = self.pos_grid.shape[0], self.vel_grid.shape[0]

@@ -30,6 +30,30 @@ def bank_half_widths_refine(levels, fs, nfft):
     return L, B
 
 
+def quantisation_floor(grid):
+    """h^2 / 12 per grid axis [4], h = the smallest non-zero spacing of that axis's values: the variance of the grid's own
+    quantisation (a fix is a grid point).  An axis with a single value has no spacing and gets 0.  grid: a [G, 4] point list or
+    a GridAxes."""
+    cols = grid.axes if hasattr(grid, "axes") else [np.asarray(grid, dtype=np.float64)[:, c] for c in range(4)]
+    out = np.zeros(4)
+    for c, v in enumerate(cols):
+        d = np.diff(np.unique(v))      # (unique sorts; its differences are > 0)
+        out[c] = d.min() ** 2 / 12.0 if d.size else 0.0
+    return out
+
+
+def measurement_cov_floor(pos_floor, vel_floor, enu2ecef):
+    """The quantisation floors of both manifolds (quantisation_floor of each grid) as an 8x8 matrix in the frame of zVal:
+    blockdiag(J D_pos J^T, J D_vel J^T), D = diag(floor), J = blockdiag(enu2ecef, 1) -- diag(h^2 / 12) itself where the three
+    ENU spacings are equal."""
+    J = np.eye(4)
+    J[:3, :3] = np.asarray(enu2ecef, dtype=np.float64).reshape(3, 3)
+    F = np.zeros((8, 8))
+    F[:4, :4] = J @ np.diag(pos_floor) @ J.T
+    F[4:, 4:] = J @ np.diag(vel_floor) @ J.T
+    return 0.5 * (F + F.T)
+
+
 @contextlib.contextmanager
 def _single_rx_loop(iq_windows, ho, fs, K, init_delta, half_widths, make_bcm, make_cm=None, lag_half_width=None, bin_half_width=None,
                     max_windows=1):
@@ -68,13 +92,19 @@ def _single_rx_loop(iq_windows, ho, fs, K, init_delta, half_widths, make_bcm, ma
 
 
 def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), init_delta=(0, 0, 0, 0), K=None,
-                    lpower=1, enable_ekf=False, reference_pair=False, keep_scores=False, couple_velocity=True, doppler_sign=1):
+                    lpower=1, enable_ekf=False, reference_pair=False, keep_scores=False, couple_velocity=True, doppler_sign=1,
+                    measurement_cov=None):
     """iq_windows: int16 [W, 2S] (host).  Returns fixes [W, 8] (= xCurrk1k1 per window) and the raw
     per-window result dicts.  One window per Update, fix fed back to the channel manager.
     enable_ekf: route the fix through cuEKF's real filter (EnableEKF=true) instead of the shipped pass-through.
     reference_pair: dpe_bcm_config.referencePair; keep_scores: every result dict also carries the window's position and velocity scores;
     couple_velocity: the filter's F couples position and velocity over one window (cuekf.cu:111-143) or is the identity (ekf.py:47).
-    doppler_sign: the channel manager's DopplerSign (+1 / -1); the handoff's fi is the front end's own, the handoff names no sign."""
+    doppler_sign: the channel manager's DopplerSign (+1 / -1); the handoff's fi is the front end's own, the handoff names no sign.
+    measurement_cov: None (the reference's identity RVal), or (rho_pos, rho_vel): after each Update the thresholded moments of the
+    score rows are taken (BatchCorrManifold.moments) and the filter is fed R = RValMom + the grid's quantisation floor
+    (measurement_cov_floor; it keeps R positive definite when one point is above the threshold).  The measurement stays the
+    arg-max zVal.  The result dicts then carry `moments` and, as RVal, the R handed to the filter; a manifold with no point above
+    its threshold (every score 0) has no moments and keeps the identity block."""
     def make_bcm(S, nfft, L, B, K):
         return engine.BatchCorrManifold(fs, S, nfft, pos_grid, vel_grid, LPower=lpower, lag_half_width=L, bin_half_width=B,
                                         max_channels=K, reference_pair=reference_pair)
@@ -86,6 +116,7 @@ def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
         bcs, bcm, cm = lp.bcs, lp.bcm, lp.cm
         fixes, results = np.zeros((lp.W, 8)), []
         ekf = engine.cuEKF(lp.x, SampleLength=lp.S / fs, EnableEKF=enable_ekf, couple_velocity=couple_velocity)
+        floors = None if measurement_cov is None else (quantisation_floor(pos_grid), quantisation_floor(vel_grid))
         try:
             xk1k1, xkk1 = lp.x, lp.x
             for w in range(lp.W):
@@ -97,6 +128,13 @@ def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
                 if keep_scores:
                     ps, vs = bcm.read_scores()
                     r["posScores"], r["velScores"] = ps[0].copy(), vs[0].copy()
+                if measurement_cov is not None:
+                    mom = bcm.moments(measurement_cov)[0]
+                    R = mom["RValMom"] + measurement_cov_floor(floors[0], floors[1], bw["enu2ecef"][0])
+                    for m in (slice(0, 4), slice(4, 8)):
+                        if not np.isfinite(R[m, m]).all():
+                            R[m, m] = np.eye(4)
+                    r["moments"], r["RVal"] = mom, R
                 ekf.Update(r["zVal"], r["RVal"])    # EKF_PassMeas (the ML point is the new state) or the filter
                 xk1k1, xkk1 = ekf.xCurrk1k1.copy(), ekf.xCurrkk1.copy()
                 fixes[w] = xk1k1
