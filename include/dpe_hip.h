@@ -560,6 +560,13 @@ int dpe_bcm_moments_dev(dpe_bcm *h, const double **sums_dev, const int64_t **nAb
  * C is evaluated as (S2 - mu S1^T) / S0, which equals S2/S0 - mu mu^T and is exactly 0 for a single point. */
 int dpe_bcm_moments_from_sums(const double sums[2][15], const double centre[8], const double enu2ecef[9],
                               double zValMom[8], double RValMom[64]);
+/* Host only: the measurement covariance a filter takes from the sums.  Block m of R (row-major [64]) = M_m + F_m element by element,
+ * M_m = RValMom's block, F_m = J diag(floorVar[m]) J^T the grid's quantisation variance per (E, N, U, t) axis moved into the frame;
+ * the two off-diagonal blocks are 0.  A block with an entry that is not finite (S0 == 0) becomes the 4 x 4 identity and bit m of
+ * *fallback is set.  The device-resident loop forms its R with the same function (dpe_chm_dev_set_measurement_cov): same bits.
+ * Refused: a null argument, a floor that is negative or not finite. */
+int dpe_bcm_moments_rval(const double sums[2][15], const double enu2ecef[9], const double floorVar[2][4], double R[64],
+                         int32_t *fallback);
 
 /* ------------------------------------------------------------------ batches in flight ------ */
 /* Several batches of the path on the device at once -- what the reference gets from SampleBlock's 32-slot ring and reader thread
@@ -696,7 +703,8 @@ typedef struct dpe_fix_record {
     float posScore, velScore;
     int32_t status;             /* sticky bits: 1 Kepler iteration failed, 4 an arg-max key was 0 / outside the grid (state held for
                                  * that window), 8 / 16 the BatchCorrScores input flags of dpe_bcs_dev_status, 32 the filter's S was singular
-                                 * (dpe_chm_dev_set_ekf; state held), 64 a dpe_bcs_set_dev_hint promise did not hold */
+                                 * (dpe_chm_dev_set_ekf; state held), 64 a dpe_bcs_set_dev_hint promise did not hold, 128 a block of the
+                                 * filter's R fell back to the identity (dpe_chm_dev_set_measurement_cov: no point above the threshold) */
     int32_t reserved;
 } dpe_fix_record;
 int dpe_chm_dev_create(const dpe_chm_config *cfg, const dpe_chm_init_chan *chans, const double *timeGrid_host, int32_t dimT,
@@ -729,6 +737,33 @@ int dpe_chm_dev_ekf_state(dpe_chm_dev *h, double *xk1k1, double *xkk1, double *P
  * host form; the state ports stay.  Valid only between windows: once dpe_chm_dev_fix has returned the fix of the last
  * dpe_chm_dev_step.  Refused before dpe_chm_dev_set_ekf. */
 int dpe_chm_dev_ekf_load(dpe_chm_dev *h, const double *xkk1_host, const double *Pkk1_host, dpe_stream_t stream);
+/* The manifold moments' covariance as the device filter's R (csrc/dpe_bcm_moments_cov.h).  dpe_chm_dev_step then
+ * enqueues, behind the scan and in front of the measurement kernel, the moments kernel of dpe_bcm_moments on the scan's keys and score
+ * rows (thresholds rho[0] / rho[1] for the position / velocity manifold); the measurement kernel adds each row's block sums in the
+ * order dpe_bcm_moments does (the same sums, counts and thresholds, bit for bit), forms
+ *     R = blockdiag(M_pos + F_pos, M_vel + F_vel),   M = J C J^T as in RValMom,   F = J diag(floorVar) J^T,   J = blockdiag(enu2ecef, 1)
+ * with dpe_bcm_moments_rval's own function in the frame the window was scored in, and runs the filter with S = H P H^T + R: the states
+ * equal the host filter's (dpe_ekf_step_update) fed the same z and R.  posFloorVar / velFloorVar: the grids' quantisation variance per
+ * (E, N, U, t) axis, h^2 / 12 with h the axis' smallest non-zero spacing.  A block with an entry that is not finite (no point above the
+ * threshold) is the 4 x 4 identity for that window, and bit 128 of the fix record's status is set.  A window without a valid key holds
+ * the state as before and does not use its moments.
+ * After dpe_chm_dev_set_ekf, before Start; allocates the loop's moments buffers (the per-window path allocates nothing and never waits).
+ * Refused, each with a message: no BatchCorrManifold attached; no filter (the pass-through ignores R); after Start; a sharded loop
+ * (dpe_chm_dev_set_shard: the sums of shards would need an all-reduce); rho outside [0, 1) or not finite; a floor that is negative or not
+ * finite; an attached handle with writeScores = 0, or of a family dpe_bcm_moments refuses (joint, epochs, subsets, refine). */
+int dpe_chm_dev_set_measurement_cov(dpe_chm_dev *h, const double rho[2], const double posFloorVar[4], const double velFloorVar[4]);
+/* One window's R and what it was made from, as the measurement kernel left it in a ring in device memory of the fix ring's depth. */
+typedef struct dpe_rval_record {
+    uint64_t seq;               /* window index + 1 */
+    double R[64];               /* row-major, as the filter took it; all 0 for a window whose state was held (status bit 4) */
+    double sums[2][15];         /* dpe_bcm_moments_result.sums */
+    int64_t nAbove[2];
+    float threshold[2];
+    int32_t fallback;           /* bit m: block m is the identity */
+    int32_t reserved;
+} dpe_rval_record;
+/* Synchronises `stream` and copies window `window`'s record.  -1: no dpe_chm_dev_set_measurement_cov, never enqueued, or overwritten. */
+int dpe_chm_dev_rval(dpe_chm_dev *h, int64_t window, dpe_rval_record *out, dpe_stream_t stream);
 /* The device port arrays, in the structs dpe_bcs_update_dev / dpe_bcm_update_dev take, plus rxTime and the two state ports
  * (any pointer may be NULL): what dpeflow.cpp:169-191,212 connects. */
 int dpe_chm_dev_ports(dpe_chm_dev *h, dpe_bcs_ports_dev *bcs, dpe_bcm_ports_dev *bcm, const double **rxTime_dev,

@@ -2540,6 +2540,40 @@ static size_t moments_partial_len(int maxWindows)   // doubles: >= nWindows * 2 
     return 2 * rows * dpe::kMomSlots;
 }
 
+// The launch set-up dpe_bcm_moments and the device-resident loop (dpe_bcm_hook_moments_launch) share: the two manifolds' sides from
+// the handle's rows and grids (or cfg's overrides), and the launch over (blocks per row, nW, 2) into partial_d.  Returns gridDim.x.
+static unsigned moments_launch(dpe_bcm *h, const dpe_bcm_moments_config *cfg, int nW, const unsigned long long *keys, double *partial_d,
+                               dpe::MomSide (&sd)[2], hipStream_t stream)
+{
+    using namespace dpe;
+    const long long G[2] = {h->cfg.posGridSize, h->cfg.velGridSize};
+    sd[0] = MomSide{}; sd[1] = MomSide{};
+    for (int m = 0; m < 2; ++m) {
+        MomSide &s = sd[m];
+        const float *over = m ? cfg->velScores_dev : cfg->posScores_dev;
+        s.scores = over ? over : (m ? h->velScores_d : h->posScores_d);
+        s.pitch = over ? (long long)(m ? cfg->velPitch : cfg->posPitch) : (m ? h->velPitch : h->posPitch);
+        s.G = G[m];
+        s.vec = ((uintptr_t)s.scores % 16 == 0 && s.pitch % 4 == 0) ? 1 : 0;
+        s.rho = (float)cfg->rho[m];
+        s.split = (int)moments_split(G[m], nW);
+        if (h->axes) {
+            const dpe_bcm::Axes &ax = m ? h->velAx : h->posAx;
+            s.ax = h->axes_d;
+            s.offX = h->axOff[m][0]; s.offY = h->axOff[m][1]; s.offZ = h->axOff[m][2]; s.offT = h->axOff[m][3];
+            s.dimY = (unsigned)ax.dim[1]; s.dimZ = (unsigned)ax.dim[2]; s.dimT = (unsigned)ax.dim[3];
+            s.gBegin = (unsigned)(m ? h->cfg.velGridIndexOffset : h->cfg.posGridIndexOffset);
+        } else {
+            s.grid = m ? h->velGrid_d : h->posGrid_d;
+        }
+    }
+    const unsigned nBlk = (unsigned)std::max(sd[0].split, sd[1].split);
+    const dim3 grid(nBlk, (unsigned)nW, 2);
+    if (h->axes) hipLaunchKernelGGL(bcm_moments_kernel<true>, grid, dim3(256), 0, stream, sd[0], sd[1], keys, partial_d);
+    else hipLaunchKernelGGL(bcm_moments_kernel<false>, grid, dim3(256), 0, stream, sd[0], sd[1], keys, partial_d);
+    return nBlk;
+}
+
 int dpe_bcm_moments(dpe_bcm *h, const dpe_bcm_moments_config *cfg, dpe_stream_t stream_)
 {
     using namespace dpe;
@@ -2586,30 +2620,8 @@ int dpe_bcm_moments(dpe_bcm *h, const dpe_bcm_moments_config *cfg, dpe_stream_t 
     }
     const unsigned long long *keys = cfg->keys_dev ? reinterpret_cast<const unsigned long long *>(cfg->keys_dev)
                                                    : h->keys_d + (size_t)h->cur * 4 * maxW;
-    MomSide sd[2] = {};
-    for (int m = 0; m < 2; ++m) {
-        MomSide &s = sd[m];
-        const float *over = m ? cfg->velScores_dev : cfg->posScores_dev;
-        s.scores = over ? over : (m ? h->velScores_d : h->posScores_d);
-        s.pitch = over ? (long long)(m ? cfg->velPitch : cfg->posPitch) : (m ? h->velPitch : h->posPitch);
-        s.G = G[m];
-        s.vec = ((uintptr_t)s.scores % 16 == 0 && s.pitch % 4 == 0) ? 1 : 0;
-        s.rho = (float)cfg->rho[m];
-        s.split = (int)moments_split(G[m], nW);
-        if (h->axes) {
-            const dpe_bcm::Axes &ax = m ? h->velAx : h->posAx;
-            s.ax = h->axes_d;
-            s.offX = h->axOff[m][0]; s.offY = h->axOff[m][1]; s.offZ = h->axOff[m][2]; s.offT = h->axOff[m][3];
-            s.dimY = (unsigned)ax.dim[1]; s.dimZ = (unsigned)ax.dim[2]; s.dimT = (unsigned)ax.dim[3];
-            s.gBegin = (unsigned)(m ? h->cfg.velGridIndexOffset : h->cfg.posGridIndexOffset);
-        } else {
-            s.grid = m ? h->velGrid_d : h->posGrid_d;
-        }
-    }
-    const unsigned nBlk = (unsigned)std::max(sd[0].split, sd[1].split);
-    const dim3 grid(nBlk, (unsigned)nW, 2);
-    if (h->axes) hipLaunchKernelGGL(bcm_moments_kernel<true>, grid, dim3(256), 0, stream, sd[0], sd[1], keys, h->momPartial_d);
-    else hipLaunchKernelGGL(bcm_moments_kernel<false>, grid, dim3(256), 0, stream, sd[0], sd[1], keys, h->momPartial_d);
+    MomSide sd[2];
+    const unsigned nBlk = moments_launch(h, cfg, nW, keys, h->momPartial_d, sd, stream);
     hipLaunchKernelGGL(bcm_moments_finish_kernel, dim3((unsigned)((2 * nW * kMomSlots + 255) / 256)), dim3(256), 0, stream, h->momPartial_d, (int)nBlk,
                        sd[0].split, sd[1].split, keys, sd[0].rho, sd[1].rho, nW, h->momSums_d, h->momAbove_d, h->momMirror_hd);
     DPE_CHECK_HIP(hipGetLastError());
@@ -2621,38 +2633,31 @@ int dpe_bcm_moments_from_sums(const double sums[2][15], const double centre[8], 
 {
 #pragma clang fp contract(off)   // (S2 - mu S1 must cancel to an exact 0 for a single point: no fused multiply-add)
     DPE_REQUIRE(sums && centre && enu2ecef && zValMom && RValMom, "[BatchCorrManifold] moments_from_sums: null argument");
-    // order of a manifold's sums: 1 | x y z t | xx xy xz xt yy yz yt zz zt tt
-    static const int second[4][4] = {{5, 6, 7, 8}, {6, 9, 10, 11}, {7, 10, 12, 13}, {8, 11, 13, 14}};
-    const double *R = enu2ecef;
-    const double J[4][4] = {{R[0], R[1], R[2], 0}, {R[3], R[4], R[5], 0}, {R[6], R[7], R[8], 0}, {0, 0, 0, 1}};
+    double J[4][4];
+    dpe::mom_frame(enu2ecef, J);
     for (int i = 0; i < 64; ++i) RValMom[i] = 0.0;
     for (int m = 0; m < 2; ++m) {
-        const double *S = sums[m], S0 = S[0];
-        double mu[4], Cm[4][4], JC[4][4];
-        const bool empty = !(S0 != 0.0);   // (S0 == 0: no point above the threshold; a NaN sum goes the same way)
-        for (int a = 0; a < 4; ++a) mu[a] = empty ? (double)NAN : S[1 + a] / S0;
-        // C = S2 / S0 - mu mu^T as (S2 - mu S1^T) / S0: exactly 0 for a single point; one value per pair, both triangles
-        for (int a = 0; a < 4; ++a)
-            for (int b = a; b < 4; ++b) Cm[a][b] = Cm[b][a] = empty ? (double)NAN : (S[second[a][b]] - mu[a] * S[1 + b]) / S0;
+        double mu[4], M[4][4];
+        dpe::mom_cov_block(sums[m], J, mu, M);   // (shared with dpe_bcm_moments_rval and the device loop: dpe_bcm_moments_cov.h)
         for (int a = 0; a < 4; ++a) {
             double z = centre[4 * m + a];
             for (int b = 0; b < 4; ++b) z += J[a][b] * mu[b];   // (J is exact 0 / 1 outside the rotation: dt adds as it is)
             zValMom[4 * m + a] = z;
         }
         for (int a = 0; a < 4; ++a)
-            for (int b = 0; b < 4; ++b) {
-                double v = 0.0;
-                for (int c = 0; c < 4; ++c) v += J[a][c] * Cm[c][b];
-                JC[a][b] = v;
-            }
-        for (int a = 0; a < 4; ++a)
-            for (int b = a; b < 4; ++b) {
-                double v = 0.0;
-                for (int c = 0; c < 4; ++c) v += JC[a][c] * J[b][c];
-                if (empty) v = (double)NAN;
-                RValMom[(4 * m + a) * 8 + 4 * m + b] = RValMom[(4 * m + b) * 8 + 4 * m + a] = v;
-            }
+            for (int b = 0; b < 4; ++b) RValMom[(4 * m + a) * 8 + 4 * m + b] = M[a][b];
     }
+    return 0;
+}
+
+int dpe_bcm_moments_rval(const double sums[2][15], const double enu2ecef[9], const double floorVar[2][4], double R[64], int32_t *fallback)
+{
+    DPE_REQUIRE(sums && enu2ecef && floorVar && R && fallback, "[BatchCorrManifold] moments_rval: null argument");
+    for (int m = 0; m < 2; ++m)
+        for (int c = 0; c < 4; ++c)
+            DPE_REQUIRE(std::isfinite(floorVar[m][c]) && floorVar[m][c] >= 0.0, "[BatchCorrManifold] moments_rval: floorVar[%d][%d] = %g is negative or not finite",
+                        m, c, floorVar[m][c]);
+    *fallback = dpe::mom_rval(&sums[0][0], enu2ecef, &floorVar[0][0], R);
     return 0;
 }
 
@@ -2689,6 +2694,47 @@ int dpe_bcm_moments_dev(dpe_bcm *h, const double **sums_dev, const int64_t **nAb
     DPE_REQUIRE(h->momW > 0 && h->momSums_d, "[BatchCorrManifold] moments_dev: no moments call yet");
     if (sums_dev) *sums_dev = h->momSums_d;
     if (nAbove_dev) *nAbove_dev = reinterpret_cast<const int64_t *>(h->momAbove_d);
+    return 0;
+}
+
+// ---- the device-resident loop's share (dpe_chm_dev_set_measurement_cov, dpe_prep.h): what dpe_bcm_moments refuses of a handle is
+// refused when the loop is set up, and the per-window entry launches the moments kernel alone, into the caller's buffer
+int dpe_bcm_hook_moments_check(dpe_bcm *h, size_t *partialLen)
+{
+    DPE_REQUIRE(h, "[BatchCorrManifold] moments: null handle");
+    DPE_REQUIRE(!h->joint && !h->epochs && !h->subsets && !h->refine,
+                "[BatchCorrManifold] moments: a %s handle is not supported (dpe_bcm_moments refuses its family)",
+                h->joint ? "joint" : h->epochs ? "epochs" : h->subsets ? "subsets" : "refine");
+    DPE_REQUIRE(h->cfg.writeScores, "[BatchCorrManifold] moments: created with writeScores=0 (the handle has no score rows)");
+    if (partialLen) *partialLen = moments_partial_len(h->cfg.maxWindows);
+    return 0;
+}
+
+int dpe_bcm_hook_moments_launch(dpe_bcm *h, const double rho[2], double *partial_d, dpe_bcm_mom_geom *geom, void *stream)
+{
+    using namespace dpe;
+    DPE_REQUIRE(h && rho && partial_d && geom, "[BatchCorrManifold] moments: null argument");
+    DPE_REQUIRE(h->lastW == 1, "[BatchCorrManifold] moments: the device-resident loop scans one window per Update");
+    dpe_bcm_moments_config cfg{};
+    cfg.rho[0] = rho[0]; cfg.rho[1] = rho[1];
+    MomSide sd[2];
+    const unsigned long long *keys = h->keys_d + (size_t)h->cur * 4 * h->cfg.maxWindows;
+    geom->nBlk = (int)moments_launch(h, &cfg, 1, keys, partial_d, sd, (hipStream_t)stream);
+    geom->split[0] = sd[0].split; geom->split[1] = sd[1].split;
+    geom->rho[0] = sd[0].rho; geom->rho[1] = sd[1].rho;
+    return 0;
+}
+
+// bcm_moments_finish_kernel behind such a launch (the two-launch form of the loop): one window's sums, counts and thresholds into device
+// memory (mirror_d: MomMirror [2], any memory the device can write)
+int dpe_bcm_hook_moments_finish(dpe_bcm *h, const double *partial_d, const dpe_bcm_mom_geom *geom, double *sums_d, long long *nAbove_d,
+                                void *mirror_d, void *stream)
+{
+    using namespace dpe;
+    DPE_REQUIRE(h && partial_d && geom && sums_d && nAbove_d && mirror_d, "[BatchCorrManifold] moments: null argument");
+    const unsigned long long *keys = h->keys_d + (size_t)h->cur * 4 * h->cfg.maxWindows;
+    hipLaunchKernelGGL(bcm_moments_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial_d, geom->nBlk, geom->split[0], geom->split[1],
+                       keys, geom->rho[0], geom->rho[1], 1, sums_d, nAbove_d, static_cast<MomMirror *>(mirror_d));
     return 0;
 }
 

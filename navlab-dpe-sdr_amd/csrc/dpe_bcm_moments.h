@@ -16,11 +16,10 @@
 // Reduction: lanes by xor butterfly, the four waves in wave order through LDS, the blocks of a row in block order by
 // bcm_moments_finish_kernel behind the kernel boundary -- no atomics on doubles, the bits depend on inputs and geometry only.
 #pragma once
+#include "dpe_bcm_moments_cov.h"   // kMomSums, kMomSlots; what becomes of the sums (the filter's R)
 
 namespace dpe {
 
-constexpr int kMomSums = 15;
-constexpr int kMomSlots = 16;    // a block's partial: the 15 sums and, as an integer in the last slot, its count of points above tau
 constexpr int kMomUnit = 512;    // points per wave step
 
 // One manifold's share of the launch

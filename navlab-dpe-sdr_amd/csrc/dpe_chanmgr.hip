@@ -160,6 +160,14 @@ struct dpe_chm_dev {
     double *gPos_d = nullptr, *gVel_d = nullptr;
     long long gPosG = 0, gVelG = 0;
     dpe::EkfDev *ekf_d = nullptr;    // cuEKF's filter inside the measurement kernel (dpe_chm_dev_set_ekf); nullptr: pass-through
+    // the manifold moments' covariance as the filter's R (dpe_chm_dev_set_measurement_cov): everything allocated there
+    bool cov = false, covTwoLaunch = false;
+    double covRho[2] = {0, 0}, covFloor[2][4] = {};
+    double *covPartial_d = nullptr;      // the moments kernel's block partials of the window
+    double *covSums_d = nullptr;         // the two-launch form: bcm_moments_finish_kernel's outputs
+    long long *covAbove_d = nullptr;
+    char *covMirror_d = nullptr;
+    dpe_rval_record *covRing_d = nullptr;   // device memory, ringDepth records
 };
 
 static int chm_dev_args(dpe_chm_dev *h, int mode, int meas, const double *xk1k1, const double *xkk1, dpe::ChmKArgs &a)
@@ -210,7 +218,25 @@ static int chm_dev_launch(dpe_chm_dev *h, int mode, int meas, const double *xk1k
     using namespace dpe;
     ChmKArgs a;
     if (chm_dev_args(h, mode, meas, xk1k1, xkk1, a)) return -1;
-    hipLaunchKernelGGL(chm_k1_kernel, dim3(1), dim3(64), 0, stream, a);
+    if (meas && h->cov) {
+        // scan -> bcm_moments_kernel -> chm_k1_cov_kernel: the measurement kernel adds the rows' block partials itself (one launch
+        // less on the chain the next window's correlator waits for); the two-launch form puts bcm_moments_finish_kernel in between
+        ChmCovArgs cv{};
+        dpe_bcm_mom_geom g{};
+        if (dpe_bcm_hook_moments_launch(h->bcm, h->covRho, h->covPartial_d, &g, stream)) return -1;
+        if (h->covTwoLaunch) {
+            if (dpe_bcm_hook_moments_finish(h->bcm, h->covPartial_d, &g, h->covSums_d, h->covAbove_d, h->covMirror_d, stream)) return -1;
+            cv.sums = h->covSums_d; cv.nAbove = h->covAbove_d;
+        }
+        cv.partial = h->covPartial_d;
+        cv.nBlk = g.nBlk; cv.split[0] = g.split[0]; cv.split[1] = g.split[1];
+        cv.rho[0] = g.rho[0]; cv.rho[1] = g.rho[1];
+        memcpy(cv.floorVar, h->covFloor, sizeof(cv.floorVar));
+        cv.ring = h->covRing_d; cv.ringDepth = h->ringDepth;
+        hipLaunchKernelGGL(chm_k1_cov_kernel, dim3(1), dim3(64), 0, stream, a, cv);
+    } else {
+        hipLaunchKernelGGL(chm_k1_kernel, dim3(1), dim3(64), 0, stream, a);
+    }
     if (ride && h->bcs) {
         if (dpe_bcs_cotask_set(h->bcs, &a, sizeof(a))) return -1;
     } else {
@@ -317,6 +343,8 @@ int dpe_chm_dev_destroy(dpe_chm_dev *h)
     (void)hipFree(h->gPos_d);
     (void)hipFree(h->gVel_d);
     (void)hipFree(h->ekf_d);
+    (void)hipFree(h->covPartial_d); (void)hipFree(h->covSums_d); (void)hipFree(h->covAbove_d); (void)hipFree(h->covMirror_d);
+    (void)hipFree(h->covRing_d);
     if (h->ring_h) (void)hipHostFree(h->ring_h);
     (void)hipFree(h->stage_d);
     delete h;
@@ -362,6 +390,7 @@ int dpe_chm_dev_set_shard(dpe_chm_dev *h, dpe_comm *comm, const double *posGridG
 {
     DPE_REQUIRE(h && !h->started, "[cuChanMgr] set_shard: before Start");
     DPE_REQUIRE(h->bcm && h->ring_h, "[cuChanMgr] set_shard: attach a BatchCorrManifold first (dpe_chm_dev_attach)");
+    DPE_REQUIRE(!h->cov, "[cuChanMgr] set_shard: the loop takes its R from the manifold moments (dpe_chm_dev_set_measurement_cov), which a sharded loop cannot");
     DPE_REQUIRE(comm && (posGridGlobal != nullptr) == (velGridGlobal != nullptr), "[cuChanMgr] set_shard: bad arguments");
     if (!posGridGlobal) {   // a BatchCorrManifold with grid axes: the keys decode against its axes, which are the global ones
         DPE_REQUIRE(h->hm.posAx64_d, "[cuChanMgr] set_shard: NULL global grids need a BatchCorrManifold made with grid axes (dpe_bcm_create_axes)");
@@ -411,6 +440,60 @@ int dpe_chm_dev_set_ekf(dpe_chm_dev *h, const dpe_ekf_config *cfg)
     h->ekf_d = dev_alloc<EkfDev>(1);
     DPE_REQUIRE(h->ekf_d, "[cuChanMgr] set_ekf: device allocation failed");
     DPE_CHECK_HIP(hipMemcpy(h->ekf_d, &e[0], sizeof(EkfDev), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int dpe_chm_dev_set_measurement_cov(dpe_chm_dev *h, const double rho[2], const double posFloorVar[4], const double velFloorVar[4])
+{
+    using namespace dpe;
+    DPE_REQUIRE(h, "[cuChanMgr] set_measurement_cov: null handle");
+    DPE_REQUIRE(rho && posFloorVar && velFloorVar, "[cuChanMgr] set_measurement_cov: null argument");
+    for (int m = 0; m < 2; ++m)
+        DPE_REQUIRE(std::isfinite(rho[m]) && rho[m] >= 0.0 && rho[m] < 1.0, "[cuChanMgr] set_measurement_cov: rho[%d] = %g outside [0, 1) (%s manifold)",
+                    m, rho[m], m ? "velocity" : "position");
+    for (int c = 0; c < 4; ++c) {
+        DPE_REQUIRE(std::isfinite(posFloorVar[c]) && posFloorVar[c] >= 0.0, "[cuChanMgr] set_measurement_cov: posFloorVar[%d] = %g is negative or not finite",
+                    c, posFloorVar[c]);
+        DPE_REQUIRE(std::isfinite(velFloorVar[c]) && velFloorVar[c] >= 0.0, "[cuChanMgr] set_measurement_cov: velFloorVar[%d] = %g is negative or not finite",
+                    c, velFloorVar[c]);
+    }
+    DPE_REQUIRE(!h->started, "[cuChanMgr] set_measurement_cov: before Start");
+    DPE_REQUIRE(h->bcm && h->ring_h, "[cuChanMgr] set_measurement_cov: attach a BatchCorrManifold first (dpe_chm_dev_attach)");
+    DPE_REQUIRE(h->ekf_d, "[cuChanMgr] set_measurement_cov: no filter (dpe_chm_dev_set_ekf first: the pass-through ignores R)");
+    DPE_REQUIRE(!h->comm, "[cuChanMgr] set_measurement_cov: a sharded loop (dpe_chm_dev_set_shard) is not supported (the sums of shards need an all-reduce)");
+    size_t partialLen = 0;
+    if (dpe_bcm_hook_moments_check(h->bcm, &partialLen)) return -1;   // (writeScores = 0, the families dpe_bcm_moments refuses)
+    if (!h->covPartial_d) {
+        h->covPartial_d = dev_alloc<double>(partialLen);
+        h->covSums_d = dev_alloc<double>(2 * kMomSums);
+        h->covAbove_d = dev_alloc<long long>(2);
+        h->covMirror_d = dev_alloc<char>(512);   // (bcm_moments_finish_kernel's mirror of two manifolds; nobody reads it here)
+        h->covRing_d = dev_alloc<dpe_rval_record>((size_t)h->ringDepth);
+        DPE_REQUIRE(h->covPartial_d && h->covSums_d && h->covAbove_d && h->covMirror_d && h->covRing_d,
+                    "[cuChanMgr] set_measurement_cov: device allocation failed");
+        DPE_CHECK_HIP(hipMemset(h->covRing_d, 0, sizeof(dpe_rval_record) * (size_t)h->ringDepth));
+    }
+    for (int c = 0; c < 4; ++c) { h->covFloor[0][c] = posFloorVar[c]; h->covFloor[1][c] = velFloorVar[c]; }
+    h->covRho[0] = rho[0]; h->covRho[1] = rho[1];
+    // the two-launch form (bcm_moments_finish_kernel in front of the measurement kernel) gives the same bits and measured slower
+    // (profiles/device_loop_cov.txt); it stays selectable for that comparison
+    const char *two = getenv("DPE_CHM_COV_TWO_LAUNCH");
+    h->covTwoLaunch = two && two[0] == '1';
+    h->cov = true;
+    return 0;
+}
+
+int dpe_chm_dev_rval(dpe_chm_dev *h, int64_t window, dpe_rval_record *out, dpe_stream_t stream)
+{
+    DPE_REQUIRE(h && out, "[cuChanMgr] rval: null argument");
+    DPE_REQUIRE(h->cov && h->covRing_d, "[cuChanMgr] rval: no measurement covariance (dpe_chm_dev_set_measurement_cov)");
+    DPE_REQUIRE(window >= 0 && window < h->enqueued, "[cuChanMgr] rval: window %lld not enqueued yet", (long long)window);
+    DPE_REQUIRE(window + h->ringDepth >= h->enqueued, "[cuChanMgr] rval: window %lld was overwritten (the ring holds %d records)", (long long)window,
+                h->ringDepth);
+    DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    DPE_CHECK_HIP(hipMemcpy(out, h->covRing_d + (window % h->ringDepth), sizeof(dpe_rval_record), hipMemcpyDeviceToHost));
+    DPE_REQUIRE(out->seq == (uint64_t)window + 1u, "[cuChanMgr] rval: window %lld's record is not in the ring (found sequence %llu)", (long long)window,
+                (unsigned long long)out->seq);
     return 0;
 }
 

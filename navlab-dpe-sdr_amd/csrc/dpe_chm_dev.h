@@ -4,6 +4,7 @@
 #pragma once
 #include "dpe_common.h"
 #include "dpe_prep.h"
+#include "dpe_bcm_moments_cov.h"
 
 #ifdef __HIPCC__
 #define DPE_HD __host__ __device__
@@ -300,6 +301,21 @@ __device__ inline const double *axes_point(const double *ax, const int dim[4], l
     return out;
 }
 
+// The same point into `out` whichever form the grid has: axes (ax set; index local + off) or a point list (row `local` of grid)
+__device__ __forceinline__ void chm_point(const double *ax, const int (&dim)[4], const double *grid, long long local, long long off, double (&out)[4])
+{
+    if (ax) {
+        long long index = local + off;
+        const double *a3 = ax + dim[0] + dim[1] + dim[2], *a2 = ax + dim[0] + dim[1], *a1 = ax + dim[0];
+        out[3] = a3[index % dim[3]]; index /= dim[3];
+        out[2] = a2[index % dim[2]]; index /= dim[2];
+        out[1] = a1[index % dim[1]]; index /= dim[1];
+        out[0] = ax[index % dim[0]];
+    } else {
+        out[0] = grid[4 * local]; out[1] = grid[4 * local + 1]; out[2] = grid[4 * local + 2]; out[3] = grid[4 * local + 3];
+    }
+}
+
 struct ChmKArgs {
     ChmDevState *st;
     ChmPorts p;
@@ -428,6 +444,10 @@ __shared__ unsigned long long dpe_ekf_stamps[10];
 #else
 #define DPE_EKF_STAMP(i) do { } while (0)
 #endif
+// (The filter's pieces are templates on the kernel form for one reason: each measurement kernel then has copies of its own, with the
+// callers the single kernel had, and the inliner treats them as it did.  As functions shared by two kernels ekf_dev_invert became a
+// call with a stack frame and ekf_dev_mul lost its 16-byte LDS reads -- in BOTH kernels.)
+template <bool COV>
 __device__ static inline double ekf_dev_mul(const double *a, const double *b, bool bT, double *c)
 {
 #pragma clang fp contract(off)
@@ -519,6 +539,7 @@ __device__ __forceinline__ bool ekf_lu_column(double &x, int &pv, int l, int r, 
     }
     return true;
 }
+template <bool COV>
 __device__ static inline bool ekf_dev_invert(const double *a, double *lu, double *inv, int *piv)
 {
 #pragma clang fp contract(off)
@@ -589,7 +610,10 @@ __device__ static inline EkfPre ekf_dev_prefetch(const EkfDev *e)
     r.coupled = e->coupled;
     return r;
 }
-__device__ static inline bool ekf_dev_step(EkfDev *e, const EkfPre &pre, const double *z, double *sm, int *piv)
+// COV: the measurement covariance is Rm (64 doubles of LDS, row-major) instead of the identity: S = (H P) H^T + Rm, the host form's
+// S[i] += R[i] (dpe_ekf_step_update), so the states stay the host filter's fed the same R.  (dpe_chm_dev_set_measurement_cov)
+template <bool COV>
+__device__ static inline bool ekf_dev_step(EkfDev *e, const EkfPre &pre, const double *z, double *sm, int *piv, const double *Rm)
 {
 #pragma clang fp contract(off)
     const int l = threadIdx.x, i = l >> 3, j = l & 7;
@@ -602,7 +626,8 @@ __device__ static inline bool ekf_dev_step(EkfDev *e, const EkfPre &pre, const d
     const int lpfIdx = __builtin_amdgcn_readfirstlane(pre.lpfIdx);
     const double lpfAvg0 = pre.lpfAvg;
     const double pz = 0.0 + p;                                     // H P = P H^T = 0.0 + P
-    S[l] = (0.0 + pz) + ((l % 9 == 0) ? 1.0 : 0.0);                // S = (H P) H^T + R
+    if constexpr (COV) S[l] = (0.0 + pz) + Rm[l];
+    else S[l] = (0.0 + pz) + ((l % 9 == 0) ? 1.0 : 0.0);           // S = (H P) H^T + R
     T[l] = pz;                                                     // P H^T, the first factor of K
     if (l < 8) y[l] = z[l] - pre.xk;                               // y = z - H x_k|k-1
     __syncthreads();
@@ -611,10 +636,10 @@ __device__ static inline bool ekf_dev_step(EkfDev *e, const EkfPre &pre, const d
     Sinv[l] = S[l];
     __syncthreads();
 #else
-    if (!ekf_dev_invert(S, lu, Sinv, piv)) return false;
+    if (!ekf_dev_invert<COV>(S, lu, Sinv, piv)) return false;
 #endif
     DPE_EKF_STAMP(4);
-    const double kv = ekf_dev_mul(T, Sinv, false, tmp);            // K = (P H^T) S^-1
+    const double kv = ekf_dev_mul<COV>(T, Sinv, false, tmp);            // K = (P H^T) S^-1
     e->K[l] = kv;
     double xs1 = 0.0;                                              // lanes 0 .. 7: x_k|k
     if (l < 8) {                                                   // x_k|k = x_k|k-1 + K y
@@ -632,7 +657,7 @@ __device__ static inline bool ekf_dev_step(EkfDev *e, const EkfPre &pre, const d
     }
     __syncthreads();
     DPE_EKF_STAMP(5);
-    const double p1 = ekf_dev_mul(T, P, false, P1);
+    const double p1 = ekf_dev_mul<COV>(T, P, false, P1);
     DPE_EKF_STAMP(6);
     e->Pk1k1[l] = p1;
     // ---- StepPredict with GetQVal (:733-742) and EKF_Update_Q (:42-78).  The block is one wave: the low-pass state is wave-uniform
@@ -682,7 +707,28 @@ __device__ static inline bool ekf_dev_step(EkfDev *e, const EkfPre &pre, const d
     return true;
 }
 
-__device__ static inline void chm_k1(const ChmKArgs &a)
+// The manifold moments' share of the measurement kernel (dpe_chm_dev_set_measurement_cov): where the partial sums of
+// the moments launch behind the scan lie, the grid's quantisation floor, and the ring of R records (device memory)
+struct ChmCovArgs {
+    const double *partial;          // [2][nBlk][kMomSlots]: the blocks of a row are added here, in block order (bcm_moments_finish_kernel's)
+    int nBlk, split[2];
+    float rho[2];
+    const double *sums;             // the two-launch form: bcm_moments_finish_kernel ran in front and left the sums [2][15] and the
+    const long long *nAbove;        //   counts [2] here; nullptr: this kernel adds the partials itself (the fold, the form in use)
+    double floorVar[2][4];          // (E, N, U, t) quantisation variance of the position and the velocity grid
+    dpe_rval_record *ring;          // device memory, ringDepth records (the fix ring's depth)
+    int ringDepth;
+};
+constexpr int kMomFold = 32;     // block partials a lane of chm_k1_cov_kernel has in flight while it adds a row's blocks in order
+struct ChmCovLds {
+    double mom[32];                 // the 2 x 15 sums, then the two counts as integers
+    double R[64];
+    int fall;                       // bit m: block m of R fell back to the identity
+};
+
+// COV (chm_k1_cov_kernel): the filter runs on the R of the window's manifold moments; cv and lds are read in that form only
+template <bool COV>
+__device__ static inline void chm_k1(const ChmKArgs &a, const ChmCovArgs &cv, ChmCovLds *lds)
 {
     __shared__ double sX1[8], sXk[8], sZ[8];   // x_k|k, x_k+1|k, the measurement
     __shared__ double sEkf[kEkfDevScratch];
@@ -696,6 +742,40 @@ __device__ static inline void chm_k1(const ChmKArgs &a)
     DPE_EKF_STAMP(0);
     EkfPre ekfPre{};
     if (a.meas && a.ekf) ekfPre = ekf_dev_prefetch(a.ekf);
+    double momV = 0.0;   // COV, lanes 0 .. 29: sum (manifold k / 15, slot k % 15); lanes 30 / 31: the count of manifold 0 / 1, as an integer
+    if constexpr (COV) {
+        // requested here, beside the keys and the filter's operands: the row's block partials in block order -- the order and the
+        // operations of bcm_moments_finish_kernel, so sums and counts carry the bits dpe_bcm_moments gives
+        if (k < 32) {
+            const int m = k < 30 ? k / kMomSums : k - 30, j = k < 30 ? k - m * kMomSums : kMomSums;
+            if (cv.sums) {
+                momV = k < 30 ? cv.sums[k] : __longlong_as_double(cv.nAbove[m]);
+            } else {
+                // (bcm_moments_finish_kernel's a = p[0]; a += p[b] and n += count[b], with the loads of kMomFold blocks in flight at a time:
+                //  one block per round trip to device memory made this loop the kernel -- 128 blocks per row at 25^4)
+                const double *p = cv.partial + (size_t)m * cv.nBlk * kMomSlots + j;
+                const int split = m ? cv.split[1] : cv.split[0];   // (selects: no indexed kernel argument)
+                double v = 0.0;
+                long long n = 0;
+                for (int b0 = 0; b0 < split; b0 += kMomFold) {
+                    double t[kMomFold];
+#pragma unroll
+                    for (int i = 0; i < kMomFold; ++i) t[i] = b0 + i < split ? p[(size_t)(b0 + i) * kMomSlots] : 0.0;
+#pragma unroll
+                    for (int i = 0; i < kMomFold; ++i) {
+                        if (b0 + i < split) {
+                            v = b0 + i == 0 ? t[i] : v + t[i];
+                            n += __double_as_longlong(t[i]);
+                        }
+                    }
+                }
+                momV = k < 30 ? v : __longlong_as_double(n);
+            }
+            lds->mom[k] = momV;
+        }
+        lds->R[k] = 0.0;
+        if (k == 0) lds->fall = 0;
+    }
     Chan c;
     if (k < K) c = st->ch[k];
     double z[8];
@@ -712,8 +792,15 @@ __device__ static inline void chm_k1(const ChmKArgs &a)
             if (kp == 0ull || ip < 0 || ip >= a.posG) { measBad = 4; ip = 0; }
             if (kv == 0ull || iv < 0 || iv >= a.velG) { measBad = 4; iv = 0; }
             double gAx[4], vAx[4];   // (grid axes: the point decoded from its global index)
-            const double *g = a.posAx ? axes_point(a.posAx, a.posDim, ip + a.posOff, gAx) : a.posGrid + 4 * ip;
-            const double *v = a.velAx ? axes_point(a.velAx, a.velDim, iv + a.velOff, vAx) : a.velGrid + 4 * iv;
+            const double *g, *v;
+            if constexpr (COV) {   // (the same doubles, by value: a pointer that is either the list's row or a local array keeps the array in scratch)
+                chm_point(a.posAx, a.posDim, a.posGrid, ip, a.posOff, gAx);
+                chm_point(a.velAx, a.velDim, a.velGrid, iv, a.velOff, vAx);
+                g = gAx; v = vAx;
+            } else {
+                g = a.posAx ? axes_point(a.posAx, a.posDim, ip + a.posOff, gAx) : a.posGrid + 4 * ip;
+                v = a.velAx ? axes_point(a.velAx, a.velDim, iv + a.velOff, vAx) : a.velGrid + 4 * iv;
+            }
             const double *R = a.p.enu2ecef, *cc = a.p.xkk1;
             {
 #pragma clang fp contract(off)   // (the host form's BCM_MakePosMeas / MakeVelMeas run without fused multiply-adds: the same doubles here)
@@ -736,13 +823,50 @@ __device__ static inline void chm_k1(const ChmKArgs &a)
     if (a.meas && a.ekf) {   // EnableEKF = true: StepUpdate + StepPredict on the measurement (block-uniform branch; all 64 lanes work)
         __syncthreads();
         DPE_EKF_STAMP(1);
-        const bool ok = sFlags == 0 && ekf_dev_step(a.ekf, ekfPre, sZ, sEkf, sPiv);
+        bool ok;
+        if constexpr (COV) {
+            // R from the sums, in the frame the measurement was formed in (the ports as the previous window's chm_k2 left them): one
+            // lane per manifold, dpe_bcm_moments_rval's own function.  No measurement: the state is held and the moments are not used
+            // (the record then carries the sums and an R of zeros).
+            if (sFlags == 0 && k < 2) {
+                double blk[16], fv[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) fv[i] = k ? cv.floorVar[1][i] : cv.floorVar[0][i];
+                if (mom_rval_block(lds->mom + kMomSums * k, a.p.enu2ecef, fv, blk)) atomicOr(&lds->fall, 1 << k);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) lds->R[(4 * k + (i >> 2)) * 8 + 4 * k + (i & 3)] = blk[i];
+            }
+            __syncthreads();
+            ok = sFlags == 0 && ekf_dev_step<true>(a.ekf, ekfPre, sZ, sEkf, sPiv, lds->R);
+        } else {
+            ok = sFlags == 0 && ekf_dev_step<false>(a.ekf, ekfPre, sZ, sEkf, sPiv, nullptr);
+        }
         __syncthreads();
+        if constexpr (COV) {
+            // the window's record: plain stores to device memory (dpe_chm_dev_rval copies it out behind the stream)
+            const unsigned long long seq = (unsigned long long)(st->window + 1);
+            dpe_rval_record *rr = cv.ring + (long long)(seq - 1ull) % cv.ringDepth;
+            rr->R[k] = lds->R[k];
+            if (k < 30) {
+                rr->sums[k / kMomSums][k % kMomSums] = momV;
+            } else if (k < 32) {
+                const int m = k - 30;
+                rr->nAbove[m] = __double_as_longlong(momV);
+                rr->threshold[m] = __fmul_rn(m ? cv.rho[1] : cv.rho[0], __uint_as_float((unsigned int)(a.keys[m] >> 32)));   // (mom_tau's multiply)
+            } else if (k == 32) {
+                rr->fallback = lds->fall;
+                rr->reserved = 0;
+                rr->seq = seq;
+            }
+        }
         if (k < 8) {
             if (ok) { sX1[k] = sEkf[kEkfDevX1 + k]; sXk[k] = sEkf[kEkfDevXk + k]; }
             else { sX1[k] = a.p.xkk1[k]; sXk[k] = a.p.xkk1[k]; }   // (no measurement, or S singular: hold the predicted state)
         }
         if (!ok && k == 0 && sFlags == 0) { atomicOr(&sFlags, 32); a.ekf->failed = 1; }
+        if constexpr (COV) {
+            if (k == 0 && lds->fall) atomicOr(&sFlags, 128);       // (behind the test above: bit 128 does not hold the state)
+        }
         DPE_EKF_STAMP(8);
         __syncthreads();
     }
@@ -770,7 +894,7 @@ __device__ static inline void chm_k1(const ChmKArgs &a)
 #endif
             r->posScore = __uint_as_float((unsigned)(kp >> 32));
             r->velScore = __uint_as_float((unsigned)(kv >> 32));
-            r->status = st->status | measBad | (sFlags & 32);
+            r->status = st->status | measBad | (sFlags & (COV ? 32 | 128 : 32));
             r->seq = (unsigned long long)(st->window + 1);
         } else {
             for (int i = 0; i < 8; ++i) {
@@ -1004,7 +1128,14 @@ __device__ __forceinline__ static void chm_k3(const ChmKArgs &a)
     if (active && wave == 1 && bad) st->specOk[wb][k] = 0;   // (behind wave 0's store: both waves of a channel run in this block)
 }
 
-__global__ __launch_bounds__(64) static void chm_k1_kernel(ChmKArgs a) { chm_k1(a); }
+__global__ __launch_bounds__(64) static void chm_k1_kernel(ChmKArgs a) { chm_k1<false>(a, ChmCovArgs{}, nullptr); }
+// the measurement kernel of a loop with dpe_chm_dev_set_measurement_cov: behind bcm_moments_kernel (the fold), or behind that and
+// bcm_moments_finish_kernel (cv.sums set)
+__global__ __launch_bounds__(64) static void chm_k1_cov_kernel(ChmKArgs a, ChmCovArgs cv)
+{
+    __shared__ ChmCovLds lds;
+    chm_k1<true>(a, cv, &lds);
+}
 __global__ __launch_bounds__(256) static void chm_k2_kernel(ChmKArgs a) { chm_k2(a); }
 
 }  // namespace dpe

@@ -182,4 +182,16 @@ int dpe_bcm_hook_set_publish(dpe_bcm *h, int enable);
 // referencePair with dpe_bcm_update_prepared: the attached channel manager's port arrays and its rxTime port, for the fp64 re-evaluation
 // of the affected grid points (ports = nullptr: detached)
 int dpe_bcm_hook_set_ref_ports(dpe_bcm *h, const dpe_bcm_ports_dev *ports, const double *rxTime_dev);
+// The manifold moments inside the device-resident loop (dpe_chm_dev_set_measurement_cov): _check refuses what dpe_bcm_moments refuses
+// of a handle and gives the length in doubles of a partial-sum buffer; _launch enqueues bcm_moments_kernel alone, on the keys and rows
+// of the LAST Update, into partial_d ([2][nBlk][16]; the blocks of a row are summed in block order by whoever reads them); _finish is
+// bcm_moments_finish_kernel behind it (mirror_d: room for two MomMirror, dpe_bcm_moments.h).  Nothing here allocates or waits.
+struct dpe_bcm_mom_geom {
+    int nBlk, split[2];
+    float rho[2];
+};
+int dpe_bcm_hook_moments_check(dpe_bcm *h, size_t *partialLen);
+int dpe_bcm_hook_moments_launch(dpe_bcm *h, const double rho[2], double *partial_d, dpe_bcm_mom_geom *geom, void *stream);
+int dpe_bcm_hook_moments_finish(dpe_bcm *h, const double *partial_d, const dpe_bcm_mom_geom *geom, double *sums_d, long long *nAbove_d,
+                                void *mirror_d, void *stream);
 }

@@ -42,6 +42,7 @@ EXPORTS = [
     "dpe_bcm_create_subsets", "dpe_bcm_update_subsets", "dpe_bcm_results_subsets",
     "dpe_bcm_create_refine", "dpe_bcm_update_refine", "dpe_bcm_results_refine", "dpe_bcm_refine_scores", "dpe_bcm_refine_keys",
     "dpe_bcm_moments", "dpe_bcm_moments_results", "dpe_bcm_moments_dev", "dpe_bcm_moments_from_sums",
+    "dpe_bcm_moments_rval", "dpe_chm_dev_set_measurement_cov", "dpe_chm_dev_rval",
     "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
     "dpe_vt_create", "dpe_vt_destroy", "dpe_vt_set_ephemerides", "dpe_vt_init", "dpe_vt_init_from_trk", "dpe_vt_track", "dpe_vt_read_log",
     "dpe_vt_read_corr", "dpe_vt_state", "dpe_vt_dev_status", "dpe_vt_filter_step_host",
@@ -499,6 +500,21 @@ def moments_from_sums(sums, centre, enu2ecef):
     _check(lib().dpe_bcm_moments_from_sums(s.ctypes.data_as(dp), c.ctypes.data_as(dp), R.ctypes.data_as(dp), z.ctypes.data_as(dp),
                                            Rv.ctypes.data_as(dp)))
     return z, Rv.reshape(8, 8)
+
+
+def moments_rval(sums, enu2ecef, floor_var):
+    """dpe_bcm_moments_rval (host only): the measurement covariance a filter takes from a window's sums [2, 15] in the frame given
+    by enu2ecef: per manifold RValMom's block plus the grid's quantisation floor J diag(floor_var[m]) J^T (floor_var [2, 4]:
+    pipeline.quantisation_floor of the position and the velocity grid).  A block that is not finite (no point above the threshold)
+    becomes the identity.  Returns (R [8, 8], fallback: bit m set where block m is the identity).  The device-resident loop forms
+    its R with the same function (ChanMgrDev.set_measurement_cov)."""
+    s = np.ascontiguousarray(sums, dtype=np.float64).reshape(2, 15)
+    R = np.ascontiguousarray(enu2ecef, dtype=np.float64).reshape(9)
+    f = np.ascontiguousarray(floor_var, dtype=np.float64).reshape(2, 4)
+    out, fb = np.zeros(64), C.c_int32(0)
+    dp = C.POINTER(C.c_double)
+    _check(lib().dpe_bcm_moments_rval(s.ctypes.data_as(dp), R.ctypes.data_as(dp), f.ctypes.data_as(dp), out.ctypes.data_as(dp), C.byref(fb)))
+    return out.reshape(8, 8), int(fb.value)
 
 
 class BatchCorrManifold:
@@ -1254,6 +1270,11 @@ class FixRecord(C.Structure):     # dpe_fix_record
                 ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RvalRecord(C.Structure):    # dpe_rval_record
+    _fields_ = [("seq", C.c_uint64), ("R", C.c_double * 64), ("sums", (C.c_double * 15) * 2), ("nAbove", C.c_int64 * 2),
+                ("threshold", C.c_float * 2), ("fallback", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ChanMgrDev:
     """Module "cuChanMgr" as the reference has it: state and port arrays in DEVICE memory, one small kernel per window
     (dpe_chm_dev_*; cuchanmgr.cu:1100-1132,1237-1264).  attach(bcs, bcm) makes it write their parameter blocks and form the
@@ -1304,6 +1325,25 @@ class ChanMgrDev:
         cfg.x0[:] = [float(v) for v in np.asarray(x0, dtype=np.float64)]
         cfg.P0[:] = [float(v) for v in (np.eye(8) if P0 is None else np.asarray(P0, dtype=np.float64)).reshape(64)]
         _check(lib().dpe_chm_dev_set_ekf(self._h, C.byref(cfg)))
+
+    def set_measurement_cov(self, rho, pos_floor, vel_floor):
+        """dpe_chm_dev_set_measurement_cov: the device filter takes R from the window's manifold moments (thresholds rho =
+        (rho_pos, rho_vel) or one value for both) plus the grids' quantisation floors (pipeline.quantisation_floor of each grid)
+        instead of the identity.  After set_ekf, before Start."""
+        rp, rv = (rho, rho) if np.isscalar(rho) else rho
+        pf = np.ascontiguousarray(pos_floor, dtype=np.float64).reshape(4)
+        vf = np.ascontiguousarray(vel_floor, dtype=np.float64).reshape(4)
+        dp = C.POINTER(C.c_double)
+        _check(lib().dpe_chm_dev_set_measurement_cov(self._h, (C.c_double * 2)(float(rp), float(rv)), pf.ctypes.data_as(dp),
+                                                     vf.ctypes.data_as(dp)))
+
+    def rval(self, window, stream=None):
+        """dpe_chm_dev_rval: window's R [8, 8] as the device filter took it, with the sums [2, 15], nAbove [2] and threshold [2] it
+        was made from and `fallback` (bit m: block m is the identity).  Synchronises `stream`."""
+        r = RvalRecord()
+        _check(lib().dpe_chm_dev_rval(self._h, C.c_int64(window), C.byref(r), _stream(stream)))
+        return dict(R=np.array(r.R[:]).reshape(8, 8), sums=np.array([list(r.sums[0]), list(r.sums[1])]),
+                    nAbove=np.array(r.nAbove, dtype=np.int64), threshold=np.array(r.threshold, dtype=np.float32), fallback=int(r.fallback))
 
     def ekf_state(self, stream=None):
         """dpe_chm_dev_ekf_state: the device filter's members in the form of cuEKF.state()."""

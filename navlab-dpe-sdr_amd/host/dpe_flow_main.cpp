@@ -17,6 +17,11 @@
 //                                                flow correlates K / N of the channels, dpe_bcs_allgather_banks completes the banks.
 //                                                With --device-loop the exchange is enqueued between the scan and the channel
 //                                                manager's measurement kernel (dpe_chm_dev_set_shard): still nothing read back
+//            [--ekf [--measurement-cov rp,rv]]   cuEKF's filter instead of the pass-through; --measurement-cov: its R from the
+//                                                manifold moments of each window (thresholds rp / rv of the position / velocity
+//                                                row's maximum) plus the grids' quantisation floor, instead of the identity --
+//                                                host-driven: dpe_bcm_moments -> dpe_bcm_moments_rval -> dpe_ekf_step_update;
+//                                                with --device-loop: dpe_chm_dev_set_measurement_cov.  Not with --ranks > 1 / --graph
 //   dpe_flow --dump-grid <type> <dim> <spacing> <out.bin>        (grid builders only, no GPU)
 #include <cstdio>
 #include <cstdlib>
@@ -37,7 +42,8 @@
 static int run_device_loop(const std::string &samples, const std::string &handoff, const std::string &out, const std::string &rinex,
                            const std::string &loadGrid, double fs, double T, int iters, int gridDim, int gridType, int lpower, float spacing,
                            const float *delta, int L, int B, int fixLag, int device, bool timing, int ranks, int rank,
-                           const std::string &rendezvous, const std::string &commName, bool enableEkf, bool gridAxes)
+                           const std::string &rendezvous, const std::string &commName, bool enableEkf, bool gridAxes, bool measCov,
+                           const double *rho)
 {
     dsp::Flow flow;
     auto *bcs = new dsp::BatchCorrScores;
@@ -73,6 +79,9 @@ static int run_device_loop(const std::string &samples, const std::string &handof
     CHECK(flow.SetModParam("cuChanMgr", "DopplerSign", 1));
     CHECK(flow.SetModParam("cuChanMgr", "FixLag", fixLag));
     CHECK(flow.SetModParam("cuChanMgr", "EnableEKF", enableEkf));   // cuEKF's filter inside the measurement kernel (dpe_chm_dev_set_ekf)
+    CHECK(flow.SetModParam("cuChanMgr", "MeasurementCov", measCov));
+    CHECK(flow.SetModParam("cuChanMgr", "RhoPos", rho[0]));
+    CHECK(flow.SetModParam("cuChanMgr", "RhoVel", rho[1]));
     CHECK(flow.SetModParam("cuChanMgr", "XFilename", out.c_str()));
     if (!loadGrid.empty()) {
         CHECK(flow.SetModParam("BatchCorrManifold", "LoadPosGrid", true));
@@ -146,7 +155,8 @@ int main(int argc, char **argv)
     int ranks = 1, rank = 0, device = -1;
     double fs = 2.5e6, T = 0.02;
     int iters = 3000, gridDim = 25, gridType = 0, lpower = 1;
-    bool useGraph = false, timing = false, enableEkf = false, shardStage1 = false, deviceLoop = false, gridAxes = false;
+    bool useGraph = false, timing = false, enableEkf = false, shardStage1 = false, deviceLoop = false, gridAxes = false, measCov = false;
+    double rho[2] = {0.0, 0.0};
     int fixLag = 8;
     float spacing = 1.0f, delta[4] = {0, 0, 0, 0};
     for (int i = 1; i < argc; ++i) {
@@ -203,6 +213,11 @@ int main(int argc, char **argv)
         else if (a == "--shard-stage1") { shardStage1 = true; }
         else if (a == "--timing") { timing = true; }
         else if (a == "--ekf") { enableEkf = true; }
+        else if (a == "--measurement-cov") {
+            if (std::sscanf(next(), "%lf,%lf", &rho[0], &rho[1]) != 2) { std::fprintf(stderr, "--measurement-cov takes rho_pos,rho_vel\n"); return 2; }
+            measCov = true;
+            ++i;
+        }
         else if (a == "--device-loop") { deviceLoop = true; }
         else if (a == "--grid-axes") { gridAxes = true; }
         else if (a == "--fix-lag") { fixLag = std::atoi(next()); ++i; }
@@ -232,12 +247,25 @@ int main(int argc, char **argv)
         }
     }
 
+    if (measCov && !enableEkf) {
+        std::fprintf(stderr, "[DPEFlow] --measurement-cov needs --ekf (the pass-through ignores R)\n");
+        return 2;
+    }
+    if (measCov && (ranks > 1 || useGraph)) {
+        std::fprintf(stderr, "[DPEFlow] --measurement-cov is not available with --ranks > 1 (the sums of shards need an all-reduce) or --graph "
+                             "(the moments are not part of the Update's graph)\n");
+        return 2;
+    }
+    if (measCov && !(rho[0] >= 0.0 && rho[0] < 1.0 && rho[1] >= 0.0 && rho[1] < 1.0)) {
+        std::fprintf(stderr, "[DPEFlow] --measurement-cov: rho outside [0, 1)\n");
+        return 2;
+    }
     if (deviceLoop && (useGraph || shardStage1)) {
         std::fprintf(stderr, "[DPEFlow] --device-loop launches eagerly and correlates every channel on every rank (not with --graph / --shard-stage1)\n");
         return 2;
     }
     if (deviceLoop) return run_device_loop(samples, handoff, out, rinex, loadGrid, fs, T, iters, gridDim, gridType, lpower, spacing, delta, L, B,
-                                           fixLag, device, timing, ranks, rank, rendezvous, commName, enableEkf, gridAxes);
+                                           fixLag, device, timing, ranks, rank, rendezvous, commName, enableEkf, gridAxes, measCov, rho);
     dsp::Flow flow;                                             // dpeflow.cpp:55-62
     flow.Add(new dsp::DPInit);
     flow.Add(new dsp::SampleBlock);
@@ -267,6 +295,9 @@ int main(int argc, char **argv)
     CHECK(flow.SetModParam("BatchCorrManifold", "LPower", lpower));
     CHECK(flow.SetModParam("cuChanMgr", "DopplerSign", 1));
     CHECK(flow.SetModParam("cuEKF", "EnableEKF", enableEkf));   // dpeflow.cpp:90 ships false
+    CHECK(flow.SetModParam("BatchCorrManifold", "MeasurementCov", measCov));
+    CHECK(flow.SetModParam("BatchCorrManifold", "RhoPos", rho[0]));
+    CHECK(flow.SetModParam("BatchCorrManifold", "RhoVel", rho[1]));
     CHECK(flow.SetModParam("XECEFLogger", "Filename", out.c_str()));
     CHECK(flow.SetModParam("XECEFLogger", "CSV", true));
     if (!loadGrid.empty()) {

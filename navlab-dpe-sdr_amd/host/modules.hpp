@@ -20,6 +20,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -484,6 +485,11 @@ class BatchCorrManifold : public Module {
         InsertParam("UseGraph", &useGraph, BOOL_t, sizeof(bool), sizeof(bool));
         InsertParam("ReferencePair", &referencePair, BOOL_t, sizeof(bool), sizeof(bool));   // dpe_bcm_config.referencePair
         InsertParam("DeviceLoop", &deviceLoop, BOOL_t, sizeof(bool), sizeof(bool));         // coefficient blocks from cuChanMgrDev, no wait for the fix
+        // RVal from the manifold moments of the window's score rows (dpe_bcm_moments -> dpe_bcm_moments_rval) instead of the identity:
+        // thresholds RhoPos / RhoVel, floors from the spacing of the grids built here.  (With DeviceLoop the same switch is cuChanMgr's.)
+        InsertParam("MeasurementCov", &measurementCov, BOOL_t, sizeof(bool), sizeof(bool));
+        InsertParam("RhoPos", &rhoPos, DOUBLE_t, sizeof(double), sizeof(double));
+        InsertParam("RhoVel", &rhoVel, DOUBLE_t, sizeof(double), sizeof(double));
         // multi-GPU (one flow per GPU): this flow scores grid shard ShardRank of ShardCount and exchanges the arg-max
         InsertParam("ShardRank", &shardRank, INT_t, sizeof(int), sizeof(int));
         InsertParam("ShardCount", &shardCount, INT_t, sizeof(int), sizeof(int));
@@ -562,6 +568,7 @@ class BatchCorrManifold : public Module {
         UpdateOutput(2, (uint32_t)timeGrid.size(), timeGrid.data(), 0);
         UpdateOutput(3, (uint32_t)cfg.posGridSize, (void *)ps, 0);
         for (int i = 0; i < 64; ++i) RVal[i] = (i % 9 == 0) ? 1.0 : 0.0;                                  // :2003-2011,2055-2063
+        if (measurementCov) { QuantisationFloor(0, floorVar[0]); QuantisationFloor(1, floorVar[1]); }     // (a sort of the grid: once)
         Started = true;
         return 0;
     }
@@ -602,6 +609,15 @@ class BatchCorrManifold : public Module {
                 DPE_MOD_FAIL("Update: " << dpe_last_error());
         } else if (dpe_bcm_results(h, &r, st)) return -1;                                                  // synchronises, :2606-2632
         std::memcpy(zVal, r.zVal, sizeof(zVal));
+        if (measurementCov) {   // the window's R: its moments in the frame it was scored in, plus the grids' quantisation floor
+            if (comm) DPE_MOD_FAIL("Update: MeasurementCov is not available on a sharded grid");
+            dpe_bcm_moments_config mc = {};
+            mc.rho[0] = rhoPos; mc.rho[1] = rhoVel;
+            dpe_bcm_moments_result mr;
+            int32_t fallback = 0;
+            if (dpe_bcm_moments(h, &mc, st) || dpe_bcm_moments_results(h, &mr, st) || dpe_bcm_moments_rval(mr.sums, win.enu2ecef, floorVar, RVal, &fallback))
+                DPE_MOD_FAIL("Update: " << dpe_last_error());
+        }
         last = r;
         return 0;
     }
@@ -622,6 +638,24 @@ class BatchCorrManifold : public Module {
     const std::vector<double> &PosGrid() const { return posGrid; }
     const std::vector<double> &VelGrid() const { return velGrid; }
     bool Axes() const { return axes; }           // the grids went to the engine as axes: PosGrid() / VelGrid() are empty
+    // h^2 / 12 per (E, N, U, t) axis of manifold m (0 position, 1 velocity), h = the smallest non-zero spacing of the axis' values:
+    // the variance of the grid's own quantisation; an axis with a single value gets 0
+    void QuantisationFloor(int m, double out[4]) const
+    {
+        const std::vector<double> &g = m ? velGrid : posGrid;
+        for (int c = 0; c < 4; ++c) {
+            std::vector<double> v;
+            if (axes) v = m ? velAx[c] : posAx[c];
+            else for (size_t i = c; i < g.size(); i += 4) v.push_back(g[i]);
+            std::sort(v.begin(), v.end());
+            double hMin = 0.0;
+            for (size_t i = 1; i < v.size(); ++i) {
+                const double d = v[i] - v[i - 1];
+                if (d > 0.0 && (hMin == 0.0 || d < hMin)) hMin = d;
+            }
+            out[c] = hMin * hMin / 12.0;
+        }
+    }
 
   private:
     dpe_bcm *h = nullptr;
@@ -629,6 +663,8 @@ class BatchCorrManifold : public Module {
     std::vector<double> posAx[4], velAx[4];
     int posDim = 25, velDim = 25, gridType = 0, LPower = 1;
     bool useGraph = false, deviceLoop = false;
+    bool measurementCov = false;
+    double rhoPos = 0.0, rhoVel = 0.0, floorVar[2][4] = {};
     bool referencePair = false;   // reproduce the reference's floor(idx) / floor(idx + 1) pair where it double-counts (dpe_hip.h)
     int shardRank = 0, shardCount = 1, commBackend = DPE_COMM_RCCL;
     char commRendezvous[512] = "";
@@ -823,6 +859,10 @@ class cuChanMgrDev : public Module {
         InsertParam("DopplerSign", &dopplerSign, INT_t, sizeof(int), sizeof(int));
         InsertParam("EnableEKF", &enableEkf, BOOL_t, sizeof(bool), sizeof(bool));   // cuEKF's parameter: the filter runs in this module's measurement kernel
         InsertParam("FixLag", &fixLag, INT_t, sizeof(int), sizeof(int));
+        // with EnableEKF: the filter's R from the manifold moments of each window (dpe_chm_dev_set_measurement_cov), thresholds RhoPos / RhoVel
+        InsertParam("MeasurementCov", &measurementCov, BOOL_t, sizeof(bool), sizeof(bool));
+        InsertParam("RhoPos", &rhoPos, DOUBLE_t, sizeof(double), sizeof(double));
+        InsertParam("RhoVel", &rhoVel, DOUBLE_t, sizeof(double), sizeof(double));
         InsertParam("XFilename", xFilename, CHAR_t, sizeof(xFilename), 0);
         const char *out[18] = {"rxTime", "txTime", "CodePhaseStart", "CarrierPhaseStart", "CodePhaseEnd", "CarrierPhaseEnd",
                                "CodeFrequency", "CarrierFrequency", "SatStates", "DopplerSign", "ValidPRNs", "cpReference",
@@ -869,6 +909,13 @@ class cuChanMgrDev : public Module {
             if (inputs[12]) std::memcpy(ec.P0, inputs[12]->Data, sizeof(ec.P0));
             else for (int i = 0; i < 64; ++i) ec.P0[i] = (i % 9 == 0) ? 1.0 : 0.0;
             if (dpe_chm_dev_set_ekf(h, &ec)) DPE_MOD_FAIL("Start: " << dpe_last_error());
+        }
+        if (measurementCov) {
+            const double rho[2] = {rhoPos, rhoVel};
+            double pf[4], vf[4];
+            bcm->QuantisationFloor(0, pf);
+            bcm->QuantisationFloor(1, vf);
+            if (dpe_chm_dev_set_measurement_cov(h, rho, pf, vf)) DPE_MOD_FAIL("Start: " << dpe_last_error());
         }
         if (bcm->Comm() &&
             dpe_chm_dev_set_shard(h, bcm->Comm(), bcm->Axes() ? nullptr : bcm->PosGrid().data(), (int64_t)bcm->PosGrid().size() / 4,
@@ -945,7 +992,8 @@ class cuChanMgrDev : public Module {
     BatchCorrManifold *bcm;
     dpe_chm_dev *h = nullptr;
     int K = 0, dopplerSign = 1, fixLag = 8;
-    bool enableEkf = false;
+    bool enableEkf = false, measurementCov = false;
+    double rhoPos = 0.0, rhoVel = 0.0;
     long long enq = 0, got = 0;
     bool warned = false;
     char xFilename[512] = "";

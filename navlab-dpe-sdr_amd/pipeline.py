@@ -146,7 +146,7 @@ def run_closed_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
 
 def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), init_delta=(0, 0, 0, 0), K=None, lpower=1,
                     ring_depth=64, stream=None, reference_pair=False, keep_scores=False, enable_ekf=False, couple_velocity=True,
-                    doppler_sign=1):
+                    doppler_sign=1, measurement_cov=None):
     """The same loop with nothing read back per window: the channel manager lives on the device (engine.ChanMgrDev), forms
     the measurement from the scan's keys, passes it through and writes the next window's parameter blocks; the host enqueues
         BatchCorrScores.UpdatePrepared -> BatchCorrManifold.UpdatePrepared -> ChanMgrDev.step
@@ -155,7 +155,10 @@ def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
     keep_scores (tests): waits for every window and keeps its position and velocity scores, its code banks and the channel manager's outputs the
     window was scored with (`inputs` = ChanMgrDev.outputs() before the window) -- the loop then does read back.
     enable_ekf: cuEKF's filter inside the measurement kernel (dpe_chm_dev_set_ekf) instead of the pass-through; the fixes are then x_k|k.
-    doppler_sign: the channel manager's DopplerSign, as in run_closed_loop."""
+    doppler_sign: the channel manager's DopplerSign, as in run_closed_loop.
+    measurement_cov: None (R = I), or (rho_pos, rho_vel) with enable_ekf: the device filter takes R from each window's manifold
+    moments plus the grids' quantisation floors (ChanMgrDev.set_measurement_cov; still nothing read back per window).  The result
+    dicts then carry RVal (the R the filter took), sums, nAbove, threshold and fallback (ChanMgrDev.rval)."""
     def make_bcm(S, nfft, L, B, K):
         return engine.BatchCorrManifold(fs, S, nfft, pos_grid, vel_grid, LPower=lpower, lag_half_width=L, bin_half_width=B,
                                         max_channels=K, reference_pair=reference_pair)
@@ -173,11 +176,20 @@ def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
         bcs, bcm, cm, W, K = lp.bcs, lp.bcm, lp.cm, lp.W, lp.K
         if enable_ekf:
             cm.set_ekf(lp.S / fs, lp.x, couple_velocity=couple_velocity)
+        if measurement_cov is not None:
+            cm.set_measurement_cov(measurement_cov, quantisation_floor(pos_grid), quantisation_floor(vel_grid))
         cm.Start(lp.x, stream)
         fixes, results, got = np.zeros((W, 8)), [], 0
+
+        def collect(w):      # (the R record lives in a ring of the fix ring's depth: collected with the fix)
+            r = cm.fix(w)
+            if measurement_cov is not None:
+                rv = cm.rval(w, stream)
+                r.update(RVal=rv["R"], sums=rv["sums"], nAbove=rv["nAbove"], threshold=rv["threshold"], fallback=rv["fallback"])
+            return r
         for w in range(W):
             while w - got >= ring_depth - 1:          # never more than the ring holds ahead of the fixes already collected
-                results.append(cm.fix(got))
+                results.append(collect(got))
                 got += 1
             inputs = cm.outputs(stream=stream) if keep_scores else None     # (the previous window's time update has run: fix() flushed it)
             bcs.UpdatePrepared(lp.iq_d[w], K, stream)
@@ -185,14 +197,14 @@ def run_device_loop(iq_windows, ho, fs, pos_grid, vel_grid, time_grid=(0.0,), in
             cm.step(stream)
             if keep_scores:
                 while got <= w:
-                    results.append(cm.fix(got))
+                    results.append(collect(got))
                     got += 1
                 ps, vs = bcm.read_scores(stream)
                 results[w]["posScores"], results[w]["velScores"] = ps[0].copy(), vs[0].copy()
                 results[w]["codeBank"] = bcs.read_banks(stream)[0][0].copy()
                 results[w]["inputs"] = inputs
         while got < W:
-            results.append(cm.fix(got))
+            results.append(collect(got))
             got += 1
         for w, r in enumerate(results):
             fixes[w] = r["zVal"]
