@@ -21,12 +21,12 @@
 #include <type_traits>
 
 #include "dpe_common.h"
+#include "dpe_bcs_plan.h"   // the launch plan and its constants (kSub, kSumSlots, kPass, ...): plain C++
 #include "dpe_prep.h"
 #include "dpe_chm_dev.h"   // chm_k2: the device-resident channel manager's time update, carried as an extra block (FUSE form)
 
 namespace dpe {
 
-constexpr int kSub = 256;   // samples per wave sub-tile (4 per lane) == moment block
 constexpr int kNMomMax = 6;  // power moments 0..5 at most; 4 when the bin window is narrow (chosen at create)
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -87,7 +87,6 @@ __device__ __forceinline__ f2 table_fix(f2 wv, const BcsChanDev &ch, const doubl
 // DC sum (thrust::reduce at batchcorrscores.cu:1065): exact int64 sums.  Each block writes its own slot
 // sums[w][blockIdx.x][2] (no atomics, nothing to zero beforehand -- the whole Update stays free of memset
 // nodes, which matters for the hipGraph replay); consumers add the <= kSumSlots slots (window_mean).
-constexpr int kSumSlots = 64;
 __device__ __forceinline__ void sum_body(const int16_t *__restrict__ iq, long long winStride, int S, long long *__restrict__ sums)
 {
     const int w = blockIdx.y;
@@ -413,7 +412,6 @@ __global__ __launch_bounds__(256) void bcs_bank_kernel(BcsParamBlock pb, int inl
 // once per 16 samples instead of once per 4.  Used when the batch offers enough passes to fill the chip
 // (dpe_bcs_update); single windows keep the 4-samples-per-lane kernel, whose blocks are 4x shorter.
 // Same partial / moment layouts, so bcs_finalize_kernel is shared.
-constexpr int kB16Blocks = 4;   // blocks per CU the narrow, table-free form is held to (128 registers; five -> 96 with spills measured 1 % slower)
 template <int LH, int kNMom, bool TABLE>
 __global__ __launch_bounds__(256, (LH <= 4 && !TABLE) ? kB16Blocks : 3) void bcs_bank16_kernel(BcsParamBlock pb, int inl, const int16_t *__restrict__ iq, long long winStride,
                                                          int S, int K, int nW, int nSub, int tilesPerBlock, int nBlk, int vecOK, int nSumBlk,
@@ -1121,45 +1119,21 @@ __global__ void bcs_export_kernel(const float2 *__restrict__ bank, int n, long l
 // ============================================================================================
 struct dpe_bcs {
     dpe_bcs_config cfg;
-    int LH;             // internal lag half width (4,8,16,32)
-    int nSub, nBlk, tilesPerBlock, nMom;
-    bool wideAllowed = true;     // (-DDPE_EXPERIMENTS builds: DPE_BCS_NO_WIDE=1 at create keeps the dense kernel)
-    bool bank16Allowed = true;   // DPE_BCS_NO_BANK16=1: never the 16-samples-per-lane batch kernel (A/B tests)
-    bool fuseAllowed = true;     // DPE_BCS_NO_FUSE=1: always the separate DC-sum kernel (A/B tests)
-    bool chipAllowed = true;     // DPE_BCS_NO_CHIP=1: never the chip-boundary kernel (A/B tests)
-    bool chipOK = false;         // create-time eligibility of the chip-boundary kernel (dpe_bcs_chip.h)
-    bool chip2Allowed = true;    // DPE_BCS_NO_CHIP2=1: never the lanes-as-chips form (dpe_bcs_chip2.h; A/B tests)
-    int chip2Resident = 0;       // co-resident waves of that kernel on the whole device
-    int chip2PForce = 0;         // DPE_BCS_CHIP2_P at create: passes per tile of that kernel (experiments)
-    int cus = 256;
-    int nPassChip = 0, nBlkAlloc = 0;
-    // full-length FFT fallback (dpe_bcs_fft.h): lag windows beyond DPE_MAX_LAG_HALF_WIDTH, bin windows beyond the moment
-    // expansion, or DPE_BCS_FORCE_FFT=1 at create (A/B tests)
-    bool fftMode = false, havePlans = false;
+    dpe::BcsShape sh;   // everything create derives from cfg, the device and the switches (dpe_bcs_plan.h)
+    bool havePlans = false;   // full-length FFT fallback (dpe_bcs_fft.h, sh.fftMode)
     dpe::FftPlan planS3, planS2, planC;   // rocFFT: length S, batch 3 chunk K (forward) / 2 chunk K (inverse); length C, batch chunk K
     int planK = 0;        // channels per window the plans are made for (the Update's nChan: re-planned when it changes)
     int fftChunkW = 1;
     float2 *fftWork_d = nullptr;
     int chipDbg = 0;                   // -DDPE_EXPERIMENTS builds only, DPE_BCS_CHIP_DBG: skips parts of the chip kernel (timing; wrong results)
-    int fatForce = -1;                 // -DDPE_EXPERIMENTS builds only, DPE_BCS_FAT at create: finalize block shape (0 split, 1 fat)
-    int chipTpbForce = 0;              // DPE_BCS_CHIP_TPB at create: passes per wave of the chip kernel (experiments)
-    int tpb16Force = 0;                // DPE_BCS_TPB16 at create: tiles per block of the 16-samples-per-lane kernel (experiments)
-    int resident16 = 1024;             // co-resident blocks of the 16-samples-per-lane kernel on the whole device
-    int chipResident = 0;              // co-resident waves of the chip kernel on the whole device
-    int chipTpbMax = 1;                // longest tile (passes) whose 6-moment block still meets the Taylor bound
-    long long C;
     int8_t *chipTable_d = nullptr;
     uint32_t *chipBits_d = nullptr;   // the same chips as sign bits, periodically extended (bcs_bank_chip2_kernel: scalar loads)
-    double *tTable_d = nullptr;   // ns-rounded sample times (always allocated; used only when useTable)
-    bool useTable = false;
+    double *tTable_d = nullptr;   // ns-rounded sample times (always allocated; used only when sh.useTable)
     long long *sums_d = nullptr;
     unsigned long long *rideWord_d = nullptr;   // [maxWindows][kSumSlots] {epoch, I, Q} words of the sums computed inside the chip2 launch
     unsigned rideEpoch = 0;                     // cycles 1 .. 3
     int rideW = 0, rideSlots = 0;               // the slot set the last such launch wrote
-    bool rideAllowed = true;                    // DPE_BCS_NO_SUMRIDE=1: DC-sum kernel in front of the chip2 kernel, as before (A/B runs)
-    int rideLA = 4;                             // look-ahead of the sum blocks in windows (-DDPE_EXPERIMENTS builds: DPE_BCS_RIDE_LA)
     int rideSpin = dpe::kRideSpinDefault;       // polls after which a correlator block sums its window itself (DPE_BCS_RIDE_SPIN; tests force 1)
-    int rideMinW = 48;                          // smallest batch that takes the riding form (measured at H: 8 / 16 windows slower, 32 equal, 64 -1.2 %, 128 -2.6 %); DPE_BCS_SUMRIDE_MIN
     dpe::BcsChanDev *chan_d = nullptr;
     // pinned parameter staging: a ring of kStaging blocks, each guarded by an event recorded once its H2D copy (or the
     // graph that contains it) has been enqueued -- Updates may be issued kStaging - 1 deep without waiting
@@ -1184,26 +1158,27 @@ struct dpe_bcs {
     dpe::GraphCache graphs;
 };
 
-// Blocks per window of the DC-sum kernel: ~8192 samples per block for batches; few windows get up to
-// one int4 load per thread (a lone window is latency-bound, not bandwidth-bound).
-static int sum_blocks(int S, int nWindows)
+// The environment switches of dpe_hip.h, read once per create.
+static dpe::BcsSwitches bcs_read_switches()
 {
-    const int base = S / 8192 > 0 ? S / 8192 : 1;
-    const int fine = (S / 4 + 255) / 256;
-    int want = 512 / nWindows < fine ? 512 / nWindows : fine;
-    if (want < base) want = base;
-    return want > dpe::kSumSlots ? dpe::kSumSlots : want;
-}
-
-// widest supported lag window: the centre chunk (+-32) plus 4 chunks of 65 lags on each side
-static constexpr int kMaxLagHalfWidth = DPE_MAX_LAG_HALF_WIDTH;
-static_assert(kMaxLagHalfWidth == 32 + 4 * 65, "centre chunk plus four 65-lag chunks per side");
-
-static long long next_pow2(long long x)
-{
-    long long p = 1;
-    while (p < x) p <<= 1;
-    return p;
+    dpe::BcsSwitches sw;
+    const auto num = [](const char *name) { const char *e = getenv(name); return e ? atoi(e) : 0; };
+    sw.forceFft = getenv("DPE_BCS_FORCE_FFT") != nullptr;
+    sw.noBank16 = getenv("DPE_BCS_NO_BANK16") != nullptr;
+    sw.noFuse = getenv("DPE_BCS_NO_FUSE") != nullptr;
+    sw.noChip = getenv("DPE_BCS_NO_CHIP") != nullptr;
+    sw.noChip2 = getenv("DPE_BCS_NO_CHIP2") != nullptr;
+    sw.noSumRide = num("DPE_BCS_NO_SUMRIDE") != 0;
+    sw.sumRideMin = num("DPE_BCS_SUMRIDE_MIN");
+    sw.chip2P = num("DPE_BCS_CHIP2_P");
+    sw.chipTpb = num("DPE_BCS_CHIP_TPB");
+    sw.tpb16 = num("DPE_BCS_TPB16");
+#ifdef DPE_EXPERIMENTS   // ablation switches: never in the product library
+    sw.noWide = getenv("DPE_BCS_NO_WIDE") != nullptr;
+    sw.rideLA = num("DPE_BCS_RIDE_LA");
+    if (const char *e = getenv("DPE_BCS_FAT")) sw.fat = e[0] == '1' ? 1 : 0;
+#endif
+    return sw;
 }
 
 extern "C" {
@@ -1219,35 +1194,24 @@ int dpe_bcs_create(const dpe_bcs_config *cfg, dpe_bcs **out)
     DPE_REQUIRE(cfg->lagHalfWidth >= 1 && 2 * (long long)cfg->lagHalfWidth + 1 < cfg->samplesPerWindow,
                 "[BatchCorrScores] create: lagHalfWidth %d not in [1, S/2)", cfg->lagHalfWidth);
     DPE_REQUIRE(cfg->binHalfWidth >= 1, "[BatchCorrScores] create: binHalfWidth < 1");
-    bool fftMode = getenv("DPE_BCS_FORCE_FFT") != nullptr;   // full-length FFT form instead of the streaming kernels
-    if (cfg->lagHalfWidth > kMaxLagHalfWidth || cfg->lagHalfWidth + 32 + dpe::kSub >= cfg->samplesPerWindow) fftMode = true;
-    const int S = cfg->samplesPerWindow;
-    const long long C = 8 * next_pow2(S);  // batchcorrscores.cu:761
-    // Taylor remainder of the moment expansion must stay below fp32 rounding (see file header)
-    const double th = 6.283185307179586 * 127.5 * cfg->binHalfWidth / (double)C;
-    const int nMom = (std::pow(th, 4) / 24.0 < 1e-7) ? 4 : 6;   // Taylor order of the moment expansion
-    DPE_REQUIRE(2 * (long long)cfg->binHalfWidth + 1 < C, "[BatchCorrScores] create: binHalfWidth %d not below C/2 = %lld",
-                cfg->binHalfWidth, C / 2);
-    if (!(std::pow(th, 6) / 720.0 < 2e-7)) fftMode = true;   // bin window too wide for the moment expansion at this C
-    // The reference rounds the sample times to 1 ns (BCS_GenTimeIdcs :191-193).  For integer-ns sampling
-    // periods (all usual SDR rates) that is a no-op and the kernels use n/fs; otherwise they read the
-    // reference's own table.
-    const double fs = cfg->samplingFrequency;
-    bool needTable = false;
-    for (int n = 0; n < S && !needTable; ++n) {
-        const double t = (double)n / fs, tr = std::round(t * 1.0e9) / 1.0e9;
-        if (std::fabs(t - tr) > 4e-16 * (t + 1e-9)) needTable = true;
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    BcsShape sh = bcs_shape(*cfg, bcs_read_switches(), cus);
+    DPE_REQUIRE(2 * (long long)cfg->binHalfWidth + 1 < sh.C, "[BatchCorrScores] create: binHalfWidth %d not below C/2 = %lld",
+                cfg->binHalfWidth, sh.C / 2);
+    if (sh.chipOK) {
+        int nbChip = 0, nbChip2 = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbChip, (const void *)bcs_bank_chip_kernel<6>, 64, 0) != hipSuccess) nbChip = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbChip2, (const void *)bcs_bank_chip2_kernel<6, 24>, 64, 0) != hipSuccess) nbChip2 = 0;
+        bcs_shape_residency(sh, nbChip, nbChip2);
     }
+    const int S = sh.S;
+    const long long C = sh.C;
+    const double fs = sh.fs;
     dpe_bcs *h = new dpe_bcs();
     h->cfg = *cfg;
-    h->C = C;
-    h->nMom = nMom;
-    h->fftMode = fftMode;
-    h->LH = cfg->lagHalfWidth <= 4 ? 4 : cfg->lagHalfWidth <= 8 ? 8 : cfg->lagHalfWidth <= 16 ? 16 : 32;
-    h->nSub = (S + kSub - 1) / kSub;
-    const int nTiles = (h->nSub + 3) / 4;
-    h->tilesPerBlock = (nTiles + 63) / 64;   // fewest tiles per block ever used -> sizes the partial buffer
-    h->nBlk = (nTiles + h->tilesPerBlock - 1) / h->tilesPerBlock;
+    h->sh = sh;
     const size_t W = cfg->maxWindows, K = cfg->maxChannels;
     std::vector<int8_t> table(37 * 1024, 0);
     for (int prn = 1; prn <= 37; ++prn) gen_ca_code_host(prn, table.data() + (prn - 1) * 1024);
@@ -1262,59 +1226,15 @@ int dpe_bcs_create(const dpe_bcs_config *cfg, dpe_bcs **out)
         for (int n = 0; n < S; ++n) tt[n] = std::round(((double)n / fs) * 1.0e9) / 1.0e9;
         h->tTable_d = dev_alloc<double>(S);
         if (h->tTable_d) (void)hipMemcpy(h->tTable_d, tt.data(), sizeof(double) * S, hipMemcpyHostToDevice);
-        h->useTable = needTable;
     }
     h->sums_d = dev_alloc<long long>(2 * W * kSumSlots);
     h->rideWord_d = dev_alloc<unsigned long long>(W * kSumSlots);
     if (h->rideWord_d) (void)hipMemset(h->rideWord_d, 0, sizeof(unsigned long long) * W * kSumSlots);
-    h->rideAllowed = !(getenv("DPE_BCS_NO_SUMRIDE") && atoi(getenv("DPE_BCS_NO_SUMRIDE")) != 0);
-    if (getenv("DPE_BCS_SUMRIDE_MIN") && atoi(getenv("DPE_BCS_SUMRIDE_MIN")) >= 1) h->rideMinW = atoi(getenv("DPE_BCS_SUMRIDE_MIN"));
-#ifdef DPE_EXPERIMENTS
-    if (getenv("DPE_BCS_RIDE_LA") && atoi(getenv("DPE_BCS_RIDE_LA")) >= 1) h->rideLA = atoi(getenv("DPE_BCS_RIDE_LA"));
-#endif
     if (getenv("DPE_BCS_RIDE_SPIN") && atoi(getenv("DPE_BCS_RIDE_SPIN")) >= -1) h->rideSpin = atoi(getenv("DPE_BCS_RIDE_SPIN"));
     h->chan_d = dev_alloc<BcsChanDev>(W * K);
-    // chip-boundary kernel (dpe_bcs_chip.h): lag windows of 17..31 samples (wider: chunks of 64 lags) at sampling rates where a
-    // sub-tile holds few chips, plain n/fs sample times; its moment block is one pass of kPass samples, and a chip's
-    // second-order term (theta len)^2 / 24 must stay below fp32 rounding
-    h->nPassChip = (S + kPass - 1) / kPass;
-    {
-        const double thetaB = 6.283185307179586 * cfg->binHalfWidth / (double)C;   // phase step per sample of the outermost bin
-        const double chipLen = fs / kFCA * 1.001;
-        // the moment block is the wave's tile of tpb passes, 6 moments: (thetaB tpb kPass / 2)^6 / 720 < 2e-7
-        const double halfMax = std::pow(2e-7 * 720.0, 1.0 / 6.0) / thetaB;
-        h->chipTpbMax = (int)(2.0 * halfMax / kPass);
-        if (h->chipTpbMax > 32) h->chipTpbMax = 32;
-        h->chipOK = h->LH == 32 && !needTable && (kFCA / fs) * 128.0 < 40.0 && h->chipTpbMax >= 1 && chipLen < 31.0 &&
-                    (thetaB * chipLen) * (thetaB * chipLen) / 24.0 < 5e-7 && S >= 2 * kPass;
-    }
-    h->nBlkAlloc = h->nBlk;
-    {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        h->resident16 = ((h->LH <= 4 && !needTable) ? dpe::kB16Blocks : 3) * cus;   // the kernel's launch bounds
-        h->cus = cus;
-    }
-    if (h->chipOK) {
-        // partial sums of up to 128 blocks per (window, SV); a handle for a few windows gets one block per pass
-        int want = (int)(2048 / W) > 128 ? (int)(2048 / W) : 128;
-        if (want > h->nPassChip) want = h->nPassChip;
-        if (want < (h->nPassChip + h->chipTpbMax - 1) / h->chipTpbMax) want = (h->nPassChip + h->chipTpbMax - 1) / h->chipTpbMax;
-        if (h->nBlkAlloc < want) h->nBlkAlloc = want;
-        int dev = 0, cus = 256, nb = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        h->chipResident = 12 * cus;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)bcs_bank_chip_kernel<6>, 64, 0) == hipSuccess && nb > 0)
-            h->chipResident = nb * cus;
-        h->chip2Resident = 11 * cus;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)bcs_bank_chip2_kernel<6, 24>, 64, 0) == hipSuccess && nb > 0)
-            h->chip2Resident = nb * cus;
-    }
-    h->part_d = dev_alloc<float2>(W * K * h->nBlkAlloc * 2 * (2 * h->LH + 1));
-    h->mom_d = dev_alloc<float2>(W * K * 2 * h->nSub * kNMomMax);
-    h->momRep_d = dev_alloc<float2>(W * K * 2 * h->nSub * kNMomMax);
+    h->part_d = dev_alloc<float2>(W * K * sh.nBlkAlloc * 2 * (2 * sh.LH + 1));
+    h->mom_d = dev_alloc<float2>(W * K * 2 * sh.nSub * kNMomMax);
+    h->momRep_d = dev_alloc<float2>(W * K * 2 * sh.nSub * kNMomMax);
     h->codeBank_d = dev_alloc<float2>(W * K * (2 * cfg->lagHalfWidth + 1));
     h->carrBank_d = dev_alloc<float2>(W * K * (2 * cfg->binHalfWidth + 1));
     h->info_d = dev_alloc<int>(W * K);
@@ -1337,7 +1257,7 @@ int dpe_bcs_create(const dpe_bcs_config *cfg, dpe_bcs **out)
         DPE_CHECK_HIP(hipMemset(h->carrBank_d, 0, W * K * (2 * cfg->binHalfWidth + 1) * sizeof(float2)));
         for (hipEvent_t &e : h->stagingFree) DPE_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         DPE_CHECK_HIP(hipHostGetDevicePointer((void **)&h->chanBase_hd, h->chanBase_h, 0));
-        if (h->fftMode) {
+        if (sh.fftMode) {
             // windows per chunk: at most 2^27 complex work elements (1 GB); planes b, rX, rY of [chunk][K][S], reused as [chunk][K][C]
             const size_t perW = K * (size_t)(3 * (size_t)S > (size_t)C ? 3 * (size_t)S : (size_t)C);
             size_t chunk = ((size_t)1 << 27) / perW;
@@ -1359,19 +1279,8 @@ int dpe_bcs_create(const dpe_bcs_config *cfg, dpe_bcs **out)
     }
     h->idxNext_h.assign(W * K, 0);
     h->chan_h = h->chanBase_h;
-#ifdef DPE_EXPERIMENTS
-    h->wideAllowed = getenv("DPE_BCS_NO_WIDE") == nullptr;
-#endif
-    h->bank16Allowed = getenv("DPE_BCS_NO_BANK16") == nullptr;
-    h->fuseAllowed = getenv("DPE_BCS_NO_FUSE") == nullptr;
-    h->chipAllowed = getenv("DPE_BCS_NO_CHIP") == nullptr;
-    h->chip2Allowed = getenv("DPE_BCS_NO_CHIP2") == nullptr;
-    if (const char *e = getenv("DPE_BCS_CHIP2_P")) h->chip2PForce = atoi(e);
-    if (const char *e = getenv("DPE_BCS_CHIP_TPB")) h->chipTpbForce = atoi(e);
-    if (const char *e = getenv("DPE_BCS_TPB16")) h->tpb16Force = atoi(e);
-#ifdef DPE_EXPERIMENTS   // ablation switches: never in the product library (the first one makes the banks wrong)
+#ifdef DPE_EXPERIMENTS   // ablation switch: never in the product library (it makes the banks wrong)
     if (const char *e = getenv("DPE_BCS_CHIP_DBG")) h->chipDbg = atoi(e);
-    if (const char *e = getenv("DPE_BCS_FAT")) h->fatForce = e[0] == '1' ? 1 : 0;
 #endif
     *out = h;
     return 0;
@@ -1394,28 +1303,32 @@ int dpe_bcs_destroy(dpe_bcs *h)
     return 0;
 }
 
-// chan_host == nullptr: the channel parameters of this (single-window) call are already in h->chan_d, written by
-// bcs_prep_kernel earlier on `stream` (dpe_bcs_update_dev) -- nothing the host decides below may then depend on their values,
-// except the choice of a chip-boundary kernel at high sampling rates (which fetches them first, see there).
-// rerun = 1 (internal): the guarded general kernels behind a hinted chip-kernel launch (see BcsParamBlock::guard).
-static int bcs_update_impl(dpe_bcs *h, const int16_t *samples_dev, int64_t windowStrideSamples, int32_t nWindows,
-                           int32_t nChan, const dpe_chan_start *chan_host, dpe_stream_t stream_, int rerun = 0)
+}  // extern "C"
+
+// ---- Update: staging, channel facts, plan (dpe_bcs_plan.h), launch -----------------------------------------------------------
+
+// Run-time value -> template argument: pick<4, 8, 16, 32>(LH, f) calls f(std::integral_constant<int, 4>{}) when LH == 4, ...; a value
+// outside the list calls nothing (the callers' values are in their lists by construction of the plan).
+template <int V, int... Vs, class F>
+static inline void pick(int v, F &&f)
+{
+    if (v == V) f(std::integral_constant<int, V>{});
+    else if constexpr (sizeof...(Vs) > 0) pick<Vs...>(v, f);
+}
+template <class F>
+static inline void pick_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// The dpe_chan_start -> BcsChanDev loop of the host-parameter form, into the staging block.
+static int bcs_stage_host_params(dpe_bcs *h, const dpe_chan_start *chan_host, int n)
 {
     using namespace dpe;
-    const bool dev = chan_host == nullptr;
-    DPE_REQUIRE(h && samples_dev, "[BatchCorrScores] Update: null argument");
-    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrScores] Update: nWindows %d out of range", nWindows);
-    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrScores] Update: nChan %d out of range", nChan);
     const int S = h->cfg.samplesPerWindow;
-    DPE_REQUIRE(nWindows == 1 || windowStrideSamples >= S, "[BatchCorrScores] Update: window stride < S");
-    hipStream_t stream = (hipStream_t)stream_;
     const double fs = h->cfg.samplingFrequency;
-    // next staging block of the ring; an Update issued kStaging calls ago may still be copying it (no-op otherwise)
-    h->slot = (h->slot + 1) % dpe_bcs::kStaging;
-    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
-    h->chan_h = h->chanBase_h + (size_t)h->slot * h->cfg.maxWindows * h->cfg.maxChannels;
-    h->lastDev = dev;
-    for (int i = 0; !dev && i < nWindows * nChan; ++i) {
+    for (int i = 0; i < n; ++i) {
         const dpe_chan_start &c = chan_host[i];
         DPE_REQUIRE(c.prn >= 1 && c.prn <= kPrnMax, "[BatchCorrScores] Update: PRN %d out of range", c.prn);
         DPE_REQUIRE(c.codeFrequency > 0 && c.codePhaseStart >= 0, "[BatchCorrScores] Update: bad code phase/frequency");
@@ -1438,24 +1351,37 @@ static int bcs_update_impl(dpe_bcs *h, const int16_t *samples_dev, int64_t windo
         d.pad = 0;
         h->idxNext_h[i] = d.idxNext;
     }
-    // chip-boundary kernel: the closed-form DC term of a chip needs 2 pi |fi| / fc <= 0.25 (|fi| below ~40 kHz).  Its
-    // eligibility (and the second form's below) is a property of the channel VALUES.  The device-parameter form has them
-    // only on the device: at sampling rates where these kernels exist at all (>= 16 samples per chip) it reads back the
-    // block bcs_prep_kernel has just derived -- <= 3 KB and one stream wait per window, against a 4-5 x slower stage 1;
-    // at lower rates nothing is fetched and nothing the host decides depends on the values.
-    bool chip = h->chipOK && h->chipAllowed && !rerun;
-    bool hintedCall = false;   // this call chose the chip kernels on the caller's promise: the guarded re-run follows it
-    if (dev && (h->devHint & 1) && __atomic_load_n(h->hintViol_h, __ATOMIC_RELAXED)) {
-        // a device-side check found the promise broken in an earlier window (flagged there: status bit 3): the hint is withdrawn for the
-        // life of the handle -- from here on the call reads the derived block back and chooses the kernel from the real values
-        h->devHint &= ~1;
-    }
-    if (chip && dev && (h->devHint & 1)) {
-        hintedCall = true;
-        // the caller's promise (dpe_bcs_set_dev_hint): decide from nominal values -- code frequency F_CA within 1e-5 (ten times the
-        // largest code Doppler), carrier offset inside the closed-form DC term's range -- and let bcs_prep_kernel check what was
-        // promised (status bit 3); nothing is read back, the host does not wait for the stream
-        for (int i = 0; i < nWindows * nChan; ++i) {
+    return 0;
+}
+
+// The caller's promise for the device-parameter form (dpe_bcs_set_dev_hint): the chip kernels are chosen from NOMINAL channel
+// values -- code frequency F_CA within 1e-5 (ten times the largest code Doppler), carrier offset inside the closed-form DC term's
+// range -- and bcs_prep_kernel / chm_k1 check what was promised (hintL1, hintStepMax; status bit 3, the pinned violation word).
+// A raised violation word withdraws the hint for the life of the handle.
+struct BcsHint {
+    bool hinted;
+    int l1;           // hintL1 of the device-side check, 0: no hint
+    double stepMax;
+};
+static BcsHint bcs_hint_state(dpe_bcs *h)
+{
+    if ((h->devHint & 1) && __atomic_load_n(h->hintViol_h, __ATOMIC_RELAXED)) h->devHint &= ~1;
+    const bool hinted = (h->devHint & 1) && h->sh.chipOK && h->sh.chipAllowed;
+    const double nomStep = dpe::kFCA / h->cfg.samplingFrequency;
+    return {hinted, hinted ? (int)(1.0 / nomStep) : 0, nomStep * (1.0 + 1e-5)};
+}
+
+// What this Update knows of the channel values (BcsChanFacts).  The host form has them in the staging block.  The device-parameter
+// form has them only on the device: under the hint nominal values stand in and nothing is read back (the host does not wait for the
+// stream); without it, at sampling rates where the chip kernels exist at all (>= 16 samples per chip), the block bcs_prep_kernel has
+// just derived is read back -- <= 3 KB and one stream wait per window, against a 4-5 x slower stage 1; at lower rates nothing is
+// fetched and nothing the host decides depends on the values.
+static int bcs_channel_facts(dpe_bcs *h, bool dev, bool hinted, int n, hipStream_t stream, dpe::BcsChanFacts &facts)
+{
+    using namespace dpe;
+    if (dev && hinted) {
+        const double fs = h->cfg.samplingFrequency;
+        for (int i = 0; i < n; ++i) {
             BcsChanDev &d = h->chan_h[i];
             d = BcsChanDev{};
             d.fc = kFCA; d.fi = 0.0;
@@ -1463,376 +1389,306 @@ static int bcs_update_impl(dpe_bcs *h, const int16_t *samples_dev, int64_t windo
             d.invStep = fs / kFCA;
             d.hasFlip = 0;
         }
-    } else if (chip && dev) {
-        DPE_CHECK_HIP(hipMemcpyAsync(h->chan_h, h->chan_d, sizeof(BcsChanDev) * nWindows * nChan, hipMemcpyDeviceToHost, stream));
+    } else if (dev) {
+        DPE_CHECK_HIP(hipMemcpyAsync(h->chan_h, h->chan_d, sizeof(BcsChanDev) * n, hipMemcpyDeviceToHost, stream));
         DPE_CHECK_HIP(hipStreamSynchronize(stream));
     }
-    for (int i = 0; chip && i < nWindows * nChan; ++i)
-        if (6.283185307179586 * std::fabs(h->chan_h[i].fi) > 0.25 * h->chan_h[i].fc) chip = false;
-    // second form of the chip kernel (dpe_bcs_chip2.h): every chip 16 .. 25 samples long, and the nav-bit boundary
-    // (BCS_NavBitBoundary :247-253) on a chip boundary of the replica (:347-349) -- it is, unless fp64 rounding separates them
-    bool chip2 = chip && h->chip2Allowed;
-    double stepMax = 0.0;
-    int c2L1 = 0;
-    for (int i = 0; chip2 && i < nWindows * nChan; ++i) {
-        const BcsChanDev &d = h->chan_h[i];
-        const int l1 = (int)d.invStep;   // chips of l1 or l1 + 1 samples; instantiated for every l1 in 16 .. 24 (16.4 .. 25.6 Msps)
-        if (i == 0) c2L1 = l1;
-        if (l1 != c2L1 || l1 < k2MinL1 || l1 > k2MaxL1) chip2 = false;
-        if (d.hasFlip && (int)std::fma((double)d.idxNext, d.codeStep, d.rc) == (int)std::fma((double)(d.idxNext - 1), d.codeStep, d.rc)) chip2 = false;
-        if (d.codeStep > stepMax) stepMax = d.codeStep;
+    facts = bcs_chan_facts(h->chan_h, n, h->sh.chip2Allowed);
+    return 0;
+}
+
+// What every launch of one Update shares.
+struct BcsLaunchArgs {
+    const int16_t *samples;
+    long long winStride;
+    int nWindows, nChan;
+    hipStream_t stream;
+};
+
+// Full-length FFT form (dpe_bcs_fft.h): DC sum, then per chunk of windows the reference's own sequence.
+static int bcs_launch_fft(dpe_bcs *h, const dpe::BcsPlan &plan, const BcsLaunchArgs &a, bool dev)
+{
+    using namespace dpe;
+    const hipStream_t stream = a.stream;
+    const int S = h->cfg.samplesPerWindow, nWindows = a.nWindows, nChan = a.nChan;
+    if (h->coPending) {   // (a pending task of the device-resident channel manager: a kernel of its own in front)
+        hipLaunchKernelGGL(chm_k2_kernel, dim3(1), dim3(256), 0, stream, h->co);
+        h->coPending = false;
     }
+    const long long C = h->sh.C;
+    const int L = h->cfg.lagHalfWidth, B = h->cfg.binHalfWidth, maxK = h->cfg.maxChannels;
+    const int sumBlocks = plan.sumBlocks;
+    h->lastSumBlocks = plan.sumSlotsUsed;
+    h->lastKernel = plan.kernel;
+    if (dev) {}
+    else if (h->graphs.capturing) DPE_CHECK_HIP(hipMemcpyAsync(h->chan_d, h->chan_h, sizeof(BcsChanDev) * nWindows * nChan, hipMemcpyHostToDevice, stream));
+    else upload_params(h->chan_d, h->chanBase_hd + (h->chan_h - h->chanBase_h), sizeof(BcsChanDev) * nWindows * nChan, stream);
+    DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
+    h->prof.begin(0, stream);
+    hipLaunchKernelGGL(bcs_sum_kernel, dim3(sumBlocks, nWindows), dim3(256), 0, stream, a.samples, a.winStride, S, h->sums_d,
+                       (uint4 *)nullptr, (const uint4 *)nullptr, 0);
+    h->prof.end(0, stream);
+    const int chunk = h->fftChunkW;
+    if (!h->havePlans || h->planK != nChan) {   // batched over the channels this host really tracks, not over maxChannels
+        h->havePlans = false;
+        const size_t b3 = (size_t)3 * chunk * nChan, b2 = (size_t)2 * chunk * nChan, b1 = (size_t)chunk * nChan;
+        if (h->planS3.create((size_t)S, b3, false) || h->planS2.create((size_t)S, b2, true) || h->planC.create((size_t)C, b1, false)) {
+            h->planS3.destroy(); h->planS2.destroy(); h->planC.destroy();
+            return -1;   // (the message is rocFFT's, from dpe_fft.h)
+        }
+        h->havePlans = true;
+        h->planK = nChan;
+    }
+    h->prof.begin(1, stream);
+    const size_t plane = (size_t)chunk * nChan * S;
+    const int gxS = S / 256 < 64 ? (S / 256 > 0 ? S / 256 : 1) : 64;
+    const auto exec = [&](FftPlan &p, float2 *ptr) {   // a failed transform closes the profiler slot on its way out
+        if (p.exec(stream, (void *)ptr) == 0) return true;
+        h->prof.end(1, stream);
+        return false;
+    };
+    for (int w0 = 0; w0 < nWindows; w0 += chunk) {
+        const int nw = nWindows - w0 < chunk ? nWindows - w0 : chunk;
+        // the plans transform `chunk` windows of rows; a short last chunk carries stale (finite) rows that nobody reads
+        if (h->sh.useTable)
+            hipLaunchKernelGGL((bcs_fft_prep_code_kernel<true>), dim3(gxS, nChan, nw), dim3(256), 0, stream, a.samples, a.winStride,
+                               S, nChan, chunk, w0, h->chan_d, h->chipTable_d, h->tTable_d, h->fftWork_d);
+        else
+            hipLaunchKernelGGL((bcs_fft_prep_code_kernel<false>), dim3(gxS, nChan, nw), dim3(256), 0, stream, a.samples, a.winStride,
+                               S, nChan, chunk, w0, h->chan_d, h->chipTable_d, h->tTable_d, h->fftWork_d);
+        if (!exec(h->planS3, h->fftWork_d)) return -1;
+        hipLaunchKernelGGL(bcs_fft_mul_kernel, dim3(2048), dim3(256), 0, stream, h->fftWork_d, plane);
+        if (!exec(h->planS2, h->fftWork_d + plane)) return -1;
+        hipLaunchKernelGGL(bcs_fft_extract_code_kernel, dim3(nChan, nw), dim3(256), 0, stream, h->fftWork_d, plane, S, nChan, L, w0, maxK,
+                           h->chan_d, h->codeBank_d, h->info_d);
+        const int gxC = 256;
+        if (h->sh.useTable)
+            hipLaunchKernelGGL((bcs_fft_prep_carr_kernel<true>), dim3(gxC, nChan, nw), dim3(256), 0, stream, a.samples, a.winStride,
+                               S, C, nChan, w0, sumBlocks, h->chan_d, h->sums_d, h->chipTable_d, h->tTable_d, h->info_d, h->fftWork_d);
+        else
+            hipLaunchKernelGGL((bcs_fft_prep_carr_kernel<false>), dim3(gxC, nChan, nw), dim3(256), 0, stream, a.samples, a.winStride,
+                               S, C, nChan, w0, sumBlocks, h->chan_d, h->sums_d, h->chipTable_d, h->tTable_d, h->info_d, h->fftWork_d);
+        if (!exec(h->planC, h->fftWork_d)) return -1;
+        hipLaunchKernelGGL(bcs_fft_extract_carr_kernel, dim3(nChan, nw), dim3(256), 0, stream, h->fftWork_d, C, nChan, B, w0, maxK, h->carrBank_d);
+    }
+    h->prof.end(1, stream);
+    DPE_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// One chunk's stage-1 launch: the form's kernel with the plan's run-time choices as template arguments.
+static void bcs_launch_bank(dpe_bcs *h, const dpe::BcsPlan &p, const dpe::BcsChunk &c, const dpe::BcsParamBlock &pb, const BcsLaunchArgs &a)
+{
+    using namespace dpe;
+    const hipStream_t stream = a.stream;
+    const int S = h->cfg.samplesPerWindow, nWindows = a.nWindows, nChan = a.nChan;
+    const BcsShape &sh = h->sh;
+    const int inl = p.inl ? 1 : 0, vecOK = p.vecOK ? 1 : 0;
+    const dim3 grid(p.nBlk, nChan, nWindows), block(256);
+    if (c.c2) {
+        const int c2Groups = (p.c2nBlk * nWindows + 7) / 8;
+        // one block per (tile, SV), tiles dealt to the XCDs (see the kernel)
+        const dim3 cgrid(p.ride ? p.rideF + ((c2Groups + p.rideGS - 1) / p.rideGS) * (p.rideSB + p.rideGS * 8 * nChan) : c2Groups * 8 * nChan);
+        pick<16, 17, 18, 19, 20, 21, 22, 23, 24>(p.c2L1, [&](auto l1) {
+            pick_bool(p.ride, [&](auto rd) {
+                pick<4, 6>(p.c2NMom, [&](auto nm) {
+                    hipLaunchKernelGGL((bcs_bank_chip2_kernel<nm(), l1(), rd()>), cgrid, dim3(64), 0, stream, pb, inl, a.samples, a.winStride, S,
+                                       nChan, nWindows, p.c2Lt, p.c2nBlk, p.sumBlocks, h->chan_d, h->sums_d, h->chipTable_d, h->chipBits_d, h->part_d,
+                                       h->mom_d, h->rideWord_d, h->rideEpoch, p.rideF, p.rideSB, p.rideGS, h->rideSpin, h->status_d);
+                });
+            });
+        });
+    } else if (p.chip) {
+        const dim3 cgrid(((p.nBlk * nWindows + 7) / 8) * 8 * nChan);   // one block per (tile, SV), tiles dealt to the XCDs (see the kernel)
+        pick<4, 6>(p.chipNMom, [&](auto nm) {
+            hipLaunchKernelGGL((bcs_bank_chip_kernel<nm()>), cgrid, dim3(64), 0, stream, pb, inl, a.samples, a.winStride, S, nChan, nWindows,
+                               sh.nPassChip, p.tpb, p.nBlk, p.sumBlocks, c.lagShift, h->chipDbg, h->chan_d, h->sums_d, h->chipTable_d, h->part_d, h->mom_d);
+        });
+    } else if (p.form == BcsForm::Bank16) {
+        pick<4, 8>(sh.LH, [&](auto lh) {
+            pick<4, 6>(sh.nMom, [&](auto nm) {
+                pick_bool(sh.useTable, [&](auto tb) {
+                    hipLaunchKernelGGL((bcs_bank16_kernel<lh(), nm(), tb()>), dim3(((p.nBlk * nWindows + 7) / 8) * 8 * nChan), block, 0, stream, pb, inl,
+                                       a.samples, a.winStride, S, nChan, nWindows, sh.nSub, p.tpb, p.nBlk, vecOK, p.sumBlocks, h->chan_d, h->sums_d,
+                                       h->chipTable_d, h->tTable_d, h->part_d, h->mom_d);
+                });
+            });
+        });
+    } else if (p.form == BcsForm::Wide) {
+        pick<4, 6>(sh.nMom, [&](auto nm) {
+            pick_bool(sh.useTable, [&](auto tb) {
+                hipLaunchKernelGGL((bcs_bank_wide_kernel<nm(), tb()>), grid, block, 0, stream, pb, inl, a.samples, a.winStride, S, nChan, sh.nSub, p.tpb,
+                                   p.nBlk, vecOK, p.sumBlocks, c.lagShift, h->chan_d, h->sums_d, h->chipTable_d, h->tTable_d, h->part_d, h->mom_d);
+            });
+        });
+    } else {
+        // dense: FUSE (the DC sums ride along) only for LH <= 16, the co-task form only without the time table
+        const auto dense = [&](auto lh, auto nm, auto tb, auto fs, auto co, dim3 g) {
+            hipLaunchKernelGGL((bcs_bank_kernel<lh(), nm(), tb(), fs(), co()>), g, block, 0, stream, pb, inl, a.samples, a.winStride, S, nChan,
+                               sh.nSub, p.tpb, p.nBlk, vecOK, p.sumBlocks, c.lagShift, h->chan_d, h->sums_d, h->chipTable_d, h->tTable_d, h->part_d,
+                               h->mom_d, h->momRep_d, h->sums_d, co() ? h->co : ChmKArgs{});
+        };
+        pick<4, 8, 16, 32>(sh.LH, [&](auto lh) {
+            pick<4, 6>(sh.nMom, [&](auto nm) {
+                pick_bool(sh.useTable, [&](auto tb) {
+                    if constexpr (lh() <= 16) {
+                        if (p.fuse && p.coRide) return dense(lh, nm, std::false_type{}, std::true_type{}, std::true_type{}, dim3(p.nBlk + 1, nChan, nWindows));
+                        if (p.fuse) return dense(lh, nm, tb, std::true_type{}, std::false_type{}, grid);
+                    }
+                    dense(lh, nm, tb, std::false_type{}, std::false_type{}, grid);
+                });
+            });
+        });
+    }
+}
+
+// One chunk's finalize launch.
+static void bcs_launch_finalize(dpe_bcs *h, const dpe::BcsPlan &p, const dpe::BcsChunk &c, const dpe::BcsParamBlock &pb, const BcsLaunchArgs &a)
+{
+    using namespace dpe;
+    const int inl = p.inl ? 1 : 0;
+    const bool fat = p.fatFinalize && c.lagShift == 0;
+    const dim3 fgrid((p.fatFinalize || c.lagShift != 0) ? 1 : 1 + p.nBinBlk, a.nChan, a.nWindows);
+    const int ng = fat ? p.nBinBlk : 1;   // (fat: nBinBlk <= 4)
+    pick<4, 6>(c.nMomUse, [&](auto nm) {
+        pick_bool(p.fuse && c.lagShift == 0, [&](auto fs) {
+            pick<1, 2, 3, 4>(ng <= 1 ? 1 : ng >= 4 ? 4 : ng, [&](auto g) {
+                hipLaunchKernelGGL((bcs_finalize_kernel<nm(), fs(), g()>), fgrid, dim3(256), 0, a.stream, pb, inl, h->cfg.samplesPerWindow, a.nChan,
+                                   p.chip ? c.nBlkUse : h->sh.nSub, c.nBlkUse, h->sh.LH, h->cfg.lagHalfWidth, h->cfg.binHalfWidth,
+                                   p.form == BcsForm::Wide ? 1 : 0, c.lagShift, c.momLenUse, p.chip ? 64 : 65, h->sh.C, h->chan_d, h->part_d, h->mom_d,
+                                   h->codeBank_d, h->carrBank_d, h->info_d, h->cfg.maxChannels, h->momRep_d, h->sums_d, p.sumSlotsUsed);
+            });
+        });
+    });
+}
+
+// Everything a plan enqueues: the riding sums' prelude, the channel manager's task, the DC sums, then per chunk of lags the stage-1
+// kernel and the finalize kernel.  guard: the device status word for the re-run behind a hinted chip launch, else nullptr.
+static int bcs_launch(dpe_bcs *h, const dpe::BcsPlan &p, const BcsLaunchArgs &a, const int *guard)
+{
+    using namespace dpe;
+    const hipStream_t stream = a.stream;
+    const int nWindows = a.nWindows, nChan = a.nChan;
+    const size_t chanBytes = sizeof(BcsChanDev) * nWindows * nChan;
+    const BcsChanDev *staged_hd = h->chanBase_hd + (h->chan_h - h->chanBase_h);   // the staging block's device address
+    BcsParamBlock pb{};
+    pb.guard = guard;
+    if (p.inl) memcpy(pb.c, h->chan_h, chanBytes);
+    // (batches: the DC-sum kernel below carries the parameter upload; a captured graph keeps a copy node)
+    else if (h->graphs.capturing) DPE_CHECK_HIP(hipMemcpyAsync(h->chan_d, h->chan_h, chanBytes, hipMemcpyHostToDevice, stream));
+    if (p.ride) {
+        if (nWindows > h->rideW || p.sumBlocks > h->rideSlots)   // slots this launch reads that the last one did not write: clear the words
+            DPE_CHECK_HIP(hipMemsetAsync(h->rideWord_d, 0, sizeof(unsigned long long) * (size_t)h->cfg.maxWindows * kSumSlots, stream));
+        h->rideW = nWindows;
+        h->rideSlots = p.sumBlocks;
+        h->rideEpoch = h->rideEpoch % 3 + 1;
+        if (p.upInSum) {
+            h->prof.begin(0, stream);
+            // (the same kernel clears the status word's "a block of this launch gave up waiting" bit: a block behind such a block skips its own wait)
+            upload_params(h->chan_d, staged_hd, chanBytes, stream, h->status_d, 4);
+            h->prof.end(0, stream);
+            DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
+        }
+    }
+    if (h->coPending && !p.coRide) hipLaunchKernelGGL(chm_k2_kernel, dim3(1), dim3(256), 0, stream, h->co);
+    h->coPending = false;
+    h->lastSumBlocks = p.sumSlotsUsed;
+    h->lastKernel = p.kernel;
+    if (p.sumLaunch) {
+        h->prof.begin(0, stream);
+        hipLaunchKernelGGL(bcs_sum_kernel, dim3(p.sumBlocks, nWindows), dim3(256), 0, stream, a.samples, a.winStride, h->cfg.samplesPerWindow,
+                           h->sums_d, (uint4 *)h->chan_d, (const uint4 *)staged_hd, p.upInSum ? (int)(chanBytes / 16) : 0);
+        h->prof.end(0, stream);
+        if (p.upInSum) DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));   // the staging block is free again
+    }
+    for (int i = 0; i < p.nChunks; ++i) {
+        h->prof.begin(1, stream);
+        bcs_launch_bank(h, p, p.chunk[i], pb, a);
+        h->prof.end(1, stream);
+        h->prof.begin(2, stream);
+        bcs_launch_finalize(h, p, p.chunk[i], pb, a);
+        h->prof.end(2, stream);
+    }
+    return 0;
+}
+
+// chan_host == nullptr: the channel parameters of this (single-window) call are already in h->chan_d, written by
+// bcs_prep_kernel earlier on `stream` (dpe_bcs_update_dev) -- nothing the host decides may then depend on their values,
+// except the choice of a chip-boundary kernel at high sampling rates (bcs_channel_facts).
+static int bcs_update_impl(dpe_bcs *h, const int16_t *samples_dev, int64_t windowStrideSamples, int32_t nWindows,
+                           int32_t nChan, const dpe_chan_start *chan_host, dpe_stream_t stream_)
+{
+    using namespace dpe;
+    const bool dev = chan_host == nullptr;
+    DPE_REQUIRE(h && samples_dev, "[BatchCorrScores] Update: null argument");
+    DPE_REQUIRE(nWindows >= 1 && nWindows <= h->cfg.maxWindows, "[BatchCorrScores] Update: nWindows %d out of range", nWindows);
+    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrScores] Update: nChan %d out of range", nChan);
+    const int S = h->cfg.samplesPerWindow;
+    DPE_REQUIRE(nWindows == 1 || windowStrideSamples >= S, "[BatchCorrScores] Update: window stride < S");
+    const hipStream_t stream = (hipStream_t)stream_;
+    const BcsLaunchArgs args{samples_dev, (long long)windowStrideSamples, nWindows, nChan, stream};
+    // next staging block of the ring; an Update issued kStaging calls ago may still be copying it (no-op otherwise)
+    h->slot = (h->slot + 1) % dpe_bcs::kStaging;
+    DPE_CHECK_HIP(hipEventSynchronize(h->stagingFree[h->slot]));
+    h->chan_h = h->chanBase_h + (size_t)h->slot * h->cfg.maxWindows * h->cfg.maxChannels;
+    h->lastDev = dev;
+    if (!dev && bcs_stage_host_params(h, chan_host, nWindows * nChan)) return -1;
+    BcsCall call;
+    call.dev = dev;
+    call.graphEnabled = h->graphs.enabled;
+    call.profiler = h->prof.enabled;
+    call.vecOK = ((uintptr_t)samples_dev & 15) == 0 && (windowStrideSamples % 4) == 0;
+    const bool hintedCall = dev && bcs_hint_state(h).hinted;   // the chip kernels on the caller's promise: the guarded re-run follows
+    BcsChanFacts facts;
+    if (bcs_wants_chip(h->sh, false) && bcs_channel_facts(h, dev, hintedCall, nWindows * nChan, stream, facts)) return -1;
     h->lastW = nWindows;
     h->lastK = nChan;
-    if (h->fftMode) {
-        if (h->coPending) {   // (a pending task of the device-resident channel manager: a kernel of its own in front)
-            hipLaunchKernelGGL(chm_k2_kernel, dim3(1), dim3(256), 0, stream, h->co);
-            h->coPending = false;
-        }
-        // ---- full-length FFT form (dpe_bcs_fft.h): DC sum, then per chunk of windows the reference's own sequence
-        const long long C = h->C;
-        const int L = h->cfg.lagHalfWidth, B = h->cfg.binHalfWidth, maxK = h->cfg.maxChannels;
-        const int sumBlocks = sum_blocks(S, nWindows);
-        h->lastSumBlocks = sumBlocks;
-        h->lastKernel = "rocfft full-lag path (bcs_fft_*_kernel)";
-        if (dev) {}
-        else if (h->graphs.capturing) DPE_CHECK_HIP(hipMemcpyAsync(h->chan_d, h->chan_h, sizeof(BcsChanDev) * nWindows * nChan, hipMemcpyHostToDevice, stream));
-        else upload_params(h->chan_d, h->chanBase_hd + (h->chan_h - h->chanBase_h), sizeof(BcsChanDev) * nWindows * nChan, stream);
-        DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
-        h->prof.begin(0, stream);
-        hipLaunchKernelGGL(bcs_sum_kernel, dim3(sumBlocks, nWindows), dim3(256), 0, stream, samples_dev, (long long)windowStrideSamples, S, h->sums_d,
-                           (uint4 *)nullptr, (const uint4 *)nullptr, 0);
-        h->prof.end(0, stream);
-        const int chunk = h->fftChunkW;
-        if (!h->havePlans || h->planK != nChan) {   // batched over the channels this host really tracks, not over maxChannels
-            h->havePlans = false;
-            const size_t b3 = (size_t)3 * chunk * nChan, b2 = (size_t)2 * chunk * nChan, b1 = (size_t)chunk * nChan;
-            if (h->planS3.create((size_t)S, b3, false) || h->planS2.create((size_t)S, b2, true) || h->planC.create((size_t)C, b1, false)) {
-                h->planS3.destroy(); h->planS2.destroy(); h->planC.destroy();
-                return -1;   // (the message is rocFFT's, from dpe_fft.h)
-            }
-            h->havePlans = true;
-            h->planK = nChan;
-        }
-        h->prof.begin(1, stream);
-        const size_t plane = (size_t)chunk * nChan * S;
-        const int gxS = S / 256 < 64 ? (S / 256 > 0 ? S / 256 : 1) : 64;
-#define DPE_FFT_EXEC(plan, ptr)                  \
-    if ((plan).exec(stream, (void *)(ptr))) {    \
-        h->prof.end(1, stream);                  \
-        return -1;                               \
+    if (h->sh.fftMode) {
+        call.capturing = h->graphs.capturing;
+        call.coPending = h->coPending;
+        return bcs_launch_fft(h, bcs_plan(h->sh, facts, nWindows, nChan, call), args, dev);
     }
-        for (int w0 = 0; w0 < nWindows; w0 += chunk) {
-            const int nw = nWindows - w0 < chunk ? nWindows - w0 : chunk;
-            // the plans transform `chunk` windows of rows; a short last chunk carries stale (finite) rows that nobody reads
-            if (h->useTable)
-                hipLaunchKernelGGL((bcs_fft_prep_code_kernel<true>), dim3(gxS, nChan, nw), dim3(256), 0, stream, samples_dev, (long long)windowStrideSamples,
-                                   S, nChan, chunk, w0, h->chan_d, h->chipTable_d, h->tTable_d, h->fftWork_d);
-            else
-                hipLaunchKernelGGL((bcs_fft_prep_code_kernel<false>), dim3(gxS, nChan, nw), dim3(256), 0, stream, samples_dev, (long long)windowStrideSamples,
-                                   S, nChan, chunk, w0, h->chan_d, h->chipTable_d, h->tTable_d, h->fftWork_d);
-            DPE_FFT_EXEC(h->planS3, h->fftWork_d);
-            hipLaunchKernelGGL(bcs_fft_mul_kernel, dim3(2048), dim3(256), 0, stream, h->fftWork_d, plane);
-            DPE_FFT_EXEC(h->planS2, h->fftWork_d + plane);
-            hipLaunchKernelGGL(bcs_fft_extract_code_kernel, dim3(nChan, nw), dim3(256), 0, stream, h->fftWork_d, plane, S, nChan, L, w0, maxK,
-                               h->chan_d, h->codeBank_d, h->info_d);
-            const int gxC = 256;
-            if (h->useTable)
-                hipLaunchKernelGGL((bcs_fft_prep_carr_kernel<true>), dim3(gxC, nChan, nw), dim3(256), 0, stream, samples_dev, (long long)windowStrideSamples,
-                                   S, C, nChan, w0, sumBlocks, h->chan_d, h->sums_d, h->chipTable_d, h->tTable_d, h->info_d, h->fftWork_d);
-            else
-                hipLaunchKernelGGL((bcs_fft_prep_carr_kernel<false>), dim3(gxC, nChan, nw), dim3(256), 0, stream, samples_dev, (long long)windowStrideSamples,
-                                   S, C, nChan, w0, sumBlocks, h->chan_d, h->sums_d, h->chipTable_d, h->tTable_d, h->info_d, h->fftWork_d);
-            DPE_FFT_EXEC(h->planC, h->fftWork_d);
-            hipLaunchKernelGGL(bcs_fft_extract_carr_kernel, dim3(nChan, nw), dim3(256), 0, stream, h->fftWork_d, C, nChan, B, w0, maxK, h->carrBank_d);
-        }
-#undef DPE_FFT_EXEC
-        h->prof.end(1, stream);
-        DPE_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
-    // the per-kernel event timing and the graph replay exclude each other
-    const bool useGraph = h->graphs.enabled && !h->prof.enabled && !dev;
     GraphCache::Guard graphGuard{h->graphs, stream};
-    int sumBlocks = sum_blocks(S, nWindows);
-    if (useGraph) {
+    if (bcs_use_graph(call)) {
         const int rc = h->graphs.begin({samples_dev, nullptr, (long long)windowStrideSamples, nWindows, nChan,
-                                        (h->wideAllowed ? 1 : 0) | (h->bank16Allowed ? 2 : 0) | (h->slot << 8), stream}, stream);
+                                        (h->sh.wideAllowed ? 1 : 0) | (h->sh.bank16Allowed ? 2 : 0) | (h->slot << 8), stream}, stream);
         DPE_REQUIRE(rc >= 0, "[BatchCorrScores] Update: hipGraph capture/replay failed");
         if (rc == 1) {
             DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));   // the replayed graph reads this slot
             return 0;
         }
     }
-    // few channels (the per-window call of a running receiver): parameters travel as kernel arguments of
-    // the bank / finalize kernels; batches go through one H2D copy from the pinned staging block.  A
-    // captured graph would freeze by-value arguments, so the graph path always copies.
-    const int inl = (!dev && !h->graphs.capturing && nWindows * nChan <= DPE_MAX_CHAN) ? 1 : 0;
-    BcsParamBlock pb{};
-    pb.guard = rerun ? h->status_d : nullptr;
-    if (inl) memcpy(pb.c, h->chan_h, sizeof(BcsChanDev) * nWindows * nChan);
-    // (batches: the DC-sum kernel below carries the parameter upload; a captured graph keeps a copy node)
-    else if (h->graphs.capturing)
-        DPE_CHECK_HIP(hipMemcpyAsync(h->chan_d, h->chan_h, sizeof(BcsChanDev) * nWindows * nChan, hipMemcpyHostToDevice, stream));
-    const bool upInSum = !dev && !inl && !h->graphs.capturing;
-    const int vecOK = (((uintptr_t)samples_dev & 15) == 0 && (windowStrideSamples % 4) == 0) ? 1 : 0;
-    // |lag| <= 32 windows: boundary-difference kernel when a sub-tile holds few chip boundaries
-    // (~128 codeStep per lag step against 4 x 65 dense FMAs per lane), else a dense kernel
-    const bool wide = !chip && h->LH == 32 && h->wideAllowed && (kFCA / fs) * 128.0 < 40.0;
-    // narrow lag windows in batches: the 16-samples-per-lane kernel (tiles of 16 sub-tiles) once the batch
-    // offers >= 2048 of its tiles; fewer (a single window in particular) keep the short 4-sub-tile tiles
-    const int nTiles16 = (h->nSub + 15) / 16;
-    const bool use16 = !wide && h->LH <= 8 && h->bank16Allowed && (long long)nTiles16 * nChan * nWindows >= 2048;
-    const int nTiles = use16 ? nTiles16 : (h->nSub + 3) / 4;
-    int tpb;   // tiles per block: amortise the end-of-block lag reduction while keeping >= ~4096 blocks in flight
-    if (use16) {
-        // the choice that minimises rounds x (tiles + fixed cost): a block's start-up (chip table into LDS, parameters, the
-        // end-of-side lag reductions) measures ~0.4 tile times, and a launch whose blocks are all resident in two rounds beats
-        // eight rounds of short ones (config R: 4 tiles per block 0.237 ms, all 13 in one block 0.181 ms)
-        const int least = (nTiles + h->nBlk - 1) / h->nBlk;   // the partial buffer holds h->nBlk blocks per (window, SV)
-        double best = -1.0;
-        tpb = least < 1 ? 1 : least;
-        for (int c = tpb; c <= nTiles; ++c) {
-            const long long blocks = (long long)((nTiles + c - 1) / c) * nChan * nWindows;
-            const double cost = (double)((blocks + h->resident16 - 1) / h->resident16) * ((double)c + 0.4);
-            if (best < 0.0 || cost < best) { best = cost; tpb = c; }
-        }
-        if (h->tpb16Force >= least && h->tpb16Force >= 1) tpb = h->tpb16Force;
-    } else {
-        tpb = (int)(((long long)nTiles * nChan * nWindows) / 4096);
-        if (tpb < h->tilesPerBlock) tpb = h->tilesPerBlock;
-        if (tpb > 16) tpb = 16;
-    }
-    // chip-boundary kernel: one wave per block walks tpb passes of one (window, SV)
-    int chipNMom = 6;
-    if (chip) {
-        // passes per wave: the choice that leaves the smallest tail -- ceil(waves / resident waves) rounds of tpb passes each
-        const int least = (h->nPassChip + h->nBlkAlloc - 1) / h->nBlkAlloc;
-        long long best = -1;
-        tpb = least;
-        for (int c = least; c <= h->chipTpbMax; ++c) {
-            const long long waves = (long long)((h->nPassChip + c - 1) / c) * nChan * nWindows;
-            // + the finalize kernel's share: its time grows by ~0.06 pass-rounds per partial block (measured, config H)
-            const long long cost = 100 * ((waves + h->chipResident - 1) / h->chipResident) * c + 6 * ((h->nPassChip + c - 1) / c);
-            if (best < 0 || cost < best) { best = cost; tpb = c; }
-        }
-        if (h->chipTpbForce >= least && h->chipTpbForce <= h->chipTpbMax) tpb = h->chipTpbForce;
-        const double thc = 6.283185307179586 * h->cfg.binHalfWidth / (double)h->C * 0.5 * ((double)tpb * kPass - 1.0);
-        chipNMom = (std::pow(thc, 4) / 24.0 < 1e-7) ? 4 : 6;
-    }
-    const int nBlk = chip ? (h->nPassChip + tpb - 1) / tpb : (nTiles + tpb - 1) / tpb;
-    // second form: a tile = the chips that start inside a nominal range of Lt samples, at most P passes of k2Own chips
-    int c2Lt = 0, c2nBlk = 0, c2NMom = 6;
-    if (chip2) {
-        const double thetaB = 6.283185307179586 * h->cfg.binHalfWidth / (double)h->C;
-        const double halfMax = std::pow(2e-7 * 720.0, 1.0 / 6.0) / thetaB;   // 6-moment Taylor radius (samples)
-        long long best = -1;
-        for (int P = 1; P <= 64; ++P) {
-            const int Lt = (int)std::floor((double)(k2Own * P - 2) / stepMax);
-            if (Lt < 64 || 0.5 * Lt + 26.0 > halfMax) continue;
-            const int nb = (S + Lt - 1) / Lt;
-            if (nb > h->nBlkAlloc) continue;
-            if (h->chip2PForce > 0 && P != h->chip2PForce) continue;
-            const long long waves = (long long)nb * nChan * nWindows;
-            const long long cost = 100 * ((waves + h->chip2Resident - 1) / h->chip2Resident) * P + 6 * nb;
-            if (best < 0 || cost < best) { best = cost; c2Lt = Lt; c2nBlk = nb; }
-        }
-        if (c2Lt == 0) chip2 = false;
-        else {
-            const double thc = thetaB * (0.5 * c2Lt + 26.0);
-            c2NMom = (std::pow(thc, 4) / 24.0 < 1e-7) ? 4 : 6;
-        }
-    }
-    h->lastKernel = chip2 ? "bcs_bank_chip2_kernel" : chip ? "bcs_bank_chip_kernel" : use16 ? "bcs_bank16_kernel" : wide ? "bcs_bank_wide_kernel" : "bcs_bank_kernel";
-    const dim3 grid(nBlk, nChan, nWindows), block(256);
-    // single windows (<= 37 (window, channel) pairs) with a dense stage-1 kernel: no separate DC-sum launch, the
-    // sums ride along in the bank kernel (FUSE) and the finalize kernel applies the mean
-    const bool fuse = nWindows * nChan <= DPE_MAX_CHAN && !use16 && !wide && !chip && h->LH <= 16 && h->cfg.lagHalfWidth <= 32 && h->fuseAllowed;
-    // chip2 batches: the DC sums ride in the chip2 launch (sum blocks interleaved ahead of the correlator blocks, dpe_bcs_chip2.h);
-    // the parameter upload keeps a small kernel of its own (riding as well, every correlator block had to poll for it first thing:
-    // 0.7035 against 0.696 ms per step)
-    bool ride = chip2 && !dev && !h->graphs.capturing && vecOK && h->rideAllowed && nWindows >= h->rideMinW;
-    int rideF = 0, rideSB = 0, rideGS = 1;
-    if (ride) {   // one sum slot per correlator tile (the sum block then shares its tile's XCD): <= 64 slots, 31-bit sum fields
-        if (c2nBlk > kSumSlots || c2Lt + 8 >= 32768) ride = false;
-        else sumBlocks = c2nBlk;
-    }
-    if (ride) {
-        const long long totalSum = (long long)nWindows * sumBlocks, NG = ((long long)c2nBlk * nWindows + 7) / 8;
-        const int lookAhead = h->rideLA;   // windows between a sum block and the correlator blocks of its tile
-        rideF = (int)(((long long)lookAhead * sumBlocks + 7) / 8 * 8);
-        const long long groupsAvail = NG - ((long long)lookAhead * c2nBlk + 7) / 8 - 1;
-        if (rideF >= totalSum || groupsAvail < 1) rideF = (int)((totalSum + 7) / 8 * 8);
-        else {
-            // sum blocks per group of 8 K correlator blocks at a STEADY lead (a lead that grows puts the samples a sum block fetched
-            // out of its XCD's L2 before the correlator blocks of the same tile read them): whole eights per group, or one eight
-            // every rideGS groups; what does not fit behind the look-ahead joins the blocks in front
-            const long long rest = totalSum - rideF;
-            if (rest >= 8 * groupsAvail) { rideSB = (int)(rest / (8 * groupsAvail)) * 8; rideGS = 1; }
-            else { rideSB = 8; rideGS = (int)((8 * groupsAvail) / rest); }
-            const long long cap = (long long)rideSB * (groupsAvail / rideGS);
-            if (totalSum - cap > rideF) rideF = (int)((totalSum - cap + 7) / 8 * 8);
-        }
-        if (nWindows > h->rideW || sumBlocks > h->rideSlots)   // slots this launch reads that the last one did not write: clear the words
-            DPE_CHECK_HIP(hipMemsetAsync(h->rideWord_d, 0, sizeof(unsigned long long) * (size_t)h->cfg.maxWindows * kSumSlots, stream));
-        h->rideW = nWindows;
-        h->rideSlots = sumBlocks;
-        h->rideEpoch = h->rideEpoch % 3 + 1;
-        if (upInSum) {
-            h->prof.begin(0, stream);
-            // (the same kernel clears the status word's "a block of this launch gave up waiting" bit: a block behind such a block skips its own wait)
-            upload_params(h->chan_d, h->chanBase_hd + (h->chan_h - h->chanBase_h), sizeof(BcsChanDev) * nWindows * nChan, stream, h->status_d, 4);
-            h->prof.end(0, stream);
-            DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
-        }
-    }
-    const int sumSlotsUsed = fuse ? nBlk : sumBlocks;
-    // a pending task of the device-resident channel manager: an extra block of the FUSE form's launch, a kernel of its own in
-    // front of every other form
-    const bool coRide = h->coPending && fuse && !h->useTable && !h->graphs.capturing;
-    if (h->coPending && !coRide) hipLaunchKernelGGL(chm_k2_kernel, dim3(1), dim3(256), 0, stream, h->co);
-    h->coPending = false;
-    h->lastSumBlocks = sumSlotsUsed;
-    if (!fuse && !ride && !rerun) {   // (a re-run uses the sums of the launch it follows: same window, same slots)
-        h->prof.begin(0, stream);
-        hipLaunchKernelGGL(bcs_sum_kernel, dim3(sumBlocks, nWindows), dim3(256), 0, stream, samples_dev,
-                           (long long)windowStrideSamples, S, h->sums_d, (uint4 *)h->chan_d,
-                           (const uint4 *)(h->chanBase_hd + (h->chan_h - h->chanBase_h)),
-                           upInSum ? (int)(sizeof(BcsChanDev) * nWindows * nChan / 16) : 0);
-        h->prof.end(0, stream);
-        if (upInSum) DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));   // the staging block is free again
-    }
-#define DPE_LAUNCH_BANK5(LHV, NM, TB, FS, COV, GRID)                                                                     \
-    hipLaunchKernelGGL((bcs_bank_kernel<LHV, NM, TB, FS, COV>), GRID, block, 0, stream, pb, inl, samples_dev, (long long)windowStrideSamples, \
-                       S, nChan, h->nSub, tpb, nBlk, vecOK, sumBlocks, lagShift, h->chan_d, h->sums_d, h->chipTable_d, \
-                       h->tTable_d, h->part_d, h->mom_d, h->momRep_d, h->sums_d, COV ? h->co : ChmKArgs{})
-#define DPE_LAUNCH_BANK3(LHV, NM, TB)                                                                                    \
-    do {                                                                                                                \
-        if (fuse && LHV <= 16) {                                                                                        \
-            if (coRide) DPE_LAUNCH_BANK5(LHV <= 16 ? LHV : 16, NM, false, true, true, dim3(nBlk + 1, nChan, nWindows)); \
-            else DPE_LAUNCH_BANK5(LHV <= 16 ? LHV : 16, NM, TB, true, false, grid);                                     \
-        } else DPE_LAUNCH_BANK5(LHV, NM, TB, false, false, grid);                                                       \
-    } while (0)
-#define DPE_LAUNCH_BANK2(LHV, NM)                           \
-    do {                                                    \
-        if (h->useTable) DPE_LAUNCH_BANK3(LHV, NM, true);   \
-        else DPE_LAUNCH_BANK3(LHV, NM, false);              \
-    } while (0)
-    // Lag windows wider than +-32: further chunks of 65 lags, centred 65 samples apart -- the same kernels run
-    // against the replica delayed by lagShift samples (centre chunk first: it makes the replica choice and the
-    // Doppler bank).  One chunk when L <= 32.
-    // (the chip kernel's lanes cover lagShift - 32 .. lagShift + 31: chunks of 64 lags, 64 apart)
-    const int chunkLags = chip ? 64 : 65;
-    const int nSideChunks = chip ? (h->cfg.lagHalfWidth > 31 ? (h->cfg.lagHalfWidth - 31 + 63) / 64 : 0)
-                                 : (h->cfg.lagHalfWidth > 32 ? (h->cfg.lagHalfWidth - 32 + 64) / 65 : 0);
-    for (int chunk = 0; chunk <= 2 * nSideChunks; ++chunk) {
-    const int lagShift = chunk == 0 ? 0 : ((chunk + 1) / 2) * chunkLags * ((chunk & 1) ? 1 : -1);
-    const bool c2 = chip2 && lagShift == 0;   // the second form produces the centre chunk; side chunks of a wider window use the first
-    const int nMomUse = c2 ? c2NMom : chip ? chipNMom : h->nMom;
-    const int nBlkUse = c2 ? c2nBlk : nBlk;
-    const int momLenUse = c2 ? c2Lt : chip ? tpb * kPass : kSub;
-    h->prof.begin(1, stream);
-#define DPE_LAUNCH_BANK(LHV)            \
-    do {                                \
-        if (h->nMom == 4) DPE_LAUNCH_BANK2(LHV, 4); \
-        else DPE_LAUNCH_BANK2(LHV, 6);  \
-    } while (0)
-    if (c2) {
-        const int c2Groups = (c2nBlk * nWindows + 7) / 8;
-        const dim3 cgrid(ride ? rideF + ((c2Groups + rideGS - 1) / rideGS) * (rideSB + rideGS * 8 * nChan) : c2Groups * 8 * nChan);   // one block per (tile, SV), tiles dealt to the XCDs (see the kernel)
-#define DPE_LAUNCH_CHIP2(NM, LV, RD)                                                                                           \
-    hipLaunchKernelGGL((bcs_bank_chip2_kernel<NM, LV, RD>), cgrid, dim3(64), 0, stream, pb, inl, samples_dev, (long long)windowStrideSamples, S, \
-                       nChan, nWindows, c2Lt, c2nBlk, sumBlocks, h->chan_d, h->sums_d, h->chipTable_d, h->chipBits_d, h->part_d, h->mom_d,      \
-                       h->rideWord_d, h->rideEpoch, rideF, rideSB, rideGS, h->rideSpin, h->status_d)
-#define DPE_LAUNCH_CHIP2_L(LV)                                                                        \
-    case LV:                                                                                          \
-        if (ride) { if (c2NMom == 4) DPE_LAUNCH_CHIP2(4, LV, true); else DPE_LAUNCH_CHIP2(6, LV, true); }   \
-        else { if (c2NMom == 4) DPE_LAUNCH_CHIP2(4, LV, false); else DPE_LAUNCH_CHIP2(6, LV, false); }      \
-        break
-        switch (c2L1) {
-            DPE_LAUNCH_CHIP2_L(16); DPE_LAUNCH_CHIP2_L(17); DPE_LAUNCH_CHIP2_L(18); DPE_LAUNCH_CHIP2_L(19); DPE_LAUNCH_CHIP2_L(20);
-            DPE_LAUNCH_CHIP2_L(21); DPE_LAUNCH_CHIP2_L(22); DPE_LAUNCH_CHIP2_L(23); DPE_LAUNCH_CHIP2_L(24);
-        }
-#undef DPE_LAUNCH_CHIP2_L
-#undef DPE_LAUNCH_CHIP2
-    } else if (chip) {
-        const dim3 cgrid(((nBlk * nWindows + 7) / 8) * 8 * nChan);   // one block per (tile, SV), tiles dealt to the XCDs (see the kernel)
-#define DPE_LAUNCH_CHIP(NM)                                                                                                    \
-    hipLaunchKernelGGL((bcs_bank_chip_kernel<NM>), cgrid, dim3(64), 0, stream, pb, inl, samples_dev, (long long)windowStrideSamples, S, \
-                       nChan, nWindows, h->nPassChip, tpb, nBlk, sumBlocks, lagShift, h->chipDbg, h->chan_d, h->sums_d, h->chipTable_d, h->part_d, h->mom_d)
-        if (chipNMom == 4) DPE_LAUNCH_CHIP(4); else DPE_LAUNCH_CHIP(6);
-#undef DPE_LAUNCH_CHIP
-    } else if (use16) {
-#define DPE_LAUNCH_B16(LHV, NM, TB)                                                                                    \
-    hipLaunchKernelGGL((bcs_bank16_kernel<LHV, NM, TB>), dim3(((nBlk * nWindows + 7) / 8) * 8 * nChan), block, 0, stream, pb, inl, samples_dev, \
-                       (long long)windowStrideSamples, S, nChan, nWindows, h->nSub, tpb, nBlk, vecOK, sumBlocks, h->chan_d, h->sums_d,         \
-                       h->chipTable_d, h->tTable_d, h->part_d, h->mom_d)
-#define DPE_LAUNCH_B16_2(LHV)                                                                           \
-    do {                                                                                                \
-        if (h->nMom == 4) { if (h->useTable) DPE_LAUNCH_B16(LHV, 4, true); else DPE_LAUNCH_B16(LHV, 4, false); } \
-        else { if (h->useTable) DPE_LAUNCH_B16(LHV, 6, true); else DPE_LAUNCH_B16(LHV, 6, false); }         \
-    } while (0)
-        if (h->LH == 4) DPE_LAUNCH_B16_2(4); else DPE_LAUNCH_B16_2(8);
-#undef DPE_LAUNCH_B16_2
-#undef DPE_LAUNCH_B16
-    } else if (wide) {
-#define DPE_LAUNCH_WIDE(NM, TB)                                                                                    \
-    hipLaunchKernelGGL((bcs_bank_wide_kernel<NM, TB>), grid, block, 0, stream, pb, inl, samples_dev, (long long)windowStrideSamples, \
-                       S, nChan, h->nSub, tpb, nBlk, vecOK, sumBlocks, lagShift, h->chan_d, h->sums_d, h->chipTable_d, h->tTable_d, h->part_d, h->mom_d)
-        if (h->nMom == 4) { if (h->useTable) DPE_LAUNCH_WIDE(4, true); else DPE_LAUNCH_WIDE(4, false); }
-        else { if (h->useTable) DPE_LAUNCH_WIDE(6, true); else DPE_LAUNCH_WIDE(6, false); }
-#undef DPE_LAUNCH_WIDE
-    } else
-    switch (h->LH) {
-        case 4: DPE_LAUNCH_BANK(4); break;
-        case 8: DPE_LAUNCH_BANK(8); break;
-        case 16: DPE_LAUNCH_BANK(16); break;
-        default: DPE_LAUNCH_BANK(32); break;
-    }
-#undef DPE_LAUNCH_BANK
-#undef DPE_LAUNCH_BANK2
-#undef DPE_LAUNCH_BANK3
-#undef DPE_LAUNCH_BANK5
-    h->prof.end(1, stream);
-    h->prof.begin(2, stream);
-    const int nBinBlk = (2 * h->cfg.binHalfWidth + 1 + 15) / 16;
-    // batches: one fat block per (window, SV); few windows: 1 + nBinBlk short blocks (see the kernel);
-    // side chunks of a wide lag window: one block per (window, SV), code-bank entries only
-    // (crossover measured in round 2: 96 / 128 (window, SV) pairs are faster split, 192 / 256 / 384 fat -- H at 32 windows 0.0205 -> 0.0113 ms)
-    bool fatFinalize = nBinBlk <= 4 && (long long)nChan * nWindows >= 192;
-    if (h->fatForce >= 0) fatFinalize = nBinBlk <= 4 && h->fatForce == 1;   // (experiment builds)
-    const dim3 fgrid((fatFinalize || lagShift != 0) ? 1 : 1 + nBinBlk, nChan, nWindows);
-#define DPE_LAUNCH_FIN(NM, FS)                                                                                          \
-    do {                                                                                                                \
-        const int ng = (fatFinalize && lagShift == 0) ? nBinBlk : 1;                                                   \
-        if (ng <= 1) DPE_LAUNCH_FIN_G(NM, FS, 1); else if (ng == 2) DPE_LAUNCH_FIN_G(NM, FS, 2);                        \
-        else if (ng == 3) DPE_LAUNCH_FIN_G(NM, FS, 3); else DPE_LAUNCH_FIN_G(NM, FS, 4);                                \
-    } while (0)
-#define DPE_LAUNCH_FIN_G(NM, FS, NGV)                                                                                   \
-    hipLaunchKernelGGL((bcs_finalize_kernel<NM, FS, NGV>), fgrid, dim3(256), 0, stream, pb, inl, S, nChan, chip ? nBlkUse : h->nSub, nBlkUse, h->LH, \
-                       h->cfg.lagHalfWidth, h->cfg.binHalfWidth, wide ? 1 : 0, lagShift, momLenUse, chip ? 64 : 65, h->C, h->chan_d, h->part_d, h->mom_d,  \
-                       h->codeBank_d, h->carrBank_d, h->info_d, h->cfg.maxChannels, h->momRep_d, h->sums_d, sumSlotsUsed)
-    const bool fuseFin = fuse && lagShift == 0;
-    if (nMomUse == 4) { if (fuseFin) DPE_LAUNCH_FIN(4, true); else DPE_LAUNCH_FIN(4, false); }
-    else { if (fuseFin) DPE_LAUNCH_FIN(6, true); else DPE_LAUNCH_FIN(6, false); }
-#undef DPE_LAUNCH_FIN
-#undef DPE_LAUNCH_FIN_G
-    h->prof.end(2, stream);
-    }   // chunk
+    call.capturing = h->graphs.capturing;
+    call.coPending = h->coPending;
+    const BcsPlan plan = bcs_plan(h->sh, facts, nWindows, nChan, call);
+    if (bcs_launch(h, plan, args, nullptr)) return -1;
     const bool captured = h->graphs.capturing;
     DPE_REQUIRE(h->graphs.end(stream) == 0, "[BatchCorrScores] Update: hipGraph instantiate/launch failed");
     if (captured) DPE_CHECK_HIP(hipEventRecord(h->stagingFree[h->slot], stream));
     DPE_CHECK_HIP(hipGetLastError());
-    if (hintedCall && (chip2 || chip)) {
+    if (hintedCall && plan.chip) {
         // the chip kernels ran on a promise nobody has checked yet on the host: the general kernels follow, guarded by the device
-        // status word -- two launches whose blocks exit at once in all but the flagged windows (~1e-10 of them with honest callers)
-        const char *ran = h->lastKernel;
-        const int rc = bcs_update_impl(h, samples_dev, windowStrideSamples, nWindows, nChan, nullptr, stream_, 1);
-        h->lastKernel = ran;
-        return rc;
+        // status word -- two launches whose blocks exit at once in all but the flagged windows (~1e-10 of them with honest callers).
+        // The re-run's plan never takes a chip form, so it reads no channel value on the host.
+        call.rerun = true;
+        call.coPending = false;
+        const BcsPlan again = bcs_plan(h->sh, BcsChanFacts{}, nWindows, nChan, call);
+        DPE_REQUIRE(again.form == BcsForm::Dense || again.form == BcsForm::Wide, "[BatchCorrScores] Update: the guarded re-run chose %s", again.kernel);
+        if (bcs_launch(h, again, args, h->status_d)) return -1;
+        h->lastKernel = plan.kernel;
+        DPE_CHECK_HIP(hipGetLastError());
     }
     return 0;
 }
+
+static int bcs_check_dev_call(dpe_bcs *h, const int16_t *samples_dev, int32_t nChan)
+{
+    DPE_REQUIRE(h && samples_dev, "[BatchCorrScores] Update: null argument");
+    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrScores] Update: nChan %d out of range", nChan);
+    return 0;
+}
+
+extern "C" {
 
 int dpe_bcs_update(dpe_bcs *h, const int16_t *samples_dev, int64_t windowStrideSamples, int32_t nWindows,
                    int32_t nChan, const dpe_chan_start *chan_host, dpe_stream_t stream)
@@ -1844,17 +1700,15 @@ int dpe_bcs_update(dpe_bcs *h, const int16_t *samples_dev, int64_t windowStrideS
 int dpe_bcs_update_dev(dpe_bcs *h, const int16_t *samples_dev, int32_t nChan, const dpe_bcs_ports_dev *ports, dpe_stream_t stream)
 {
     using namespace dpe;
-    DPE_REQUIRE(h && samples_dev && ports, "[BatchCorrScores] Update: null argument");
-    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrScores] Update: nChan %d out of range", nChan);
+    DPE_REQUIRE(ports, "[BatchCorrScores] Update: null argument");
+    if (bcs_check_dev_call(h, samples_dev, nChan)) return -1;
     DPE_REQUIRE(ports->codePhaseStart && ports->carrierPhaseStart && ports->codeFrequency && ports->carrierFrequency &&
                 ports->cpElapsedStart && ports->cpReference && ports->validPRNs, "[BatchCorrScores] Update: a device port pointer is null");
     const BcsPortsDev p = {ports->codePhaseStart, ports->carrierPhaseStart, ports->codeFrequency, ports->carrierFrequency,
                            ports->cpElapsedStart, ports->cpReference, ports->validPRNs};
-    if ((h->devHint & 1) && __atomic_load_n(h->hintViol_h, __ATOMIC_RELAXED)) h->devHint &= ~1;   // a broken promise withdraws the hint (see bcs_update_impl)
-    const bool hinted = (h->devHint & 1) && h->chipOK && h->chipAllowed;
-    const double nomStep = kFCA / h->cfg.samplingFrequency;
+    const BcsHint hint = bcs_hint_state(h);
     hipLaunchKernelGGL(bcs_prep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, p, (int)nChan, h->cfg.samplingFrequency,
-                       h->cfg.samplesPerWindow, h->chan_d, h->status_d, hinted ? (int)(1.0 / nomStep) : 0, nomStep * (1.0 + 1e-5), h->hintViol_hd);
+                       h->cfg.samplesPerWindow, h->chan_d, h->status_d, hint.l1, hint.stepMax, h->hintViol_hd);
     return bcs_update_impl(h, samples_dev, h->cfg.samplesPerWindow, 1, nChan, nullptr, stream);
 }
 
@@ -1867,8 +1721,7 @@ int dpe_bcs_set_dev_hint(dpe_bcs *h, int32_t flags)
 
 int dpe_bcs_update_prepared(dpe_bcs *h, const int16_t *samples_dev, int32_t nChan, dpe_stream_t stream)
 {
-    DPE_REQUIRE(h && samples_dev, "[BatchCorrScores] Update: null argument");
-    DPE_REQUIRE(nChan >= 1 && nChan <= h->cfg.maxChannels, "[BatchCorrScores] Update: nChan %d out of range", nChan);
+    if (bcs_check_dev_call(h, samples_dev, nChan)) return -1;
     return bcs_update_impl(h, samples_dev, h->cfg.samplesPerWindow, 1, nChan, nullptr, stream);
 }
 
@@ -1909,10 +1762,9 @@ int dpe_bcs_hook_get(dpe_bcs *h, dpe_bcs_hook *out)
     out->fs = h->cfg.samplingFrequency;
     out->S = h->cfg.samplesPerWindow;
     out->maxChannels = h->cfg.maxChannels;
-    const bool hinted = (h->devHint & 1) && h->chipOK && h->chipAllowed && !__atomic_load_n(h->hintViol_h, __ATOMIC_RELAXED);
-    const double nomStep = dpe::kFCA / h->cfg.samplingFrequency;
-    out->hintL1 = hinted ? (int)(1.0 / nomStep) : 0;
-    out->hintStepMax = nomStep * (1.0 + 1e-5);
+    const BcsHint hint = bcs_hint_state(h);
+    out->hintL1 = hint.l1;
+    out->hintStepMax = hint.stepMax;
     out->hintViol = h->hintViol_hd;
     return 0;
 }
@@ -1928,7 +1780,7 @@ int dpe_bcs_dev_status(dpe_bcs *h, int32_t *status, dpe_stream_t stream)
 int dpe_bcs_set_graph(dpe_bcs *h, int32_t enable)
 {
     DPE_REQUIRE(h, "[BatchCorrScores] set_graph: null handle");
-    DPE_REQUIRE(!(enable && h->fftMode), "[BatchCorrScores] set_graph: the full-length FFT form (this handle's lag / bin windows) is not captured as a hipGraph");
+    DPE_REQUIRE(!(enable && h->sh.fftMode), "[BatchCorrScores] set_graph: the full-length FFT form (this handle's lag / bin windows) is not captured as a hipGraph");
     h->graphs.enabled = enable != 0;
     if (!enable) h->graphs.clear();
     return 0;
@@ -1942,7 +1794,7 @@ int dpe_bcs_outputs(dpe_bcs *h, const float **codeBank_dev, const float **carrBa
     if (carrBank_dev) *carrBank_dev = reinterpret_cast<const float *>(h->carrBank_d);
     if (nLag) *nLag = 2 * h->cfg.lagHalfWidth + 1;
     if (nBin) *nBin = 2 * h->cfg.binHalfWidth + 1;
-    if (numFFTPoints) *numFFTPoints = h->C;
+    if (numFFTPoints) *numFFTPoints = h->sh.C;
     return 0;
 }
 
@@ -2014,9 +1866,9 @@ int dpe_bcs_export_dense(dpe_bcs *h, int32_t window, double *codeScores_dev, dou
                            h->cfg.lagHalfWidth, reinterpret_cast<double2 *>(codeScores_dev));
     }
     if (carrScores_dev) {
-        DPE_CHECK_HIP(hipMemsetAsync(carrScores_dev, 0, sizeof(double2) * (size_t)K * h->C, stream));
+        DPE_CHECK_HIP(hipMemsetAsync(carrScores_dev, 0, sizeof(double2) * (size_t)K * h->sh.C, stream));
         hipLaunchKernelGGL(bcs_export_kernel, dim3(1, K), dim3(256), 0, stream,
-                           h->carrBank_d + (size_t)window * maxK * nBin, nBin, h->C, h->C / 2, K, maxK,
+                           h->carrBank_d + (size_t)window * maxK * nBin, nBin, h->sh.C, h->sh.C / 2, K, maxK,
                            h->cfg.binHalfWidth, reinterpret_cast<double2 *>(carrScores_dev));
     }
     DPE_CHECK_HIP(hipGetLastError());

@@ -24,11 +24,7 @@
 
 namespace dpe {
 
-#ifndef DPE_CHIP_SPL
-#define DPE_CHIP_SPL 17
-#endif
-constexpr int kSPL = DPE_CHIP_SPL;   // samples per lane (odd: the chunk stride in LDS entries must be odd for conflict-free writes)
-constexpr int kPass = 64 * kSPL;     // samples per wave pass
+// (kSPL samples per lane, kPass = 64 kSPL samples per wave pass: dpe_bcs_plan.h, the host's plan counts passes)
 constexpr int kPad = 64;             // clamp pads of the prefix array (|boundary offset| + |lag| < 64; a chip + 8 < 64)
 constexpr int kQLen = kPass + 2 * kPad + 1;
 

@@ -34,13 +34,7 @@ namespace dpe {
 #define DPE_C2_WAVES 3
 #endif
 constexpr int k2Own0 = 3;      // first owner lane
-#ifndef DPE_C2_OWN
-#define DPE_C2_OWN 58
-#endif
-constexpr int k2Own = DPE_C2_OWN;   // owner lanes per pass: lanes 3 .. 60 (measured at H: 58 owners at 11 blocks per CU 0.593 ms per 128 windows,
-                                    // 57 at 12 blocks 0.604, 50 at 13 blocks 0.635 -- lanes that own samples matter more than resident waves)
-constexpr int k2MaxL1 = 24;    // L1 = floor(fs / fc) <= 24: chips of at most 25 samples
-constexpr int k2MinL1 = 16;    // the margins reach +-32 samples: two regular chips must cover them
+// (k2Own owner lanes per pass, chips of k2MinL1 .. k2MaxL1 + 1 samples: dpe_bcs_plan.h, the host's plan sizes the tiles with them)
 constexpr int k2Pad = 64;
 constexpr int k2QLen = k2Pad + k2Own * (k2MaxL1 + 1) + 1 + 64;
 constexpr int k2Round = 16;    // list entries per gather round: two lane halves x eight entries (the list is zero-padded to a whole round)
