@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "dpe_common.h"
+#include "dpe_acq_plan.h"   // the search plan and its constants (kAcqFusedLen, kAcqBinGroup, ...): plain C++
 
 namespace dpe {
 
@@ -107,7 +108,6 @@ __global__ __launch_bounds__(256) void acq_mul_kernel(const float2 *__restrict__
 // (values are >= 0, so unsigned order is float order; a maximum does not depend on the order of the merges).  mp holds
 // zeros on entry (the wipe-off kernel clears it).  The separate column-maximum pass this replaces re-read the whole surface
 // with 320 blocks: 34 us of a 155 us search.
-constexpr int kAcqBinGroup = 25;
 __global__ __launch_bounds__(256) void acq_fold_kernel(const float2 *__restrict__ Y, int S, int M, int N, int coherent, int B,
                                                        float *__restrict__ surf, unsigned int *__restrict__ mpBits)
 {
@@ -177,8 +177,6 @@ __device__ __forceinline__ void acq_idft10(af2 (&v)[10])
 #include "dpe_acq_pack.h"
 #include "dpe_acq_mixed.h"
 namespace dpe {
-constexpr int kAcqFusedLen = 2500;
-constexpr int kAcqFusedBins = 6;     // bins per block: 21 x 32 blocks are resident at once (three per CU) on 256 CUs
 constexpr int kAcqSubStride = 281;   // LDS stride of the ten 250-point sub-sequences: = 25 (mod 32), so that the 25-lane groups of
                                      // passes 1 / 2 fall on distinct 8-byte bank slots
 // nSeg = 1: X[b][2500] holds the time-folded window (coherent mode).  nSeg = N: X[b][N][2500] holds the N code periods
@@ -886,7 +884,6 @@ __device__ __forceinline__ unsigned int wave_scan_addu(unsigned int v)
     return v;
 }
 
-constexpr int kAcqStatsR = 10;   // delays per thread: rows up to 2 560
 __global__ __launch_bounds__(256) void acq_stats_small_kernel(const float *__restrict__ surf, const float *__restrict__ mp, int B, int M, int maskS, int iLo,
                                                               double fLo, int iHi, double fHi, int *__restrict__ codeIdx, int *__restrict__ doppIdx,
                                                               AcqStats *__restrict__ out)
@@ -1123,23 +1120,21 @@ __global__ __launch_bounds__(256) void acq_stats_small_kernel(const float *__res
 
 }  // namespace dpe
 
+namespace dpe {
+static_assert(kAcqPackLds == kPkLdsBytes && kAcqMixedLds4000 == AcqMixedShape<4000, 10, 8, 5>::ldsBytes &&
+              kAcqMixedLds5000 == AcqMixedShape<5000, 10, 10, 5>::ldsBytes, "dpe_acq_plan.h states the kernels' dynamic LDS");
+}  // namespace dpe
+
 struct dpe_acq {
     dpe_acq_config cfg;
-    int S, N, M, B, P, len, chunk;   // len = FFT length (S in mode 1; M in modes 0 and 2)
-    int SX;                          // samples per Doppler row after the wipe-off (M in mode 0: time-folded)
+    dpe::AcqShape sh;   // everything create derives from cfg, the switches and the device's answers (dpe_acq_plan.h)
     dpe::FftPlan planFwd, planInv;
     float2 *X_d = nullptr, *Rc_d = nullptr, *Y_d = nullptr;
     float *surf_d = nullptr, *mp_d = nullptr;
     int *peakIdx_d = nullptr;   // [2][P]: max_code_idx, max_dopp_idx
-    float2 *tw_d = nullptr;     // exp(+j 2 pi n / 2500): the fused searches (acq_corr2500_kernel), else null
-    float2 *tw25k_d = nullptr;  // exp(+j 2 pi n / 25000): the radix-10 stage of the fused non-coherent search
-    bool fused = false, fusedAlias = false;
-    int fusedLen = 2500;        // fused coherent / textbook search: 2 500 (acq_corr2500_kernel) or 4 000 / 5 000 (acq_corr_mixed_kernel, dpe_acq_mixed.h)
-    bool fwdPack = true;        // packed form: wipe-off + forward transform in acq_fwd25k_pack_kernel (DPE_ACQ_NO_FWD_PACK=1: wipe kernel + rocFFT + decimation)
-    int cus = 256;              // compute units of the device (the packed form launches one persistent block per CU)
-    bool packForm = false;      // fusedAlias through acq_corr25k_pack_kernel (dpe_acq_pack.h); DPE_ACQ_NO_PACK=1 keeps acq_radix10_kernel + the four-pass transform (A/B runs)
+    float2 *tw_d = nullptr;     // exp(+j 2 pi n / M): the fused searches, else null
+    float2 *tw25k_d = nullptr;  // exp(+j 2 pi n / 10 M): the radix-10 stage of the fused non-coherent search
     float2 *Rcq_d = nullptr, *tw2_d = nullptr;   // packed form: the replicas' spectra decimated by ten, W2500^(a c) as [c][a]
-    bool fusedFwd = true;   // fused modes: wipe-off and forward transform in one kernel (-DDPE_EXPERIMENTS builds: DPE_ACQ_NO_FUSED_FWD=1 keeps wipe kernel + rocFFT)
     dpe::AcqStats *stats_hd = nullptr, *stats_h = nullptr;  // per-PRN peak statistics: pinned host memory the statistics kernel writes itself (_hd: its device address)
     bool searched = false;
     // fine-frequency stage, allocated on first use
@@ -1152,6 +1147,47 @@ struct dpe_acq {
     dpe::AcqFineChan *fineChan_d = nullptr;
     int8_t *chips_d = nullptr;
 };
+
+static bool acq_env(const char *name)
+{
+    const char *v = getenv(name);
+    return v && atoi(v) != 0;
+}
+
+// The switches of dpe_hip.h, read once per create.
+static dpe::AcqSwitches acq_read_switches()
+{
+    dpe::AcqSwitches sw;
+    sw.noFused = getenv("DPE_ACQ_NO_FUSED") != nullptr;   // (set at all: A/B runs and the cross-check of the parity tests)
+    sw.noPack = acq_env("DPE_ACQ_NO_PACK");
+    sw.noFwdPack = acq_env("DPE_ACQ_NO_FWD_PACK");
+#ifdef DPE_EXPERIMENTS
+    sw.noFusedFwd = acq_env("DPE_ACQ_NO_FUSED_FWD");
+    sw.statsLds = acq_env("DPE_ACQ_STATS_LDS");
+#endif
+    return sw;
+}
+
+// dst[i] = exp(+j 2 pi num(i) / den), i < count, built in fp64 on the host (dst: device memory, null after a failed allocation)
+template <class Num>
+static bool acq_upload_twiddles(float2 *dst, size_t count, double den, Num num)
+{
+    if (!dst) return false;
+    std::vector<float2> tw(count);
+    for (size_t i = 0; i < count; ++i) {
+        const double a = 6.283185307179586476925286766559 * (double)num((int)i) / den;
+        tw[i] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    return hipMemcpy(dst, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// The four acq_corr_mixed_kernel instances: 4 000 / 5 000 delays, fused (X and the replica spectra) or behind the radix-10 stage (Y)
+template <int M, int R2, int R3, int R4, bool ALIAS>
+static void acq_enqueue_mixed(dpe_acq *h, const dpe::AcqLaunch &l, hipStream_t st)
+{
+    hipLaunchKernelGGL((dpe::acq_corr_mixed_kernel<M, R2, R3, R4, ALIAS>), dim3(l.gx, l.gy), dim3(l.block), l.lds, st, ALIAS ? h->Y_d : h->X_d,
+                       ALIAS ? (const float2 *)nullptr : h->Rc_d, h->tw_d, h->sh.B, l.nSeg, l.bpb, l.p0, h->surf_d, reinterpret_cast<unsigned int *>(h->mp_d));
+}
 
 extern "C" {
 
@@ -1179,35 +1215,29 @@ int dpe_acq_create(const dpe_acq_config *cfg, dpe_acq **out)
     DPE_REQUIRE(cfg->samplingFrequency > 0, "[Acquisition] create: bad samplingFrequency");
     for (int i = 0; i < cfg->nPrn; ++i)
         DPE_REQUIRE(cfg->prn[i] >= 1 && cfg->prn[i] <= kPrnMax, "[Acquisition] create: PRN %d out of range", cfg->prn[i]);
+    // the switches and what the runtime says; the packed form is decided here, before the buffers are sized
+    const AcqSwitches sw = acq_read_switches();
+    AcqDevice dev;
+    if (acq_wants_pack(*cfg, sw)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(acq_corr25k_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPkLdsBytes) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void *>(acq_fwd25k_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPkLdsBytes) != hipSuccess) {
+            (void)hipGetLastError();
+            dev.packLds = false;
+        }
+        int id = 0;
+        hipDeviceProp_t prop;
+        if (dev.packLds && hipGetDevice(&id) == hipSuccess && hipGetDeviceProperties(&prop, id) == hipSuccess) dev.cus = prop.multiProcessorCount;
+    }
     dpe_acq *h = new dpe_acq();
     h->cfg = *cfg;
-    h->S = cfg->samplesPerWindow; h->N = cfg->nCodePeriods; h->M = h->S / h->N; h->B = cfg->nBins; h->P = cfg->nPrn;
-    h->len = (cfg->mode == 1) ? h->S : h->M;
-    h->SX = (cfg->mode == 0) ? h->M : h->S;
-    h->chunk = cfg->prnChunk > 0 ? std::min(cfg->prnChunk, h->P) : std::min(8, h->P);
-    // (the fused non-coherent form wants every PRN in one launch pair -- 32 PRNs x 25 bins: 0.19 ms at one chunk, 0.24 at chunks of
-    //  8, 1.16 at chunks of 1 -- while its stage buffer stays modest: 160 MB at the reference's raster)
-    if (cfg->prnChunk <= 0 && cfg->mode == 1 && h->M == 2500 && h->N == 10 && (size_t)h->P * h->B * h->S * sizeof(float2) <= ((size_t)1 << 30)) h->chunk = h->P;
-    const size_t S = h->SX, B = h->B, P = h->P;
-    // coherent / textbook search at 2 500 delays per code period: the fused kernel, which needs neither the product buffer nor
-    // the inverse plan (DPE_ACQ_NO_FUSED=1 keeps the rocFFT chain, for A/B runs and as the cross-check of the parity tests)
-    const bool wantFused = (cfg->mode == 0 || cfg->mode == 2) && (h->M == kAcqFusedLen || h->M == 4000 || h->M == 5000) && !getenv("DPE_ACQ_NO_FUSED");
-    // the reference's non-coherent search at 10 x 2 500 samples: radix-10 stage + ten fused 2 500-point transforms per (PRN, bin);
-    // the product buffer holds the radix-10 stage's output, no inverse plan
-    const bool wantAlias = cfg->mode == 1 && (h->M == kAcqFusedLen || h->M == 4000 || h->M == 5000) && h->N == 10 && !getenv("DPE_ACQ_NO_FUSED");
-    h->X_d = dev_alloc<float2>(B * S);
-    h->Rc_d = dev_alloc<float2>(P * (size_t)h->len);
-    bool wantPack = wantAlias && h->M == kAcqFusedLen && !(getenv("DPE_ACQ_NO_PACK") && atoi(getenv("DPE_ACQ_NO_PACK")) != 0);
-    // the packed form keeps ten transforms of a (PRN, bin) in 128 000 B of dynamic LDS: a device (or partition) that does not grant
-    // that much per work group runs the radix-10 kernel + four-pass transforms instead -- decided here, before the buffers are sized
-    if (wantPack && (hipFuncSetAttribute(reinterpret_cast<const void *>(acq_corr25k_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPkLdsBytes) != hipSuccess ||
-                     hipFuncSetAttribute(reinterpret_cast<const void *>(acq_fwd25k_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPkLdsBytes) != hipSuccess)) {
-        (void)hipGetLastError();
-        wantPack = false;
-    }
-    h->Y_d = dev_alloc<float2>(wantFused ? 1 : wantPack ? B * S : (size_t)h->chunk * B * S);   // (packed form: the bins' decimated spectra)
-    h->surf_d = dev_alloc<float>(P * B * (size_t)h->M);
-    h->mp_d = dev_alloc<float>(P * (size_t)h->M);
+    h->sh = acq_shape(*cfg, sw, dev);
+    const AcqShape &sh = h->sh;
+    const size_t P = sh.P;
+    h->X_d = dev_alloc<float2>(sh.nX);
+    h->Rc_d = dev_alloc<float2>(sh.nRc);
+    h->Y_d = dev_alloc<float2>(sh.nY);
+    h->surf_d = dev_alloc<float>(sh.nSurf);
+    h->mp_d = dev_alloc<float>(sh.nMp);
     h->peakIdx_d = dev_alloc<int>(2 * P);
     if (hipHostMalloc((void **)&h->stats_h, P * sizeof(AcqStats), hipHostMallocDefault) != hipSuccess) h->stats_h = nullptr;
     if (h->stats_h && hipHostGetDevicePointer((void **)&h->stats_hd, h->stats_h, 0) != hipSuccess) h->stats_hd = nullptr;
@@ -1216,99 +1246,72 @@ int dpe_acq_create(const dpe_acq_config *cfg, dpe_acq **out)
         dpe_acq_destroy(h);
         return -1;
     }
-    const int batchFwd = (int)(B * (S / h->len)), batchInv = (int)(h->chunk * B * (S / h->len));
-    if (h->planFwd.create((size_t)h->len, (size_t)batchFwd, false) ||
-        (!wantFused && !wantAlias && h->planInv.create((size_t)h->len, (size_t)batchInv, true))) {
+    if (h->planFwd.create((size_t)sh.fwdLen, (size_t)sh.fwdBatch, false) ||
+        (sh.invBatch && h->planInv.create((size_t)sh.invLen, (size_t)sh.invBatch, true))) {
         dpe_acq_destroy(h);   // (the message is rocFFT's, from dpe_fft.h)
         return -1;
     }
     // nominal-rate replica: chips[floor(n / fs * F_CA) mod 1023] (correlator.py:66, rawfile.py:164-166), fp64 on the host
-    std::vector<float2> rep(P * (size_t)h->len);
+    std::vector<float2> rep(sh.nRc);
     int8_t chips[kLCA];
     for (size_t p = 0; p < P; ++p) {
         gen_ca_code_host(cfg->prn[p], chips);
-        for (int i = 0; i < h->len; ++i) {
+        for (int i = 0; i < sh.len; ++i) {
             // mode 0: the replica folded over the N code periods of the window (see acq_wipe_fold_kernel)
             double acc = 0.0;
-            for (int n = 0; n < (cfg->mode == 0 ? h->N : 1); ++n) {
-                const double t = (double)(i + n * h->M) / cfg->samplingFrequency;
+            for (int n = 0; n < (cfg->mode == 0 ? sh.N : 1); ++n) {
+                const double t = (double)(i + n * sh.M) / cfg->samplingFrequency;
                 const long long ci = (long long)std::floor(t * kFCA);
                 acc += (double)chips[ci % kLCA];
             }
-            rep[p * h->len + i] = make_float2((float)acc, 0.f);
+            rep[p * sh.len + i] = make_float2((float)acc, 0.f);
         }
     }
     FftPlan pr;
     const auto finish = [&]() -> int {   // a failure here must leak neither the handle nor the temporary plan
         DPE_CHECK_HIP(hipMemcpy(h->Rc_d, rep.data(), sizeof(float2) * rep.size(), hipMemcpyHostToDevice));
-        if (pr.create((size_t)h->len, P, false) || pr.exec(nullptr, h->Rc_d)) return -1;
-        hipLaunchKernelGGL(acq_conj_scale_kernel, dim3(256), dim3(256), 0, 0, h->Rc_d, (long long)(P * h->len), 1.0f / (float)h->len);
+        if (pr.create((size_t)sh.len, P, false) || pr.exec(nullptr, h->Rc_d)) return -1;
+        hipLaunchKernelGGL(acq_conj_scale_kernel, dim3(256), dim3(256), 0, 0, h->Rc_d, (long long)(P * sh.len), 1.0f / (float)sh.len);
         DPE_CHECK_HIP(hipDeviceSynchronize());
         return 0;
     };
     int rc = finish();
     pr.destroy();
-    if (!rc && wantAlias) {
-        std::vector<float2> tw((size_t)10 * h->M);
-        for (int n = 0; n < 10 * h->M; ++n) {
-            const double a = 6.283185307179586476925286766559 * (double)n / (double)(10 * h->M);
-            tw[n] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-        h->tw25k_d = dev_alloc<float2>(tw.size());
-        if (!h->tw25k_d || hipMemcpy(h->tw25k_d, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    // the tables the shape lists
+    if (!rc && sh.nTw25k) {
+        h->tw25k_d = dev_alloc<float2>(sh.nTw25k);
+        if (!acq_upload_twiddles(h->tw25k_d, sh.nTw25k, (double)(10 * sh.M), [](int n) { return n; })) {
             set_error("[Acquisition] create: twiddle table");
             rc = -1;
-        } else h->fusedAlias = true;
+        }
     }
-    if (!rc && h->fusedAlias && wantPack) {
-        std::vector<float2> t2(2500);
-        for (int c = 0; c < 50; ++c)
-            for (int a = 0; a < 50; ++a) {
-                const double ang = 6.283185307179586476925286766559 * (double)(a * c) / 2500.0;
-                t2[c * 50 + a] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-            }
-        h->tw2_d = dev_alloc<float2>(t2.size());
-        h->Rcq_d = dev_alloc<float2>(P * (size_t)h->len);
-        if (!h->tw2_d || !h->Rcq_d || hipMemcpy(h->tw2_d, t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    if (!rc && sh.nTw2) {
+        h->tw2_d = dev_alloc<float2>(sh.nTw2);
+        h->Rcq_d = dev_alloc<float2>(sh.nRcq);
+        if (!h->Rcq_d || !acq_upload_twiddles(h->tw2_d, sh.nTw2, 2500.0, [](int i) { return (i % 50) * (i / 50); })) {   // [c][a]: W2500^(a c)
             set_error("[Acquisition] create: packed-form tables");
             rc = -1;
         } else {
             hipLaunchKernelGGL(acq_decimate10_kernel, dim3(40, (unsigned)P), dim3(640), 0, 0, h->Rc_d, h->Rcq_d);
             if (hipDeviceSynchronize() != hipSuccess) { set_error("[Acquisition] create: decimating the replica spectra"); rc = -1; }
-            else { h->packForm = true; h->fwdPack = !(getenv("DPE_ACQ_NO_FWD_PACK") && atoi(getenv("DPE_ACQ_NO_FWD_PACK")) != 0); }
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 1)
-                h->cus = prop.multiProcessorCount >= 8 ? prop.multiProcessorCount / 8 * 8 : prop.multiProcessorCount;
         }
     }
-#ifdef DPE_EXPERIMENTS
-    h->fusedFwd = !(getenv("DPE_ACQ_NO_FUSED_FWD") && atoi(getenv("DPE_ACQ_NO_FUSED_FWD")) != 0);
-#endif
-    if (!rc && (wantFused || wantAlias)) {
-        const int L = h->M;   // (2 500 for wantAlias)
-        std::vector<float2> tw((size_t)L);
-        for (int n = 0; n < L; ++n) {
-            const double a = 6.283185307179586476925286766559 * (double)n / (double)L;
-            tw[n] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-        h->tw_d = dev_alloc<float2>((size_t)L);
-        if (!h->tw_d || hipMemcpy(h->tw_d, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    if (!rc && sh.nTw) {
+        h->tw_d = dev_alloc<float2>(sh.nTw);
+        if (!acq_upload_twiddles(h->tw_d, sh.nTw, (double)sh.M, [](int n) { return n; })) {
             set_error("[Acquisition] create: twiddle table");
             rc = -1;
-        } else {
-            h->fused = wantFused;
-            h->fusedLen = L;
         }
-        if (!rc && L != kAcqFusedLen &&
-            (hipFuncSetAttribute(reinterpret_cast<const void *>(acq_corr_mixed_kernel<4000, 10, 8, 5, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)AcqMixedShape<4000, 10, 8, 5>::ldsBytes) != hipSuccess ||
-             hipFuncSetAttribute(reinterpret_cast<const void *>(acq_corr_mixed_kernel<5000, 10, 10, 5, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)AcqMixedShape<5000, 10, 10, 5>::ldsBytes) != hipSuccess ||
-             hipFuncSetAttribute(reinterpret_cast<const void *>(acq_corr_mixed_kernel<4000, 10, 8, 5, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)AcqMixedShape<4000, 10, 8, 5>::ldsBytes) != hipSuccess ||
-             hipFuncSetAttribute(reinterpret_cast<const void *>(acq_corr_mixed_kernel<5000, 10, 10, 5, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)AcqMixedShape<5000, 10, 10, 5>::ldsBytes) != hipSuccess)) {
+    }
+    if (!rc && sh.mixedOptIn) {
+        const struct { const void *kernel; size_t lds; } mixed[] = {
+            {reinterpret_cast<const void *>(acq_corr_mixed_kernel<4000, 10, 8, 5, false>), kAcqMixedLds4000},
+            {reinterpret_cast<const void *>(acq_corr_mixed_kernel<5000, 10, 10, 5, false>), kAcqMixedLds5000},
+            {reinterpret_cast<const void *>(acq_corr_mixed_kernel<4000, 10, 8, 5, true>), kAcqMixedLds4000},
+            {reinterpret_cast<const void *>(acq_corr_mixed_kernel<5000, 10, 10, 5, true>), kAcqMixedLds5000}};
+        for (const auto &m : mixed)
+            if (dev.mixedLds && hipFuncSetAttribute(m.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m.lds) != hipSuccess) dev.mixedLds = false;
+        if (!acq_create_ok(sh, dev)) {
             set_error("[Acquisition] create: LDS size of the fused search");
             rc = -1;
         }
@@ -1321,110 +1324,85 @@ int dpe_acq_create(const dpe_acq_config *cfg, dpe_acq **out)
     return 0;
 }
 
+// One record of the plan onto the stream.
+static int acq_enqueue(dpe_acq *h, const dpe::AcqLaunch &l, const int16_t *samples_dev, hipStream_t st)
+{
+    using namespace dpe;
+    const AcqShape &sh = h->sh;
+    const dpe_acq_config &c = h->cfg;
+    const int S = sh.SX, B = sh.B, P = sh.P, M = sh.M;
+    const dim3 grid(l.gx, l.gy, l.gz), block(l.block);
+    const double invFs = 1.0 / c.samplingFrequency;
+    const long long mpLen = (long long)P * M;
+    unsigned int *mpBits = reinterpret_cast<unsigned int *>(h->mp_d);
+    switch (l.kernel) {
+        case AcqKernel::Wipe:
+            hipLaunchKernelGGL(acq_wipe_kernel, grid, block, 0, st, samples_dev, S, B, c.binStartHz, c.binStepHz, invFs, h->X_d, h->mp_d, mpLen);
+            break;
+        case AcqKernel::WipeFold:
+            hipLaunchKernelGGL(acq_wipe_fold_kernel, grid, block, 0, st, samples_dev, M, sh.N, c.binStartHz, c.binStepHz, invFs, h->X_d, h->mp_d, mpLen);
+            break;
+        case AcqKernel::WipeFft2500:
+            hipLaunchKernelGGL(acq_wipe_fft2500_kernel, grid, block, 0, st, samples_dev, l.nSeg, c.binStartHz, c.binStepHz, invFs, h->tw_d, h->X_d, h->mp_d, mpLen);
+            break;
+        case AcqKernel::FwdPack:
+            hipLaunchKernelGGL(acq_fwd25k_pack_kernel, grid, block, l.lds, st, samples_dev, c.binStartHz, c.binStepHz, invFs, h->tw2_d, h->tw25k_d, h->Y_d, h->mp_d, mpLen);
+            break;
+        case AcqKernel::FftFwd:
+            return h->planFwd.exec(st, h->X_d) ? -1 : 0;
+        case AcqKernel::Corr2500:
+            hipLaunchKernelGGL(acq_corr2500_kernel<false>, grid, block, 0, st, h->X_d, h->Rc_d, h->tw_d, B, l.nSeg, l.bpb, 0, h->surf_d, mpBits);
+            break;
+        case AcqKernel::Mixed4000: acq_enqueue_mixed<4000, 10, 8, 5, false>(h, l, st); break;
+        case AcqKernel::Mixed5000: acq_enqueue_mixed<5000, 10, 10, 5, false>(h, l, st); break;
+        case AcqKernel::Decimate10:
+            hipLaunchKernelGGL(acq_decimate10_kernel, grid, block, 0, st, h->X_d, h->Y_d);
+            break;
+        case AcqKernel::CorrPack:
+            hipLaunchKernelGGL(acq_corr25k_pack_kernel, grid, block, l.lds, st, h->Y_d, h->Rcq_d + (size_t)l.p0 * sh.len, h->tw2_d, h->tw25k_d, B, l.pc, l.p0, h->surf_d,
+                               mpBits, l.order);
+            break;
+        case AcqKernel::Radix10:
+            hipLaunchKernelGGL(acq_radix10_kernel, grid, block, 0, st, h->X_d, h->Rc_d + (size_t)l.p0 * sh.len, h->tw25k_d, B, M, h->Y_d);
+            break;
+        case AcqKernel::Corr2500Alias:
+            hipLaunchKernelGGL(acq_corr2500_kernel<true>, grid, block, 0, st, h->Y_d, (const float2 *)nullptr, h->tw_d, B, l.nSeg, l.bpb, l.p0, h->surf_d, mpBits);
+            break;
+        case AcqKernel::Mixed4000Alias: acq_enqueue_mixed<4000, 10, 8, 5, true>(h, l, st); break;
+        case AcqKernel::Mixed5000Alias: acq_enqueue_mixed<5000, 10, 10, 5, true>(h, l, st); break;
+        case AcqKernel::Mul:
+            hipLaunchKernelGGL(acq_mul_kernel, grid, block, 0, st, h->X_d, h->Rc_d + (size_t)l.p0 * sh.len, S, sh.len, B, h->Y_d);
+            break;
+        case AcqKernel::FftInv:
+            return h->planInv.exec(st, h->Y_d) ? -1 : 0;
+        case AcqKernel::Fold:
+            hipLaunchKernelGGL(acq_fold_kernel, grid, block, 0, st, h->Y_d, S, M, l.nSeg, l.coherent, B, h->surf_d + (size_t)l.p0 * B * M, mpBits + (size_t)l.p0 * M);
+            break;
+        // (folding the statistics into the search kernel -- the last block of a PRN, a ticket per PRN, the maxima as 64-bit {value, ~bin}
+        //  keys -- was built in round 6 and is slower: all blocks of a coherent search are resident at once, so every PRN's last block ends
+        //  with the launch and nothing overlaps; 0.0544 -> 0.0584 ms coherent, 0.244 -> 0.2535 textbook.  With a device-scope fence per
+        //  block instead of atomics-only hand-over: 0.131 / 0.684 -- an L2 write-back per block.  DESIGN_LOG.md A.15)
+        case AcqKernel::StatsSmall:
+            hipLaunchKernelGGL(acq_stats_small_kernel, grid, block, 0, st, h->surf_d, h->mp_d, B, M, sh.maskS, sh.iLo, sh.fLo, sh.iHi, sh.fHi, h->peakIdx_d,
+                               h->peakIdx_d + P, h->stats_hd);
+            break;
+        case AcqKernel::Stats:   // (48 bytes per PRN straight into the pinned mirror: a D2H copy command behind the kernel cost ~5 us of stream time)
+            hipLaunchKernelGGL(acq_stats_kernel, grid, block, l.lds, st, h->surf_d, h->mp_d, B, M, sh.rowInLds, sh.maskS, sh.iLo, sh.fLo, sh.iHi, sh.fHi,
+                               h->peakIdx_d, h->peakIdx_d + P, h->stats_hd);
+            break;
+        case AcqKernel::Count: break;
+    }
+    return 0;
+}
+
 int dpe_acq_search(dpe_acq *h, const int16_t *samples_dev, dpe_stream_t stream_)
 {
     using namespace dpe;
     DPE_REQUIRE(h && samples_dev, "[Acquisition] search: null argument");
     hipStream_t st = (hipStream_t)stream_;
-    const int S = h->SX, B = h->B, P = h->P, M = h->M;
-    if (h->packForm && h->fwdPack) {
-        hipLaunchKernelGGL(acq_fwd25k_pack_kernel, dim3(B), dim3(512), kPkLdsBytes, st, samples_dev, h->cfg.binStartHz, h->cfg.binStepHz,
-                           1.0 / h->cfg.samplingFrequency, h->tw2_d, h->tw25k_d, h->Y_d, h->mp_d, (long long)P * M);
-    } else if (h->fused && h->fusedLen == kAcqFusedLen && h->fusedFwd && h->cfg.mode != 0) {
-        // textbook mode (N rows of 2 500 per bin): wipe-off and the forward transform in one launch, 0.271 -> 0.260 ms per 32-PRN window.
-        // (Coherent mode keeps the two launches: one block per bin would have to fold ten periods -- a hundred sin / cos pairs per
-        // thread on 125 blocks -- and measured 0.066 against 0.060 ms.)
-        hipLaunchKernelGGL(acq_wipe_fft2500_kernel, dim3(B, h->cfg.mode == 0 ? 1 : h->N), dim3(512), 0, st, samples_dev, h->cfg.mode == 0 ? h->N : 1,
-                           h->cfg.binStartHz, h->cfg.binStepHz, 1.0 / h->cfg.samplingFrequency, h->tw_d, h->X_d, h->mp_d, (long long)P * M);
-    } else {
-        if (h->cfg.mode == 0)
-            hipLaunchKernelGGL(acq_wipe_fold_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, samples_dev, M, h->N,
-                               h->cfg.binStartHz, h->cfg.binStepHz, 1.0 / h->cfg.samplingFrequency, h->X_d, h->mp_d, (long long)P * M);
-        else
-            hipLaunchKernelGGL(acq_wipe_kernel, dim3((S + 1023) / 1024, B), dim3(256), 0, st, samples_dev, S, B, h->cfg.binStartHz,
-                               h->cfg.binStepHz, 1.0 / h->cfg.samplingFrequency, h->X_d, h->mp_d, (long long)P * M);
-        if (h->planFwd.exec(st, h->X_d)) return -1;
-    }
-    if (h->fused && h->fusedLen != kAcqFusedLen) {
-        // 4 / 5 Msps: the generic four-pass transform (dpe_acq_mixed.h), two blocks resident per CU; bins per block measured over 1 .. 8
-        // (profiles/r5_ab_acq_rates.txt)
-        const int nSeg = h->cfg.mode == 0 ? 1 : h->N;
-        const int bpb = h->cfg.mode == 0 ? 8 : 4;   // 16 x 32 = 512 blocks = one round at two per CU / 32 x 32 = two rounds of ten transforms per bin
-        constexpr size_t lds4 = AcqMixedShape<4000, 10, 8, 5>::ldsBytes, lds5 = AcqMixedShape<5000, 10, 10, 5>::ldsBytes;
-        if (h->fusedLen == 4000)
-            hipLaunchKernelGGL((acq_corr_mixed_kernel<4000, 10, 8, 5, false>), dim3((B + bpb - 1) / bpb, P), dim3(400), lds4, st, h->X_d,
-                               h->Rc_d, h->tw_d, B, nSeg, bpb, 0, h->surf_d, reinterpret_cast<unsigned int *>(h->mp_d));
-        else
-            hipLaunchKernelGGL((acq_corr_mixed_kernel<5000, 10, 10, 5, false>), dim3((B + bpb - 1) / bpb, P), dim3(500), lds5, st, h->X_d,
-                               h->Rc_d, h->tw_d, B, nSeg, bpb, 0, h->surf_d, reinterpret_cast<unsigned int *>(h->mp_d));
-    } else if (h->fused) {
-        // bins per block: six in the coherent mode (672 blocks = one round of the 768 resident ones); ONE in the textbook mode, whose blocks
-        // already run ten transforms per bin -- 4 000 short blocks balance the tail (0.229 -> 0.206 ms per 32 x 125 search; five bins per
-        // block, 800 blocks = one round plus 32 stragglers, measured 0.265)
-        const int bpb = h->cfg.mode == 0 ? kAcqFusedBins : 1;
-        hipLaunchKernelGGL(acq_corr2500_kernel<false>, dim3((B + bpb - 1) / bpb, P), dim3(256), 0, st, h->X_d, h->Rc_d, h->tw_d,
-                           B, h->cfg.mode == 0 ? 1 : h->N, bpb, 0, h->surf_d, reinterpret_cast<unsigned int *>(h->mp_d));
-    }
-    for (int p0 = 0; !h->fused && p0 < P; p0 += h->chunk) {
-        const int pc = std::min(h->chunk, P - p0);
-        if (h->packForm) {
-            if (p0 == 0 && !h->fwdPack) hipLaunchKernelGGL(acq_decimate10_kernel, dim3(40, (unsigned)B), dim3(640), 0, st, h->X_d, h->Y_d);
-            const int items = pc * B, nBlk = std::min(h->cus, pc % 8 == 0 ? (items + 7) / 8 * 8 : items);
-            hipLaunchKernelGGL(acq_corr25k_pack_kernel, dim3(nBlk), dim3(512), kPkLdsBytes, st, h->Y_d, h->Rcq_d + (size_t)p0 * h->len, h->tw2_d, h->tw25k_d,
-                               B, pc, p0, h->surf_d, reinterpret_cast<unsigned int *>(h->mp_d), (pc % 8 == 0 && nBlk % 8 == 0) ? 1 : 0);
-            continue;
-        }
-        if (h->fusedAlias) {
-            hipLaunchKernelGGL(acq_radix10_kernel, dim3((M + 255) / 256, B, pc), dim3(256), 0, st, h->X_d, h->Rc_d + (size_t)p0 * h->len, h->tw25k_d,
-                               B, M, h->Y_d);
-            // one bin per block: 10 transforms each, B x pc blocks (25 x 32 = 800 at the reference's raster: one round of the chip)
-            if (M == 4000) {
-                constexpr size_t lds4 = AcqMixedShape<4000, 10, 8, 5>::ldsBytes;
-                hipLaunchKernelGGL((acq_corr_mixed_kernel<4000, 10, 8, 5, true>), dim3(B, pc), dim3(400), lds4, st, h->Y_d, (const float2 *)nullptr, h->tw_d, B, h->N, 1, p0,
-                                   h->surf_d, reinterpret_cast<unsigned int *>(h->mp_d));
-            } else if (M == 5000) {
-                constexpr size_t lds5 = AcqMixedShape<5000, 10, 10, 5>::ldsBytes;
-                hipLaunchKernelGGL((acq_corr_mixed_kernel<5000, 10, 10, 5, true>), dim3(B, pc), dim3(500), lds5, st, h->Y_d, (const float2 *)nullptr, h->tw_d, B, h->N, 1, p0,
-                                   h->surf_d, reinterpret_cast<unsigned int *>(h->mp_d));
-            } else
-                hipLaunchKernelGGL(acq_corr2500_kernel<true>, dim3(B, pc), dim3(256), 0, st, h->Y_d, (const float2 *)nullptr, h->tw_d, B, h->N, 1, p0,
-                                   h->surf_d, reinterpret_cast<unsigned int *>(h->mp_d));
-            continue;
-        }
-        hipLaunchKernelGGL(acq_mul_kernel, dim3((S + 1023) / 1024, B, pc), dim3(256), 0, st, h->X_d,
-                           h->Rc_d + (size_t)p0 * h->len, S, h->len, B, h->Y_d);
-        // a short last chunk still runs the full-batch plan over stale rows; they are never read
-        if (h->planInv.exec(st, h->Y_d)) return -1;
-        // mode 0 arrives already folded: one term, |.|
-        hipLaunchKernelGGL(acq_fold_kernel, dim3((M + 255) / 256, (B + kAcqBinGroup - 1) / kAcqBinGroup, pc), dim3(256), 0, st, h->Y_d, S, M,
-                           h->cfg.mode == 0 ? 1 : h->N, h->cfg.mode == 0 ? 1 : 0, B, h->surf_d + (size_t)p0 * B * M,
-                           reinterpret_cast<unsigned int *>(h->mp_d) + (size_t)p0 * M);
-    }
-    {
-        // percentile positions of _trim_mean(max_percode, 10): pos = (M - 1) q / 100, q = 5 and 95 (numpy.percentile)
-        const double posLo = (double)(M - 1) * 5.0 / 100.0, posHi = (double)(M - 1) * 95.0 / 100.0;
-        const int iLo = (int)std::floor(posLo), iHi = (int)std::floor(posHi);
-        const int maskS = (int)std::ceil(h->cfg.samplingFrequency / kFCA);                      // :96-99
-        // (the kernel's static LDS is ~17 KB: the row joins it only while the sum stays below the 64 KB a launch gets without
-        //  an opt-in -- M <= 10 240 -- and is read from memory beyond)
-        const int rowInLds = (size_t)M * sizeof(float) <= 40 * 1024 ? 1 : 0;
-#ifdef DPE_EXPERIMENTS
-        const bool statsLds = getenv("DPE_ACQ_STATS_LDS") && atoi(getenv("DPE_ACQ_STATS_LDS")) != 0;
-#else
-        constexpr bool statsLds = false;
-#endif
-        // (folding these statistics into the search kernel -- the last block of a PRN, a ticket per PRN, the maxima as 64-bit {value, ~bin}
-        //  keys -- was built in round 6 and is slower: all blocks of a coherent search are resident at once, so every PRN's last block ends
-        //  with the launch and nothing overlaps; 0.0544 -> 0.0584 ms coherent, 0.244 -> 0.2535 textbook.  With a device-scope fence per
-        //  block instead of atomics-only hand-over: 0.131 / 0.684 -- an L2 write-back per block.  DESIGN_LOG.md A.15)
-        if (M <= 256 * kAcqStatsR && !statsLds)
-            hipLaunchKernelGGL(acq_stats_small_kernel, dim3(P), dim3(256), 0, st, h->surf_d, h->mp_d, B, M, maskS, iLo, posLo - (double)iLo, iHi,
-                               posHi - (double)iHi, h->peakIdx_d, h->peakIdx_d + P, h->stats_hd);
-        else
-        hipLaunchKernelGGL(acq_stats_kernel, dim3(P), dim3(256), rowInLds ? (size_t)M * sizeof(float) : 0, st, h->surf_d, h->mp_d, B, M,
-                           rowInLds, maskS, iLo, posLo - (double)iLo, iHi, posHi - (double)iHi, h->peakIdx_d, h->peakIdx_d + P,
-                           h->stats_hd);   // (48 bytes per PRN straight into the pinned mirror: a D2H copy command behind the kernel cost ~5 us of stream time)
-    }
+    int rc = 0;   // (a rocFFT execution that fails ends the search: nothing behind it is enqueued)
+    acq_for_each_launch(h->sh, [&](const AcqLaunch &l) { return rc == 0 && (rc = acq_enqueue(h, l, samples_dev, st)) == 0; });
+    if (rc) return -1;
     DPE_CHECK_HIP(hipGetLastError());
     h->searched = true;
     return 0;
@@ -1435,7 +1413,7 @@ int dpe_acq_results(dpe_acq *h, dpe_acq_result *out, dpe_stream_t stream)
     using namespace dpe;
     DPE_REQUIRE(h && out && h->searched, "[Acquisition] results: no search yet");
     DPE_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));   // the statistics kernel wrote stats_h itself
-    const int P = h->P;
+    const int P = h->sh.P;
     const double fs = h->cfg.samplingFrequency;
     for (int p = 0; p < P; ++p) {
         const AcqStats &st = h->stats_h[p];
@@ -1458,7 +1436,7 @@ static int fine_prepare(dpe_acq *h)
 {
     using namespace dpe;
     if (h->haveFine) return 0;
-    const int S = h->S, P = h->P;
+    const int S = h->sh.S, P = h->sh.P;
     int bl = 0;
     for (int v = S; v; v >>= 1) ++bl;            // S.bit_length()
     const long long C = 8ll * (1ll << bl);       // rawfile.carr_fftpts, rawfile.py:173
@@ -1466,7 +1444,7 @@ static int fine_prepare(dpe_acq *h)
     h->fineC = (int)C;
     // shifted indices kept by the mask (:124-125): min(bins) <= fftfreq <= max(bins), fftfreq = k * (1 / (C * (1 / fs)))
     const double fs = h->cfg.samplingFrequency, val = 1.0 / ((double)C * (1.0 / fs));
-    const double b0 = h->cfg.binStartHz, b1 = h->cfg.binStartHz + h->cfg.binStepHz * (h->B - 1);
+    const double b0 = h->cfg.binStartHz, b1 = h->cfg.binStartHz + h->cfg.binStepHz * (h->sh.B - 1);
     const double fmin = std::min(b0, b1), fmax = std::max(b0, b1);
     long long lo = (long long)std::floor(fmin / val) - 2, hi = (long long)std::ceil(fmax / val) + 2;
     while ((double)lo * val < fmin) ++lo;
@@ -1497,7 +1475,7 @@ int dpe_acq_fine(dpe_acq *h, const int16_t *samples_dev, const dpe_acq_result *c
     DPE_REQUIRE(h && samples_dev && coarse && fine, "[Acquisition] fine: null argument");
     if (fine_prepare(h)) return -1;
     hipStream_t st = (hipStream_t)stream_;
-    const int S = h->S, P = h->P, C = h->fineC;
+    const int S = h->sh.S, P = h->sh.P, C = h->fineC;
     std::vector<AcqFineChan> ch(P);
     for (int p = 0; p < P; ++p) {
         DPE_REQUIRE(coarse[p].fc > 0, "[Acquisition] fine: bad coarse code frequency (PRN %d)", h->cfg.prn[p]);
@@ -1542,8 +1520,8 @@ int dpe_acq_scalar_acquisition(dpe_acq *h, const int16_t *window0_dev, const int
 {
     using namespace dpe;
     DPE_REQUIRE(h && window0_dev && window1_dev && out, "[Acquisition] scalar_acquisition: null argument");
-    const int P = h->P;
-    const double T = (double)h->S / h->cfg.samplingFrequency;
+    const int P = h->sh.P;
+    const double T = (double)h->sh.S / h->cfg.samplingFrequency;
     std::vector<dpe_acq_result> c0(P), c1(P);
     std::vector<dpe_acq_fine_result> f0(P), f1(P);
     if (dpe_acq_search(h, window0_dev, stream) || dpe_acq_results(h, c0.data(), stream) ||

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import navlab_dpe_sdr_amd as dpe
+from tests import acq_rows
 
 pytestmark = pytest.mark.gpu
 PRNS = [2, 12, 19, 28, 5, 30]
@@ -281,6 +282,44 @@ def test_acq_statistics_of_a_nearly_constant_row(oracle):
         assert abs(res[p]["cppm"] / ref["cppm"] - 1) < 2e-4 and abs(res[p]["cppr"] / ref["cppr"] - 1) < 2e-4
         assert 0.9 < res[p]["cppm"] < 1.1      # (a few percent of spread: some 250 values per bin)
     acq.close()
+
+
+@pytest.mark.parametrize("row", [acq_rows.STATS_RADIX_LDS, acq_rows.STATS_RADIX_MEMORY], ids=lambda r: r["name"])
+def test_acq_statistics_radix_fallback_through_the_walked_row(oracle, row):
+    """The radix passes behind the histogram of linear bins, in acq_stats_kernel, whose threads walk the row -- in LDS at 4 000
+    delays (4 Msps), in memory at 12 000 (12 Msps); the nearly constant row above reaches them only in acq_stats_small_kernel, with
+    the row in registers.  The same DC window (seed 5, I + 1000, Q - 300, +-1 LSB of noise), coherent mode, PRNs 1 and 30.
+    Precondition, from the oracle's own max_percode: after masking +-ceil(fs / 1.023e6) delays about the peak, the two bins of
+    width mean / 256 that hold the 5 % and the 95 % rank contain more than 64 values each, so the in-wave ranking cannot take them
+    (561 / 552 and 1879 / 1956 values at 4 Msps, 5998 / 5974 and 1037 / 981 at 12 Msps).  cppm and cppr within 2e-4 of the oracle
+    (the bound of the test above), nothing found, the oracle's peak cell."""
+    import torch
+    fs, S, prns, bins = row["fs"], row["S"], acq_rows.prns_of(row), acq_rows.bins_of(row)
+    M = S // 10
+    iq = acq_rows.dc_window(S)
+    acq = acq_rows.create(row)
+    acq.search(torch.from_numpy(iq).to("cuda:0"))
+    res = acq.results()
+    acq.close()
+    mask = int(np.ceil(fs / 1.023e6))
+    for r, prn in zip(res, prns):
+        ref = oracle.coarse_acquisition(iq, fs, prn, bins, coherent=True, wrap_mask=True)
+        v = np.asarray(ref["max_percode"], dtype=np.float32).copy()
+        assert v.shape == (M,)
+        width = np.float32(v.sum(dtype=np.float64) / M / 256.0)      # bins of the row's mean / 256, as the kernel lays them
+        d = np.abs(np.arange(M) - ref["max_code_idx"])
+        v[np.minimum(d, M - d) <= mask] = 0.0
+        b = np.minimum(np.floor(v / width), 2047).astype(np.int64)
+        order = np.sort(v)
+        for q in (5.0, 95.0):
+            k = int(np.floor((M - 1) * q / 100.0))
+            crowd = int((b == min(int(np.floor(order[k] / width)), 2047)).sum())
+            print("fs %.0f PRN %d: %d values in the bin of the %g %% rank" % (fs, prn, crowd, q))
+            assert crowd > 64, (prn, q, crowd)
+        print("PRN %d cppm %.9g / %.9g cppr %.9g / %.9g" % (prn, r["cppm"], ref["cppm"], r["cppr"], ref["cppr"]))
+        assert not r["found"] and not ref["found"]
+        assert (r["max_code_idx"], r["max_dopp_idx"]) == (ref["max_code_idx"], ref["max_dopp_idx"])
+        assert abs(r["cppm"] / ref["cppm"] - 1) < 2e-4 and abs(r["cppr"] / ref["cppr"] - 1) < 2e-4
 
 
 @pytest.mark.gpu
