@@ -1078,6 +1078,51 @@ int dpe_bcm_profile(dpe_bcm *h, int32_t enable, float *ms, int32_t *count);
 int dpe_bcs_set_graph(dpe_bcs *h, int32_t enable);
 int dpe_bcm_set_graph(dpe_bcm *h, int32_t enable);
 
+/* ------------------------------------------------------------------ Signal synthesiser ---- */
+/* Seeded interleaved int16 I/Q written straight into a device buffer from channel parameters (csrc/dpe_syn.hip): the
+ * buffer is what dpe_bcs_update, dpe_pipe_submit, dpe_acq_search, dpe_trk_track and dpe_vt_track take.  No counterpart in the
+ * reference, whose samples come from a file; the signal model is its Python twin's replica (pygnss correlator.py:367-465 on the
+ * rawfile.py:140-158 time base).  In pre-rounding value, sample i of a segment is
+ *   x = sum_k amp_k sign_k chip_k[ci mod 1023] exp(2 pi j frac(fi_k t + ri_k)) + sigma (gI + j gQ) + (dcI + j dcQ),  ci = floor(t fc_k + rc_k),
+ * and the output clip(rint(x), -32768, 32767) per component (round to nearest even).  t, ci, ci mod 1023 (floor modulus), the nav-bit
+ * index and the cycle fraction are IEEE fp64 with multiply and add unfused; sine, cosine, logarithm and the sums are fp32.
+ * Noise: Philox4x32-10, key (seed low, seed high), counter (n low, n high, stream low, stream high) -- n = the absolute sample index
+ * of a record, the in-window index of a window; stream = the caller's (window or realisation index).  Of the output words w0..w3,
+ * u1 = ((w0 >> 8) + 1) 2^-24, u2 = (w1 >> 8) 2^-24, r = sqrt(-2 ln u1), gI = r cos(2 pi u2), gQ = r sin(2 pi u2); w2, w3 are reserved.
+ * u1 >= 2^-24, so the Gaussian tail ends at sqrt(48 ln 2) = 5.77 sigma.  A sample's noise depends on (seed, stream, n) alone. */
+typedef struct dpe_syn dpe_syn;
+typedef struct dpe_syn_config {
+    double samplingFrequency;
+    int32_t maxSegments;          /* windows per dpe_syn_windows call, 1..65536 */
+    int32_t maxChannels;          /* <= DPE_MAX_CHAN */
+    int32_t maxNavBits;           /* per channel, record form (0: windows only) */
+    int32_t reserved;
+} dpe_syn_config;
+typedef struct dpe_syn_signal {
+    double sigma;                 /* noise standard deviation per component, >= 0; N0 = 2 sigma^2 / fs against C = amp^2 */
+    double dcI, dcQ;
+    uint64_t seed;
+} dpe_syn_signal;
+int dpe_syn_create(const dpe_syn_config *cfg, dpe_syn **out);
+int dpe_syn_destroy(dpe_syn *h);
+/* Channel slot `chan`'s nav bits (+1 / -1) of the record form; bit j covers the code periods gen_iq_record gives it: the first edge
+ * falls cpReference % 20 code periods after the start of the one sample 0 lies in.  All +1 until set.  Synchronises. */
+int dpe_syn_set_nav_bits(dpe_syn *h, int32_t chan, const int8_t *bits /* host [nBits] */, int32_t nBits, dpe_stream_t stream);
+/* nWindows windows of S samples: window w at out_dev + w strideInt16 (int16 VALUES, even, >= 2 S; what lies between windows is not
+ * touched), from chan_host[w][k] as dpe_chm_outputs yields it, t = rint(i / fs 1e9) / 1e9, noise stream firstStream + w with n = i.
+ * flip (optional, [nWindows][nChan]): non-zero puts a sign change at the predicted nav-bit boundary (BCS_NavBitBoundary) when that
+ * lies inside the window.  amp[nChan] is shared by the windows.  Asynchronous on `stream`: the parameters travel through a pinned
+ * staging ring, and the call waits only when four calls of the handle are in flight. */
+int dpe_syn_windows(dpe_syn *h, int16_t *out_dev, int64_t strideInt16, int32_t nWindows, int32_t S, int32_t nChan,
+                    const dpe_chan_start *chan_host, const double *amp, const dpe_syn_signal *sig, const uint8_t *flip,
+                    uint64_t firstStream, dpe_stream_t stream);
+/* Samples [firstSample, firstSample + nSamples) of a continuous record into out_dev[0 .. 2 nSamples): t = n / fs, chan_host[k]
+ * referred to sample 0 (cpElapsedStart is not read), nav bits as set, one noise stream with n absolute -- so any split of a range
+ * into calls, in any order, gives the bytes of one call.  Refused when a channel's bit array ends before its last sample.
+ * Asynchronous like dpe_syn_windows. */
+int dpe_syn_record(dpe_syn *h, int16_t *out_dev, int64_t firstSample, int64_t nSamples, int32_t nChan, const dpe_chan_start *chan_host,
+                   const double *amp, const dpe_syn_signal *sig, uint64_t streamId, dpe_stream_t stream);
+
 /* Timing helper for bench.py: HIP events on the stream the kernels run on. */
 int dpe_event_create(void **ev);
 int dpe_event_record(void *ev, dpe_stream_t stream);

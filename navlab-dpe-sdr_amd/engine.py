@@ -46,6 +46,7 @@ EXPORTS = [
     "dpe_nav_create", "dpe_nav_destroy", "dpe_nav_decode", "dpe_nav_set_ephemerides", "dpe_nav_solve", "dpe_nav_solve_log", "dpe_nav_status", "dpe_nav_load_log",
     "dpe_vt_create", "dpe_vt_destroy", "dpe_vt_set_ephemerides", "dpe_vt_init", "dpe_vt_init_from_trk", "dpe_vt_track", "dpe_vt_read_log",
     "dpe_vt_read_corr", "dpe_vt_state", "dpe_vt_dev_status", "dpe_vt_filter_step_host",
+    "dpe_syn_create", "dpe_syn_destroy", "dpe_syn_set_nav_bits", "dpe_syn_windows", "dpe_syn_record",
 ]
 
 
@@ -1979,6 +1980,97 @@ class cuEKF:
     def __del__(self):
         try:            # at interpreter shutdown module globals may already be gone
             self.Stop()
+        except Exception:
+            pass
+
+
+class SynConfig(C.Structure):       # dpe_syn_config
+    _fields_ = [("samplingFrequency", C.c_double), ("maxSegments", C.c_int32), ("maxChannels", C.c_int32), ("maxNavBits", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class SynSignal(C.Structure):       # dpe_syn_signal
+    _fields_ = [("sigma", C.c_double), ("dcI", C.c_double), ("dcQ", C.c_double), ("seed", C.c_uint64)]
+
+
+class Synthesizer:
+    """Seeded int16 I/Q made on the device from channel parameters (dpe_syn_*, csrc/dpe_syn.hip): synth.gen_iq's
+    model for windows and synth.gen_iq_record's for a continuous record, with counter-based noise -- a sample depends on
+    (seed, stream, sample index) alone.  Both calls are asynchronous and return torch int16 tensors on the device that
+    BatchCorrScores.Update, Pipe.submit, Acquisition.search, ScalarTracker.track and VectorTracker.track take as they are."""
+
+    def __init__(self, SamplingFrequency, max_segments=1, max_channels=8, max_nav_bits=0):
+        self.fs = float(SamplingFrequency)
+        self.max_segments, self.max_channels, self.max_nav_bits = int(max_segments), int(max_channels), int(max_nav_bits)
+        cfg = SynConfig(self.fs, self.max_segments, self.max_channels, self.max_nav_bits, 0)
+        self._h = C.c_void_p(None)
+        _check(lib().dpe_syn_create(C.byref(cfg), C.byref(self._h)))
+
+    @staticmethod
+    def _chan(chan):
+        """CHAN_START_DTYPE array, or a dict with synth.random_channels' keys (prn, rc, ri, fc, fi and optionally cp, cp_ref)."""
+        if isinstance(chan, dict):
+            z = np.zeros(np.shape(chan["rc"]), dtype=np.int32)
+            chan = chan_start_array(chan["prn"], chan["rc"], chan["ri"], chan["fc"], chan["fi"], chan.get("cp", z), chan.get("cp_ref", z))
+        return np.ascontiguousarray(chan, dtype=CHAN_START_DTYPE)
+
+    @staticmethod
+    def _signal(K, amp, sigma, dc, seed):
+        amp = np.ascontiguousarray(np.broadcast_to(np.asarray(amp, dtype=np.float64), (K,)))
+        return amp, SynSignal(float(sigma), float(dc[0]), float(dc[1]), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    def set_nav_bits(self, nav_bits, stream=None):
+        """nav_bits[k]: +-1 per bit of channel slot k (gen_iq_record's convention)."""
+        for k, b in enumerate(nav_bits):
+            b = np.ascontiguousarray(b, dtype=np.int8)
+            _check(lib().dpe_syn_set_nav_bits(self._h, C.c_int32(k), b.ctypes.data_as(C.POINTER(C.c_int8)), C.c_int32(b.size), _stream(stream)))
+
+    def windows(self, S, chan, amp=48.0, sigma=300.0, dc=(3.0, -2.0), flip=None, seed=0, first_stream=0, stride=None, out=None,
+                stream=None):
+        """W windows of S samples from chan[W][K] (or [K]: one window): the device form of the loop body of
+        workload.build_windows.  stride: int16 values between windows (even, >= 2 S; default 2 S).  Window w draws its noise
+        from stream first_stream + w.  Returns int16 [W, stride] (`out`, when given, is written in place: what lies between
+        windows is not touched)."""
+        import torch
+        chan = self._chan(chan)
+        if chan.ndim == 1:
+            chan = chan[None, :]
+        W, K = chan.shape
+        stride = 2 * int(S) if stride is None else int(stride)
+        amp, sig = self._signal(K, amp, sigma, dc, seed)
+        fl = None
+        if flip is not None:
+            fl = np.ascontiguousarray(np.broadcast_to(np.asarray(flip, dtype=bool), (W, K)), dtype=np.uint8)
+        if out is None:
+            out = torch.empty((W, max(stride, 2 * int(S))), dtype=torch.int16, device="cuda")
+        _check(lib().dpe_syn_windows(self._h, _ptr(out), C.c_int64(stride), C.c_int32(W), C.c_int32(int(S)), C.c_int32(K),
+                                     chan.ctypes.data_as(C.POINTER(ChanStart)), amp.ctypes.data_as(C.POINTER(C.c_double)), C.byref(sig),
+                                     None if fl is None else fl.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint64(int(first_stream)),
+                                     _stream(stream)))
+        return out
+
+    def record(self, first_sample, n_samples, chan, amp=48.0, sigma=300.0, dc=(0.0, 0.0), seed=0, stream_id=0, out=None, stream=None):
+        """Samples [first_sample, first_sample + n_samples) of the continuous record of chan[K] (referred to sample 0), nav bits
+        as set_nav_bits left them.  Any split of a range into calls gives the bytes of one call.  Returns int16 [2 n_samples]."""
+        import torch
+        chan = self._chan(chan)
+        K = chan.shape[0]
+        amp, sig = self._signal(K, amp, sigma, dc, seed)
+        if out is None:
+            out = torch.empty(2 * int(n_samples), dtype=torch.int16, device="cuda")
+        _check(lib().dpe_syn_record(self._h, _ptr(out), C.c_int64(int(first_sample)), C.c_int64(int(n_samples)), C.c_int32(K),
+                                    chan.ctypes.data_as(C.POINTER(ChanStart)), amp.ctypes.data_as(C.POINTER(C.c_double)), C.byref(sig),
+                                    C.c_uint64(int(stream_id)), _stream(stream)))
+        return out
+
+    def close(self):
+        if self._h:
+            lib().dpe_syn_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:            # at interpreter shutdown module globals may already be gone
+            self.close()
         except Exception:
             pass
 

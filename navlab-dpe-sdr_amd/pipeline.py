@@ -455,3 +455,78 @@ def run_vector_tracking(samples, start, fs, n_epochs=None, T=1e-3, N=20, fix=Non
     status = vt.dev_status(stream)
     vt.close()
     return log, ho, status
+
+
+def run_monte_carlo(ho, fs, S, K, pos_grid, vel_grid, cn0_dbhz, n_real, seed, init_delta=(0, 0, 0, 0), lpower=1, weighted_mean=False,
+                    sigma=300.0, lag_half_width=None, bin_half_width=None):
+    """RMSE against C/N0 over noise realisations made on the device: the batch dimension is the realisation.
+
+    One ChanMgr.Start at the true state X_ECEF of the handoff, with the grids centred on X_ECEF + init_delta (up to 8 entries, ECEF),
+    gives the window's parameters.  Per level c of cn0_dbhz (dB-Hz; every SV at amplitude synth.cn0_to_amp(c, sigma, fs)),
+    Synthesizer.windows makes n_real windows of S samples that differ only in the noise stream -- realisation r of level l draws
+    stream l n_real + r under `seed`, no nav-bit flip, no DC offset -- and one stage-1 update and one manifold update run over the
+    batch.  Nothing but the fixes leaves the device.  Returns one dict per level: cn0_dbhz, amp, fixes [n_real, 8] (the ML fix
+    zVal of every realisation), pos_index / vel_index [n_real], pos_out_of_window / vel_out_of_window [n_real], and the root mean
+    square errors against the truth rmse_enu [3], rmse_3d, rmse_clock (m), rmse_vel (3-D, m/s), rmse_drift (m/s); with
+    weighted_mean also mean_fixes [n_real, 8] and the same errors of the score-weighted mean under mean_rmse_*."""
+    from . import synth
+    truth = np.array(ho["X_ECEF"], dtype=np.float64).copy()
+    centre = truth.copy()
+    d0 = np.asarray(init_delta, dtype=np.float64)
+    centre[:d0.shape[0]] += d0
+    nfft = engine.carr_fft_len(S)
+    L, B = bank_half_widths(pos_grid, vel_grid, fs, nfft)
+    # the replica follows the truth and the grid its own centre: the banks have to reach across the offset between the two as well
+    L += int(np.ceil((np.linalg.norm(d0[:3]) + (abs(d0[3]) if d0.shape[0] > 3 else 0.0)) * fs / 299792458.0))
+    if d0.shape[0] > 4:
+        dv = np.zeros(4)
+        dv[:d0.shape[0] - 4] = d0[4:]
+        B += int(np.ceil((np.linalg.norm(dv[:3]) + abs(dv[3])) * (nfft / fs) * 1.57542e9 / 299792458.0))
+    L = L if lag_half_width is None else int(lag_half_width)
+    B = B if bin_half_width is None else int(bin_half_width)
+    n_real = int(n_real)
+    cm = engine.ChanMgr.from_handoff(ho, S / fs, K)
+    bcs = engine.BatchCorrScores(fs, samples_per_window=S, lag_half_width=L, bin_half_width=B, max_windows=n_real, max_channels=K)
+    bcm = engine.BatchCorrManifold(fs, S, nfft, pos_grid, vel_grid, LPower=lpower, lag_half_width=L, bin_half_width=B,
+                                   max_windows=n_real, max_channels=K, write_scores=False, weighted_mean=weighted_mean)
+    syn = None
+    out = []
+    try:
+        cm.Start(truth, centre, (0.0,))
+        cs, ce, bw = cm.outputs()
+        cs_b, ce_b, bw_b = np.tile(cs, (n_real, 1)), np.tile(ce, (n_real, 1)), np.tile(bw, n_real)
+        R = np.asarray(bw["enu2ecef"][0], dtype=np.float64).reshape(3, 3)
+        bcs.Start()
+        bcm.Start()
+        syn = engine.Synthesizer(fs, max_segments=n_real, max_channels=K)
+        iq_d = None
+
+        def rmse(fixes):
+            e = fixes - truth[None, :]
+            enu = e[:, :3] @ R                      # R maps ENU to ECEF: its transpose takes the error back
+            ms = lambda v: float(np.sqrt(np.mean(np.sum(np.square(v), axis=-1))))    # noqa: E731
+            return dict(rmse_enu=np.sqrt(np.mean(np.square(enu), axis=0)), rmse_3d=ms(enu), rmse_clock=ms(e[:, 3:4]),
+                        rmse_vel=ms(e[:, 4:7]), rmse_drift=ms(e[:, 7:8]))
+
+        for lev, c in enumerate(np.atleast_1d(np.asarray(cn0_dbhz, dtype=np.float64))):
+            amp = float(synth.cn0_to_amp(c, sigma, fs))
+            iq_d = syn.windows(S, cs_b, amp=amp, sigma=sigma, dc=(0.0, 0.0), flip=None, seed=seed, first_stream=lev * n_real, out=iq_d)
+            bcs.Update(iq_d, cs_b)
+            bcm.Update(bcs.CodeScores, bcs.CarrScores, bw_b, ce_b)
+            res = bcm.results()
+            fixes = np.stack([r["zVal"] for r in res])
+            row = dict(cn0_dbhz=float(c), amp=amp, fixes=fixes, pos_index=np.array([r["posIndex"] for r in res]),
+                       vel_index=np.array([r["velIndex"] for r in res]),
+                       pos_out_of_window=np.array([r["posOutOfWindow"] for r in res]),
+                       vel_out_of_window=np.array([r["velOutOfWindow"] for r in res]), **rmse(fixes))
+            if weighted_mean:
+                row["mean_fixes"] = np.stack([r["zValMean"] for r in res])
+                row.update({"mean_" + k: v for k, v in rmse(row["mean_fixes"]).items()})
+            out.append(row)
+    finally:
+        if syn is not None:
+            syn.close()
+        cm.Stop()
+        bcm.Stop()
+        bcs.Stop()
+    return out

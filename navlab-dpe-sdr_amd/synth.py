@@ -146,6 +146,17 @@ def gen_iq_record_chunks(seed, fs, n_samples, ch, nav_bits, amp=48.0, sigma=300.
         yield iq
 
 
+def cn0_to_amp(cn0_dbhz, sigma, fs):
+    """Carrier amplitude for a carrier-to-noise-density ratio in dB-Hz: with complex noise of standard deviation sigma per
+    component sampled at fs the noise density is N0 = 2 sigma^2 / fs, the carrier power C = amp^2, so C/N0 = amp^2 fs / (2 sigma^2)."""
+    return np.sqrt(2.0 * np.square(np.asarray(sigma, dtype=np.float64)) / fs * 10.0 ** (np.asarray(cn0_dbhz, dtype=np.float64) / 10.0))
+
+
+def amp_to_cn0(amp, sigma, fs):
+    """The inverse of cn0_to_amp: C/N0 in dB-Hz of a carrier of amplitude amp."""
+    return 10.0 * np.log10(np.square(np.asarray(amp, dtype=np.float64)) * fs / (2.0 * np.square(np.asarray(sigma, dtype=np.float64))))
+
+
 def rand_grid(seed, G, half=(110.0, 110.0, 110.0, 132.0)):
     """rngrid3-format random ENU-dt grid (SURVEY.md 8d iii): columns x,y,z,delta_t (m)."""
     rng = np.random.Generator(np.random.PCG64(seed))

@@ -14,6 +14,10 @@ it the centre always scores highest; only offsets beyond half a sample (60 m at 
 spread grid) reach another node.  The weighted mean sees the asymmetry of the two slopes and drifts towards the truth
 (~1.6 m/s with LPower 1).  Same arithmetic as the reference (parity tests); this script documents the behaviour.
 
+This script varies the initial offset over ONE noise realisation of the recording.  The other half of the reference's check -- RMSE
+against C/N0 over many noise realisations, each made on the device by engine.Synthesizer -- is scripts/monte_carlo_cn0.py
+(pipeline.run_monte_carlo).
+
     python scripts/monte_carlo.py [runs=8] [windows=60]
 """
 import os
