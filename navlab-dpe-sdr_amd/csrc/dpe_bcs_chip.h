@@ -69,13 +69,9 @@ __global__ __launch_bounds__(64, 4) void bcs_bank_chip_kernel(BcsParamBlock pb, 
     __shared__ __align__(16) float2 sRot[kSPL + 1];
     __shared__ float2 sList[64 + 8];   // boundaries of a round: {J, byte offset into sQ}
 
-    // Block -> (window, tile, SV), XCD-aware: workgroups are dealt round-robin to the 8 XCDs (block b -> XCD b % 8, observed;
-    // used for speed only), so the K blocks that read the SAME samples (one per SV of a tile) are given linear ids that
-    // are congruent mod 8 and consecutive on that XCD: one HBM fetch, K - 1 hits in the XCD's L2.
     const int lane = threadIdx.x;
-    const int slot = blockIdx.x >> 3, k = slot % K, tg = (slot / K) * 8 + (blockIdx.x & 7);
-    if (tg >= nBlk * nW) return;
-    const int w = tg / nBlk, blk = tg - w * nBlk;
+    int k, w, blk;   // Block -> (window, tile, SV), XCD-aware
+    if (!block_map(blockIdx.x, K, nBlk, nW, k, w, blk)) return;
     (void)pb;
     const BcsChanDev ch = params_ptr(chan, inl)[(size_t)w * K + k];
     const int8_t *chips = chipTable + (ch.prn - 1) * 1024;
@@ -95,9 +91,7 @@ __global__ __launch_bounds__(64, 4) void bcs_bank_chip_kernel(BcsParamBlock pb, 
     sQ[lane] = make_float2(0.f, 0.f);
     if (lane == 0) sQ[kPad] = make_float2(0.f, 0.f);
     if (lane <= kSPL) {
-        double ph = (double)lane * ch.carrStep;
-        ph -= floor(ph);
-        const f2 t = wipe_seed((float)ph);
+        const f2 t = wipe_seed_at((double)lane * ch.carrStep);
         sRot[lane] = make_float2(t.x, t.y);
     }
     float2 *momOut = mom + ((((size_t)w * K + k) * 2) * nBlk + blk) * kNMom;   // [side][nBlk][kNMom]
@@ -138,14 +132,7 @@ __global__ __launch_bounds__(64, 4) void bcs_bank_chip_kernel(BcsParamBlock pb, 
     int curSide = 0, flushed = 0;
     auto flush = [&](int side) {   // reduce the lanes' moment sums and store the (tile, side) block
         flushed |= 1 << side;
-        float mm[2 * kNMom];
-#pragma unroll
-        for (int p = 0; p < kNMom; ++p) { mm[2 * p] = M[p].x; mm[2 * p + 1] = M[p].y; }
-        dpp_sum_lane63(mm);
-        if (lane == 63) {
-#pragma unroll
-            for (int p = 0; p < kNMom; ++p) momOut[side * momSide + p] = make_float2(mm[2 * p], mm[2 * p + 1]);
-        }
+        moment_set_reduce_store<kNMom>(momOut + side * momSide, M, lane);
 #pragma unroll
         for (int p = 0; p < kNMom; ++p) M[p] = f2{0.f, 0.f};
     };
@@ -215,7 +202,7 @@ __global__ __launch_bounds__(64, 4) void bcs_bank_chip_kernel(BcsParamBlock pb, 
         }
         if (t + 1 < tpb && pass + 1 < nPass) fetch(n0 + kPass);
         double ph = fma((double)n0, ch.carrStep, ch.ri);
-        ph -= floor(ph);
+        ph -= floor(ph);   // restates wipe_seed_at
         const f2 wl = wipe_seed((float)ph);
         const f2 tot = cmul(wl, u[kSPL - 1]);
         float incRe = tot.x, incIm = tot.y;
@@ -324,7 +311,7 @@ __global__ __launch_bounds__(64, 4) void bcs_bank_chip_kernel(BcsParamBlock pb, 
                     // DC-mean term: mean * sum_{n in chip} {1, d} wipe[n],  d = n - centre
                     double pc = fma(nc, ch.carrStep, ch.ri);
                     pc -= floor(pc);
-                    const f2 wc = wipe_seed((float)pc);
+                    const f2 wc = wipe_seed((float)pc);   // restates wipe_seed_at
                     float G0 = len == minLen + 1 ? G0a : G0b, G1 = len == minLen + 1 ? G1a : G1b;
                     if (len != minLen + 1 && len != minLen + 2) mean_sums((float)len, G0, G1);   // chips clamped at the pass ends
                     const f2 mw = cmul(meanv, wc);

@@ -121,7 +121,7 @@ __device__ __forceinline__ void ride_sum_block(const int16_t *__restrict__ iq, l
     int hi = b == nSumBlk - 1 ? n4 : (int)(((long long)(b + 1) * Lt + 3) >> 2);
     if (hi > n4) hi = n4;
     int sI = 0, sQ = 0;   // a block adds < 32768 samples
-    auto add4 = [&](const int4 v) {
+    auto add4 = [&](const int4 v) {   // restates iq_add4
         sI += (short)(v.x & 0xFFFF) + (short)(v.y & 0xFFFF) + (short)(v.z & 0xFFFF) + (short)(v.w & 0xFFFF);
         sQ += (v.x >> 16) + (v.y >> 16) + (v.z >> 16) + (v.w >> 16);
     };
@@ -146,7 +146,7 @@ __device__ __forceinline__ void ride_sum_block(const int16_t *__restrict__ iq, l
         for (int j = 0; j < kRideLoads; ++j) add4(v[j]);
     }
     if (b == nSumBlk - 1)
-        for (int m = (n4 << 2) + lane; m < S; m += 64) { const int v = x[m]; sI += (short)(v & 0xFFFF); sQ += v >> 16; }
+        for (int m = (n4 << 2) + lane; m < S; m += 64) { const int v = x[m]; sI += (short)(v & 0xFFFF); sQ += v >> 16; }   // restates iq_add
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         sI += __shfl_xor(sI, off, 64);
@@ -192,7 +192,7 @@ __device__ __forceinline__ void ride_window_mean(const unsigned long long *__res
             int sI = 0, sQ = 0;
             const int hi = n0 + 64 * 256 < n4 ? n0 + 64 * 256 : n4;
             for (int n = n0 + lane; n < hi; n += 64) {
-                const int4 q = x4[n];
+                const int4 q = x4[n];   // restates iq_add4
                 sI += (short)(q.x & 0xFFFF) + (short)(q.y & 0xFFFF) + (short)(q.z & 0xFFFF) + (short)(q.w & 0xFFFF);
                 sQ += (q.x >> 16) + (q.y >> 16) + (q.z >> 16) + (q.w >> 16);
             }
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(64, DPE_C2_WAVES) void bcs_bank_chip2_kernel(BcsPar
             return;
         }
     }
-    const int slot = bx >> 3, k = slot % K, tg = (slot / K) * 8 + (bx & 7);
+    const int slot = bx >> 3, k = slot % K, tg = (slot / K) * 8 + (bx & 7);   // restates block_map
     if (tg >= nBlk * nW) return;
     const int w = tg / nBlk, blk = tg - w * nBlk;
     (void)pb;
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(64, DPE_C2_WAVES) void bcs_bank_chip2_kernel(BcsPar
     {
         const double a = lane < 26 ? (double)lane : (lane == 26 ? 0.5 * (double)(L1 - 1) - (double)CI : 0.5 * (double)L1 - (double)CI);
         double ph = a * ch.carrStep;
-        ph -= floor(ph);
+        ph -= floor(ph);   // restates wipe_seed_at
         const f2 t = wipe_seed((float)ph);   // lane j: T_j; lanes 26, 27: the two centre twiddles
 #pragma unroll
         for (int j = 0; j <= CI; ++j) tw[j] = f2{readlane_f(t.x, j), readlane_f(t.y, j)};
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(64, DPE_C2_WAVES) void bcs_bank_chip2_kernel(BcsPar
     int curSide = 0, flushed = 0;
     auto flush = [&](int side) {   // reduce the lanes' moment sums and store the (tile, side) block
         flushed |= 1 << side;
-        float mm[2 * kNMom];
+        float mm[2 * kNMom];   // restates moment_set_reduce_store
 #pragma unroll
         for (int p = 0; p < kNMom; ++p) { mm[2 * p] = M[p].x; mm[2 * p + 1] = M[p].y; }
         dpp_sum_lane63(mm);
@@ -555,7 +555,7 @@ __global__ __launch_bounds__(64, DPE_C2_WAVES) void bcs_bank_chip2_kernel(BcsPar
         __builtin_amdgcn_s_setprio(2);
         // ---- 2. chip offsets: wipe-off at the chip's frame origin, 64-lane scan of the chip totals, Q -> LDS (centred)
         double ph = fma((double)((own ? e : 0) + CI), ch.carrStep, ch.ri);   // wipe-off at the lane frame's origin
-        ph -= floor(ph);
+        ph -= floor(ph);   // restates wipe_seed_at
         const f2 wl = wipe_seed((float)ph);
         f2 tot = cmul(wl, run);
         tot = own ? tot : f2{0.f, 0.f};
@@ -611,7 +611,7 @@ __global__ __launch_bounds__(64, DPE_C2_WAVES) void bcs_bank_chip2_kernel(BcsPar
             } else {
                 double pc = fma((double)(own ? e : 0) + 0.5 * (double)(len - 1), ch.carrStep, ch.ri);
                 pc -= floor(pc);
-                wc = wipe_seed((float)pc);
+                wc = wipe_seed((float)pc);   // restates wipe_seed_at
                 mean_sums(lenf, G0, G1);
             }
             const f2 mw = cmul(meanv, wc);

@@ -26,9 +26,7 @@ __global__ __launch_bounds__(256) void bcs_fft_prep_code_kernel(const int16_t *_
     const size_t plane = (size_t)nW * K * S, row = ((size_t)wl * K + k) * S;
     for (int n = blockIdx.x * 256 + threadIdx.x; n < S; n += gridDim.x * 256) {
         const int v = x[n];
-        double ph = carr_phase<TABLE>(ch, tT, n);
-        ph -= floor(ph);
-        const f2 wv = wipe_seed((float)ph);
+        const f2 wv = wipe_seed_at(carr_phase<TABLE>(ch, tT, n));
         const f2 b = cmul(f2{(float)(short)(v & 0xFFFF), (float)(v >> 16)}, wv);
         const int ci = ((int)floor(code_phase<TABLE>(ch, tT, n))) % kLCA;
         const float r = (float)chips[ci];
@@ -95,9 +93,7 @@ __global__ __launch_bounds__(256) void bcs_fft_prep_carr_kernel(const int16_t *_
         float2 c = make_float2(0.f, 0.f);
         if (n < S) {
             const int v = x[n];
-            double ph = carr_phase<TABLE>(ch, tT, (int)n);
-            ph -= floor(ph);
-            const f2 wv = wipe_seed((float)ph);
+            const f2 wv = wipe_seed_at(carr_phase<TABLE>(ch, tT, (int)n));
             const int ci = ((int)floor(code_phase<TABLE>(ch, tT, (int)n))) % kLCA;
             const float r = (float)chips[ci] * ((ch.hasFlip && n >= ch.idxNext) ? sgnY : 1.f);
             const f2 b = cmul(f2{(float)(short)(v & 0xFFFF) - mRe, (float)(v >> 16) - mIm}, wv);   // (raw - mean) wipe (:480, :440-448)
