@@ -1123,6 +1123,75 @@ int dpe_syn_windows(dpe_syn *h, int16_t *out_dev, int64_t strideInt16, int32_t n
 int dpe_syn_record(dpe_syn *h, int16_t *out_dev, int64_t firstSample, int64_t nSamples, int32_t nChan, const dpe_chan_start *chan_host,
                    const double *amp, const dpe_syn_signal *sig, uint64_t streamId, dpe_stream_t stream);
 
+/* ------------------------------------------------------------------ Collective detection ---- */
+/* Position-domain acquisition (csrc/dpe_cd.hip, csrc/dpe_cd_plan.h): every SV's delay x Doppler surface, as
+ * dpe_acq_surface leaves it (float [nRows][nBins][M], M = samples per code period), summed over one grid of position offset x
+ * receiver clock bias x receiver clock drift, and one arg-max over the sum.  No counterpart in the reference, which acquires
+ * satellite by satellite (correlator.py:53-103).  With tau_k(p) = delay0_k + (|sat_k - (p0 + R d_p)| - |sat_k - p0|) fs / c in
+ * fp64, u = tau_k(p) + m, i0 = floor(u) mod M, i1 = (i0 + 1) mod M, f = u - floor(u) and b_k(j) = round_half_even(bin0_k) + j,
+ *   score(p, m, j) = sum_k (1 - f) s[row_k][b_k(j)][i0] + f s[row_k][b_k(j)][i1]          (fp32; 0 where b_k(j) leaves the raster)
+ * for m = 0 .. M-1 (clock bias, samples) and j = -J .. +J (clock drift, bins).  Limits (refused with a message where they can be
+ * checked): no ionosphere or troposphere; the Doppler's change over the grid is ignored, so a grid whose farthest point times
+ * DPE_CD_DOPPLER_HZ_PER_KM exceeds half a bin step is refused at create; the coarse receive time has to be good to ~37 ms at
+ * 2.5 Msps (differential range rate x time error below half a sample), which no call can check. */
+#define DPE_CD_MAX_SV 16
+#define DPE_CD_MAX_DRIFT 32
+#define DPE_CD_DOPPLER_HZ_PER_KM 1.1   /* |d Doppler / d position| <= v / (lambda r): 4 km/s, 0.1903 m, 20 000 km */
+typedef struct dpe_cd dpe_cd;
+typedef struct dpe_cd_config {
+    int32_t M;                    /* delays per surface row = samples per code period, 16..32768 */
+    int32_t nBins;                /* Doppler bins per surface row block: binStartHz + i binStepHz */
+    int32_t maxSv;                /* 1..DPE_CD_MAX_SV */
+    int32_t driftHalfWidth;       /* J, 0..DPE_CD_MAX_DRIFT: clock-drift hypotheses -J..+J, in whole bins */
+    int32_t nPoints;              /* P, 1..65536 */
+    int32_t reserved;
+    const double *enuGrid;        /* host [nPoints][3]: position offsets, ENU metres about the p0 of an update */
+    double samplingFrequency;
+    double binStartHz;
+    double binStepHz;
+    double dopplerSign;           /* +1 / -1, as dpe_acq_config */
+} dpe_cd_config;
+typedef struct dpe_cd_sv {        /* one SV of an update: what dpe_cd_predict fills, or the caller */
+    int32_t prn;
+    int32_t row;                  /* its row of the surface */
+    double sat[3];                /* ECEF at transmit time, rotated into the receive-time frame */
+    double delay0;                /* samples, [0, M): ((|sat - p0| / c - dt_sv) mod 1 ms) fs */
+    double bin0;                  /* fractional bin index of its Doppler at p0 */
+    double range0;                /* |sat - p0|, metres (informational: the update recomputes it) */
+    double dopplerHz;             /* binStartHz + bin0 binStepHz (informational) */
+} dpe_cd_sv;
+typedef struct dpe_cd_result {
+    int32_t point, m, j;          /* first maximum in (point, j, m) index order */
+    int32_t binsOutOfRange;       /* (SV, j) pairs whose bin lies outside the raster (they contribute 0) */
+    int32_t nSv, reserved;
+    double score;
+    double fixEcef[3];            /* p0 + R d_point */
+    double clockBiasM;            /* m / fs c: the clock bias modulo 1 ms, metres */
+    double clockDriftMps;         /* -dopplerSign j binStepHz c / F_L1: a clock running fast lowers every Doppler */
+} dpe_cd_result;
+typedef struct dpe_cd_sv_result { /* per SV at the arg-max, the fields of dpe_acq_result that dpe_acq_fine and the tracker read */
+    int32_t prn, found;           /* found: its bin lies inside the raster at j */
+    int32_t maxCodeIdx;           /* round(tau_k(point) + m) mod M */
+    int32_t maxDoppIdx;           /* b_k(j) */
+    double rc, fc, fi;            /* from the index pair as dpe_acq_results forms them */
+    double peak;                  /* the SV's own term of the score */
+} dpe_cd_sv_result;
+int dpe_cd_create(const dpe_cd_config *cfg, dpe_cd **out);
+int dpe_cd_destroy(dpe_cd *h);
+/* Host, fp64: sv[k] from ephemerides eph[nSv][DPE_NAV_EPH_DOUBLES], PRNs, surface rows, the a-priori ECEF position p0[3] and the
+ * coarse GPS time of the window's first sample (seconds of week).  Of cfg only M, samplingFrequency, the bin raster and dopplerSign
+ * are read (enuGrid may be NULL); no device is needed. */
+int dpe_cd_predict(const dpe_cd_config *cfg, int32_t nSv, const double *eph, const int32_t *prn, const int32_t *row, const double *p0,
+                   double rxTime, dpe_cd_sv *sv /* [nSv] */);
+/* One scan of surface_dev (device float [nRows][nBins][M]) about p0[3] with the row-major ENU -> ECEF matrix enu2ecef[9].
+ * Asynchronous on `stream`; sv_host may be reused as soon as the call returns. */
+int dpe_cd_update(dpe_cd *h, const float *surface_dev, int32_t nRows, const double *p0, const double *enu2ecef, int32_t nSv,
+                  const dpe_cd_sv *sv_host, dpe_stream_t stream);
+/* Synchronises with the last update's stream.  sv may be NULL. */
+int dpe_cd_results(dpe_cd *h, dpe_cd_result *res, dpe_cd_sv_result *sv /* [nSv] */);
+/* The position-domain map of the last update, device-resident: per point the best score over (j, m) and that (j, m). */
+int dpe_cd_map(dpe_cd *h, const float **score_dev /* [nPoints] */, const int32_t **jm_dev /* [nPoints][2] */);
+
 /* Timing helper for bench.py: HIP events on the stream the kernels run on. */
 int dpe_event_create(void **ev);
 int dpe_event_record(void *ev, dpe_stream_t stream);

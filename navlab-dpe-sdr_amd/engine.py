@@ -47,6 +47,7 @@ EXPORTS = [
     "dpe_vt_create", "dpe_vt_destroy", "dpe_vt_set_ephemerides", "dpe_vt_init", "dpe_vt_init_from_trk", "dpe_vt_track", "dpe_vt_read_log",
     "dpe_vt_read_corr", "dpe_vt_state", "dpe_vt_dev_status", "dpe_vt_filter_step_host",
     "dpe_syn_create", "dpe_syn_destroy", "dpe_syn_set_nav_bits", "dpe_syn_windows", "dpe_syn_record",
+    "dpe_cd_create", "dpe_cd_destroy", "dpe_cd_predict", "dpe_cd_update", "dpe_cd_results", "dpe_cd_map",
 ]
 
 
@@ -1454,7 +1455,7 @@ class Acquisition:
         self.S, self.fs = int(samples_per_window), float(SamplingFrequency)
         self.N = int(round(self.S / self.fs / 1e-3))
         self.M = self.S // self.N
-        self.prns, self.bins = [int(p) for p in prns], bins_hz
+        self.prns, self.bins, self.ds = [int(p) for p in prns], bins_hz, float(ds)
         cfg = AcqConfig(self.S, self.N, bins_hz.size, len(self.prns), self.MODES[mode], int(prn_chunk), self.fs,
                         float(bins_hz[0]), step, float(ds), (C.c_int32 * 37)(*self.prns), 0)
         self._h = C.c_void_p(None)
@@ -2066,6 +2067,128 @@ class Synthesizer:
     def close(self):
         if self._h:
             lib().dpe_syn_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:            # at interpreter shutdown module globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+class CdConfig(C.Structure):        # dpe_cd_config
+    _fields_ = [("M", C.c_int32), ("nBins", C.c_int32), ("maxSv", C.c_int32), ("driftHalfWidth", C.c_int32), ("nPoints", C.c_int32),
+                ("reserved", C.c_int32), ("enuGrid", C.POINTER(C.c_double)), ("samplingFrequency", C.c_double),
+                ("binStartHz", C.c_double), ("binStepHz", C.c_double), ("dopplerSign", C.c_double)]
+
+
+class CdSv(C.Structure):            # dpe_cd_sv
+    _fields_ = [("prn", C.c_int32), ("row", C.c_int32), ("sat", C.c_double * 3), ("delay0", C.c_double), ("bin0", C.c_double),
+                ("range0", C.c_double), ("dopplerHz", C.c_double)]
+
+
+class CdResult(C.Structure):        # dpe_cd_result
+    _fields_ = [("point", C.c_int32), ("m", C.c_int32), ("j", C.c_int32), ("binsOutOfRange", C.c_int32), ("nSv", C.c_int32),
+                ("reserved", C.c_int32), ("score", C.c_double), ("fixEcef", C.c_double * 3), ("clockBiasM", C.c_double),
+                ("clockDriftMps", C.c_double)]
+
+
+class CdSvResult(C.Structure):      # dpe_cd_sv_result
+    _fields_ = [("prn", C.c_int32), ("found", C.c_int32), ("maxCodeIdx", C.c_int32), ("maxDoppIdx", C.c_int32),
+                ("rc", C.c_double), ("fc", C.c_double), ("fi", C.c_double), ("peak", C.c_double)]
+
+
+def cd_predict(SamplingFrequency, M, bins_hz, eph, prns, rows, p0, rx_time, ds=1.0):
+    """Host, fp64, no device (dpe_cd_predict): per SV the delay and the fractional Doppler bin at p0 (ECEF) for the coarse GPS time
+    rx_time of the window's first sample, from ephemerides [K, 21] (handoff.EPH_FIELDS' order).  One dict per SV (prn, row, sat,
+    delay0, bin0, range0, doppler_hz), as CollectiveDetector.update takes them."""
+    bins_hz = np.asarray(bins_hz, dtype=np.float64)
+    step = float(bins_hz[1] - bins_hz[0]) if bins_hz.size > 1 else 0.0
+    cfg = CdConfig(int(M), bins_hz.size, 1, 0, 1, 0, None, float(SamplingFrequency), float(bins_hz[0]), step, float(ds))
+    eph = np.ascontiguousarray(eph, dtype=np.float64).reshape(-1, 21)
+    prns, rows = np.ascontiguousarray(prns, dtype=np.int32), np.ascontiguousarray(rows, dtype=np.int32)
+    p0 = np.ascontiguousarray(np.asarray(p0, dtype=np.float64)[:3])
+    K = prns.size
+    assert eph.shape[0] == K == rows.size
+    out = (CdSv * max(K, 1))()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _check(lib().dpe_cd_predict(C.byref(cfg), C.c_int32(K), eph.ctypes.data_as(dp), prns.ctypes.data_as(ip), rows.ctypes.data_as(ip),
+                                p0.ctypes.data_as(dp), C.c_double(float(rx_time)), out))
+    return [dict(prn=r.prn, row=r.row, sat=np.array(r.sat[:]), delay0=r.delay0, bin0=r.bin0, range0=r.range0,
+                 doppler_hz=r.dopplerHz) for r in out[:K]]
+
+
+class CollectiveDetector:
+    """Collective detection (dpe_cd_*, csrc/dpe_cd.hip): the delay x Doppler surfaces of all SVs, as an
+    Acquisition leaves them on the device, summed over position offset x clock bias x clock drift, one arg-max over the sum.
+    enu_grid: [P, 3] position offsets in ENU metres about the p0 of an update; bins_hz: the surfaces' Doppler raster."""
+    MAX_SV, MAX_DRIFT = 16, 32
+
+    def __init__(self, SamplingFrequency, M, bins_hz, enu_grid, drift_half_width=0, max_sv=16, ds=1.0):
+        bins_hz = np.asarray(bins_hz, dtype=np.float64)
+        step = float(bins_hz[1] - bins_hz[0]) if bins_hz.size > 1 else 0.0
+        assert bins_hz.size == 1 or np.allclose(np.diff(bins_hz), step), "bins must be equally spaced"
+        self.fs, self.M, self.bins, self.J = float(SamplingFrequency), int(M), bins_hz, int(drift_half_width)
+        self.grid = np.ascontiguousarray(enu_grid, dtype=np.float64).reshape(-1, 3)
+        self.P, self.max_sv, self.n_sv, self.ds = self.grid.shape[0], int(max_sv), 0, float(ds)
+        cfg = CdConfig(self.M, bins_hz.size, self.max_sv, self.J, self.P, 0, self.grid.ctypes.data_as(C.POINTER(C.c_double)), self.fs,
+                       float(bins_hz[0]), step, float(ds))
+        self._h = C.c_void_p(None)
+        _check(lib().dpe_cd_create(C.byref(cfg), C.byref(self._h)))
+        score, jm = C.c_void_p(), C.c_void_p()
+        _check(lib().dpe_cd_map(self._h, C.byref(score), C.byref(jm)))
+        self.MapScore, self.MapJM = score.value, jm.value
+
+    @staticmethod
+    def sv_array(sv):
+        """List of dicts (prn, row, sat, delay0, bin0) -> the C array; a C array passes through."""
+        if not isinstance(sv, (list, tuple)):
+            return sv
+        a = (CdSv * len(sv))()
+        for r, c in zip(a, sv):
+            r.prn, r.row, r.delay0, r.bin0 = int(c["prn"]), int(c["row"]), float(c["delay0"]), float(c["bin0"])
+            r.sat[0], r.sat[1], r.sat[2] = (float(v) for v in c["sat"])
+            r.range0, r.dopplerHz = float(c.get("range0", 0.0)), float(c.get("doppler_hz", 0.0))
+        return a
+
+    def predict(self, eph, prns, rows, p0, rx_time):
+        """cd_predict with the handle's sampling frequency, M, bin raster and Doppler sign."""
+        return cd_predict(self.fs, self.M, self.bins, eph, prns, rows, p0, rx_time, ds=self.ds)
+
+    def update(self, acq_or_surface, sv, p0, enu2ecef, n_rows=None, stream=None):
+        """One scan, asynchronous.  acq_or_surface: an Acquisition after search (its surface and row count are taken), or a
+        device float32 array [n_rows, nBins, M] (torch tensor, or a raw pointer with n_rows given)."""
+        if isinstance(acq_or_surface, Acquisition):
+            surf, n_rows = acq_or_surface.Surface, len(acq_or_surface.prns)
+        else:
+            surf = acq_or_surface
+            if n_rows is None:
+                n_rows = int(acq_or_surface.shape[0])
+        a = self.sv_array(sv)
+        p0 = np.ascontiguousarray(np.asarray(p0, dtype=np.float64)[:3])
+        R = np.ascontiguousarray(enu2ecef, dtype=np.float64).reshape(9)
+        dp = C.POINTER(C.c_double)
+        _check(lib().dpe_cd_update(self._h, _ptr(surf), C.c_int32(int(n_rows)), p0.ctypes.data_as(dp), R.ctypes.data_as(dp),
+                                   C.c_int32(len(a)), a, _stream(stream)))
+        self.n_sv = len(a)
+
+    def results(self):
+        """Synchronises.  -> (fix dict, per-SV list in Acquisition.results()' shape: Acquisition.fine takes it as it is)."""
+        res, sv = CdResult(), (CdSvResult * max(self.n_sv, 1))()
+        _check(lib().dpe_cd_results(self._h, C.byref(res), sv))
+        fix = dict(point=res.point, m=res.m, j=res.j, score=res.score, bins_out_of_range=res.binsOutOfRange,
+                   fix_ecef=np.array(res.fixEcef[:]), clock_bias_m=res.clockBiasM, clock_drift_mps=res.clockDriftMps)
+        return fix, [dict(prn=r.prn, found=bool(r.found), max_code_idx=r.maxCodeIdx, max_dopp_idx=r.maxDoppIdx, rc=r.rc, fc=r.fc,
+                          fi=r.fi, peak=r.peak) for r in sv[:self.n_sv]]
+
+    def read_map(self, stream=None):
+        """The position-domain map of the last update: (score float32 [P], jm int32 [P, 2]) -- per point the best score over
+        (j, m) and that (j, m)."""
+        return (d2h(self.MapScore, self.P * 4, np.float32, stream), d2h(self.MapJM, self.P * 8, np.int32, stream).reshape(self.P, 2))
+
+    def close(self):
+        if self._h:
+            lib().dpe_cd_destroy(self._h)
             self._h = C.c_void_p(None)
 
     def __del__(self):

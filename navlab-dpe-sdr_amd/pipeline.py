@@ -530,3 +530,32 @@ def run_monte_carlo(ho, fs, S, K, pos_grid, vel_grid, cn0_dbhz, n_real, seed, in
         bcm.Stop()
         bcs.Stop()
     return out
+
+
+def collective_detection(acq, samples, eph, prns, p0, rx_time, enu_grid, drift_half_width=0, detector=None, stream=None):
+    """Weak-signal cold start: acq.search on `samples` (device int16, one window), one collective scan of its surfaces over
+    enu_grid x clock bias x clock drift about the a-priori ECEF position p0 at the coarse GPS time rx_time, then acq.fine on the
+    per-SV results.  prns: the SVs to combine, each one of acq.prns; eph [K, 21] in their order.  Returns a dict: `fix`
+    (CollectiveDetector.results()' first part), `coarse` (per SV of acq.prns, Acquisition.results()' shape: the collective entry
+    for the SVs combined, the ordinary one for the others), `tracker_init` (Acquisition.fine's output with `found`, for
+    ScalarTracker.set_params), `ordinary` (acq.results()) and `sv` (the predictions).  detector: a CollectiveDetector to reuse."""
+    from . import synth
+    prns = [int(p) for p in prns]
+    rows = [acq.prns.index(p) for p in prns]
+    cd = detector or engine.CollectiveDetector(acq.fs, acq.M, acq.bins, enu_grid, drift_half_width=drift_half_width,
+                                               max_sv=min(max(len(prns), 1), engine.CollectiveDetector.MAX_SV), ds=acq.ds)
+    try:
+        sv = cd.predict(eph, prns, rows, p0, rx_time)
+        acq.search(samples, stream)
+        ordinary = acq.results(stream)
+        cd.update(acq, sv, p0, synth.enu2ecef_matrix(p0), stream=stream)
+        fix, per_sv = cd.results()
+    finally:
+        if detector is None:
+            cd.close()
+    coarse = [dict(r) for r in ordinary]
+    for row, r in zip(rows, per_sv):
+        coarse[row] = dict(ordinary[row], **r)
+    fine = acq.fine(samples, coarse, stream)
+    init = [dict(f, found=c["found"]) for f, c in zip(fine, coarse)]
+    return dict(fix=fix, coarse=coarse, tracker_init=init, ordinary=ordinary, sv=sv)

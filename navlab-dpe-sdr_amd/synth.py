@@ -189,3 +189,26 @@ def write_grid_csv(path, grid):
     with open(path, "w", newline="") as f:
         for row in grid:
             f.write("%.17g,%.17g,%.17g,%.17g\r\n" % tuple(row))
+
+
+def enu2ecef_matrix(p0):
+    """Row-major ENU -> ECEF rotation [3, 3] at the ECEF position p0: the arithmetic of csrc/dpe_chm_dev.h's enu2ecef_matrix
+    (CHM_Dev_ECEF2LL_Rad + CHM_Dev_R_ENU2ECEF, cuchanmgr.cu:37-73) in numpy."""
+    a, b, e, ep = 6378137.0, 6356752.314245, 0.08181919084262149, 0.08209443794969568
+    x, y, z = (float(v) for v in np.asarray(p0, dtype=np.float64)[:3])
+    p = np.sqrt(x * x + y * y)
+    th = np.arctan2(z * a, p * b)
+    lat = np.arctan2(z + ep ** 2 * b * np.sin(th) ** 3, p - e ** 2 * a * np.cos(th) ** 3)
+    lon = np.arctan2(y, x)
+    sa, ca, so, co = np.sin(lat), np.cos(lat), np.sin(lon), np.cos(lon)
+    return np.array([[-so, -sa * co, ca * co], [co, -sa * so, ca * so], [0.0, ca, sa]])
+
+
+def enu_disc_grid(radius_m, step_m, up_m=0.0):
+    """Horizontal ENU grid for collective detection: the points of a square lattice of spacing step_m (the origin among them)
+    that lie within radius_m of the origin, all at height up_m; rows (east, north, up), east slowest."""
+    n = int(np.floor(radius_m / step_m + 1e-9))
+    ax = step_m * np.arange(-n, n + 1, dtype=np.float64)
+    E, N = np.meshgrid(ax, ax, indexing="ij")
+    keep = E * E + N * N <= radius_m * radius_m * (1.0 + 1e-12)
+    return np.stack([E[keep], N[keep], np.full(int(keep.sum()), float(up_m))], axis=1)
