@@ -1192,6 +1192,67 @@ int dpe_cd_results(dpe_cd *h, dpe_cd_result *res, dpe_cd_sv_result *sv /* [nSv] 
 /* The position-domain map of the last update, device-resident: per point the best score over (j, m) and that (j, m). */
 int dpe_cd_map(dpe_cd *h, const float **score_dev /* [nPoints] */, const int32_t **jm_dev /* [nPoints][2] */);
 
+/* ------------------------------------------------------------------ Front end ---- */
+/* Raw record bytes in a device buffer to interleaved int16 I/Q at zero IF and at fs_out = fs_in / D, written straight into a device
+ * buffer that every other stage takes as it is (csrc/dpe_fe.hip, csrc/dpe_fe_plan.h): unpack, mix to baseband,
+ * low-pass, decimate.  No counterpart in the reference, whose file reader assumes zero-IF complex samples at the processing rate
+ * (pygnss rawfile.py:140-158).  For the output index m, counted from the start of the record, in exact arithmetic
+ *   y[m] = gain sum_{t < T} h[t] z[m D + t - T0],   T0 = (T - 1) / 2, T odd
+ *   z[n] = x[n] exp(-2 pi j ((n delta) mod 2^32) / 2^32)   for 0 <= n < recordLength, else 0
+ *   delta = rint(f_IF / fs_in 2^32) mod 2^32
+ * and the output clip(rint(y), -32768, 32767) per component (round to nearest even), or y itself as fp32 pairs.  Output m sits at
+ * the time of input sample m D: the stage does not shift code phase.  The phase of input sample n depends on n alone.  The device
+ * forms y in fp32 from the modulated taps gain h[t] exp(-j phase(t)) (fp64 on the host, held as fp32) and one rotation per output
+ * from the integer phase word; an output's arithmetic depends on m alone, so any split of an output range into calls gives the
+ * bytes of one call, in both output formats.
+ * x[n] by input format: I16C int16 I, Q; I8C int8 I, Q; I16R real int16; I8R real int8; ARGPI4 one byte per sample whose low three
+ * bits k give exp(j pi k / 4); P2R 2-bit real, four samples per byte, sample j of a byte in bits 2j, 2j+1, value levels[code];
+ * P2C 2-bit complex, two samples per byte, I in bits 4j, 4j+1, Q in bits 4j+2, 4j+3, values levels[code]. */
+#define DPE_FE_I16C 0
+#define DPE_FE_I8C 1
+#define DPE_FE_I16R 2
+#define DPE_FE_I8R 3
+#define DPE_FE_ARGPI4 4
+#define DPE_FE_P2R 5
+#define DPE_FE_P2C 6
+#define DPE_FE_OUT_I16 0
+#define DPE_FE_OUT_F32 1
+typedef struct dpe_fe dpe_fe;
+typedef struct dpe_fe_config {
+    double samplingFrequency;     /* fs_in, Hz */
+    double intermediateFrequency; /* f_IF, Hz, |f_IF| <= fs_in; negative wraps */
+    double gain;
+    double levels[4];             /* P2R / P2C: the value of each 2-bit code (e.g. -3, -1, +1, +3) */
+    int32_t format;               /* DPE_FE_I16C .. DPE_FE_P2C */
+    int32_t outputFormat;         /* DPE_FE_OUT_I16 / DPE_FE_OUT_F32 */
+    int32_t decimation;           /* D, 1..64 */
+    int32_t nTaps;                /* T, odd, 1..1023 */
+} dpe_fe_config;
+typedef struct dpe_fe_info_t {
+    double realisedIF;            /* delta fs_in / 2^32 in (-fs_in / 2, fs_in / 2]: within fs_in / 2^33 of the request */
+    double outputFrequency;       /* fs_in / D */
+    int64_t delta;                /* the phase increment per input sample, 0 .. 2^32 - 1 */
+    int32_t groupDelay;           /* T0 */
+    int32_t bytesNum, bytesDen;   /* bytes per input sample = bytesNum / bytesDen */
+    int32_t tileOutputs;          /* outputs per block of the launch geometry */
+    int32_t ldsBytes;             /* the staged tile of a block */
+    int32_t reserved;
+} dpe_fe_info_t;
+/* taps: host [cfg->nTaps], fp64; gain h[t] and its modulated form are held as fp32.  Everything outside the limits is refused
+ * with a message before anything is allocated. */
+int dpe_fe_create(const dpe_fe_config *cfg, const double *taps, dpe_fe **out);
+int dpe_fe_destroy(dpe_fe *h);
+int dpe_fe_info(const dpe_fe *h, dpe_fe_info_t *info);
+/* Outputs [outFirst, outFirst + outCount) into out_dev[0 ..) (int16 or float pairs) from raw_dev, which holds the input samples
+ * [rawFirstSample, rawFirstSample + rawCount) of the record (a packed format's rawFirstSample on a byte boundary).  recordLength:
+ * samples at and beyond it count as zero, as the samples before 0 do (-1: no end).  The outputs need the input samples
+ * [outFirst D - T0, (outFirst + outCount - 1) D + T - 1 - T0] cut to [0, recordLength); the call is refused when the buffer does
+ * not hold them all.  The handle keeps nothing of the record between calls.  Asynchronous on `stream`, like dpe_syn_record. */
+int dpe_fe_convert(dpe_fe *h, const void *raw_dev, int64_t rawFirstSample, int64_t rawCount, int64_t recordLength, void *out_dev,
+                   int64_t outFirst, int64_t outCount, dpe_stream_t stream);
+/* Output components the last int16 convert call clipped to a rail.  Synchronises with that call's stream. */
+int dpe_fe_clipped(dpe_fe *h, int64_t *count);
+
 /* Timing helper for bench.py: HIP events on the stream the kernels run on. */
 int dpe_event_create(void **ev);
 int dpe_event_record(void *ev, dpe_stream_t stream);

@@ -48,6 +48,7 @@ EXPORTS = [
     "dpe_vt_read_corr", "dpe_vt_state", "dpe_vt_dev_status", "dpe_vt_filter_step_host",
     "dpe_syn_create", "dpe_syn_destroy", "dpe_syn_set_nav_bits", "dpe_syn_windows", "dpe_syn_record",
     "dpe_cd_create", "dpe_cd_destroy", "dpe_cd_predict", "dpe_cd_update", "dpe_cd_results", "dpe_cd_map",
+    "dpe_fe_create", "dpe_fe_destroy", "dpe_fe_info", "dpe_fe_convert", "dpe_fe_clipped",
 ]
 
 
@@ -2189,6 +2190,81 @@ class CollectiveDetector:
     def close(self):
         if self._h:
             lib().dpe_cd_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:            # at interpreter shutdown module globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+class FeConfig(C.Structure):        # dpe_fe_config
+    _fields_ = [("samplingFrequency", C.c_double), ("intermediateFrequency", C.c_double), ("gain", C.c_double), ("levels", C.c_double * 4),
+                ("format", C.c_int32), ("outputFormat", C.c_int32), ("decimation", C.c_int32), ("nTaps", C.c_int32)]
+
+
+class FeInfo(C.Structure):          # dpe_fe_info_t
+    _fields_ = [("realisedIF", C.c_double), ("outputFrequency", C.c_double), ("delta", C.c_int64), ("groupDelay", C.c_int32),
+                ("bytesNum", C.c_int32), ("bytesDen", C.c_int32), ("tileOutputs", C.c_int32), ("ldsBytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+FE_FORMATS = {"I16C": 0, "I8C": 1, "I16R": 2, "I8R": 3, "ARGPI4": 4, "P2R": 5, "P2C": 6}      # DPE_FE_*
+
+
+class FrontEnd:
+    """Raw record bytes on the device to interleaved int16 I/Q at zero IF and fs_in / D (dpe_fe_*, csrc/dpe_fe.hip):
+    unpack, mix by the integer phase word, low-pass with the caller's odd-length taps, decimate.  The output is a torch int16
+    tensor on the device that Acquisition.search, the trackers and every scan take as it is (out_f32: float pairs before
+    rounding).  The handle keeps nothing of the record: any split of an output range into calls gives the bytes of one call."""
+
+    def __init__(self, fs_in, fmt, D, taps, gain=1.0, f_if=0.0, levels=(-3.0, -1.0, 1.0, 3.0), out_f32=False):
+        if isinstance(fmt, str):
+            if fmt.upper() not in FE_FORMATS:
+                raise DpeError("[FrontEnd] create: input format %r is none of %s" % (fmt, ", ".join(FE_FORMATS)))
+            fmt = FE_FORMATS[fmt.upper()]
+        self.taps = np.ascontiguousarray(taps, dtype=np.float64).ravel()
+        self.fs_in, self.D, self.T, self.out_f32 = float(fs_in), int(D), int(self.taps.size), bool(out_f32)
+        cfg = FeConfig(self.fs_in, float(f_if), float(gain), (C.c_double * 4)(*[float(v) for v in levels]), int(fmt), 1 if out_f32 else 0,
+                       self.D, self.T)
+        self._h = C.c_void_p(None)
+        _check(lib().dpe_fe_create(C.byref(cfg), self.taps.ctypes.data_as(C.POINTER(C.c_double)), C.byref(self._h)))
+        info = FeInfo()
+        _check(lib().dpe_fe_info(self._h, C.byref(info)))
+        self.delta, self.realised_if, self.fs_out, self.T0 = int(info.delta), info.realisedIF, info.outputFrequency, int(info.groupDelay)
+        self.bytes_num, self.bytes_den, self.tile_outputs, self.lds_bytes = int(info.bytesNum), int(info.bytesDen), int(info.tileOutputs), int(info.ldsBytes)
+
+    def needed(self, out_first, out_count, record_length=None):
+        """[lo, hi): the input samples the outputs [out_first, out_first + out_count) read, cut to the record."""
+        lo = max(int(out_first) * self.D - self.T0, 0)
+        hi = (int(out_first) + int(out_count) - 1) * self.D + self.T - self.T0
+        if record_length is not None:
+            hi = min(hi, int(record_length))
+        return lo, max(hi, lo)
+
+    def convert(self, raw, raw_first, out_first, out_count, record_length=None, raw_count=None, out=None, stream=None):
+        """Outputs [out_first, out_first + out_count) from `raw`, a device tensor holding the record's input samples from
+        raw_first on (raw_count of them; default: all its bytes hold).  Asynchronous.  Returns int16 [2 out_count], or float32
+        [2 out_count] for out_f32."""
+        import torch
+        if raw_count is None:
+            raw_count = raw.numel() * raw.element_size() * self.bytes_den // self.bytes_num
+        if out is None:
+            out = torch.empty(2 * int(out_count), dtype=torch.float32 if self.out_f32 else torch.int16, device="cuda")
+        _check(lib().dpe_fe_convert(self._h, _ptr(raw), C.c_int64(int(raw_first)), C.c_int64(int(raw_count)),
+                                    C.c_int64(-1 if record_length is None else int(record_length)), _ptr(out), C.c_int64(int(out_first)),
+                                    C.c_int64(int(out_count)), _stream(stream)))
+        return out
+
+    def clipped(self):
+        """Output components the last int16 convert clipped to a rail.  Synchronises."""
+        n = C.c_int64(0)
+        _check(lib().dpe_fe_clipped(self._h, C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if self._h:
+            lib().dpe_fe_destroy(self._h)
             self._h = C.c_void_p(None)
 
     def __del__(self):
