@@ -101,6 +101,17 @@ def reference(cn0=None, seed=WEAK_SEED):
     return cd_ref.scan(surf, g["sv"], g["p0"], g["R"], g["grid"], FS, J)
 
 
+SUBSET_ROWS = (7, 5, 4, 3, 1, 0)             # six of the eight PRNs, reversed: rows that differ from 0..K-1
+
+
+def subset():
+    """(prns, eph, sv) of the permuted-subset tests: the PRNs of SUBSET_ROWS in that order, their ephemerides, and the predictions
+    at p0 with `row` each one's place among the world's eight."""
+    g = geometry()
+    rows = list(SUBSET_ROWS)
+    return [g["prns"][r] for r in rows], np.asarray(g["eph"])[rows], [g["sv"][r] for r in rows]
+
+
 def weak_conditions(cn0=WEAK_CN0, seed=WEAK_SEED):
     """(SVs the oracle's per-PRN acquisition reports found, collective arg-max point, top-two margin between distinct points,
     ten times the GPU tolerance at that score)."""
@@ -133,13 +144,13 @@ RANDOM_CASES = {
 RANDOM_BIN_STEP = 500.0
 
 
-@functools.lru_cache(maxsize=None)
-def random_case(name):
-    """-> dict(surface fp32 [K + 1, nBins, M], sv, p0, R, grid, fs, J, bins, ref = cd_ref.scan of it).  SV 0 has delay0 within a
-    sample of 0 and its bin at the raster's low edge, SV 1 delay0 within a sample of M and its bin at the high edge (so some (k, j)
-    leave the raster whenever J > 0), SV 2 a bin0 of exactly 2.5 (half to even: 2).  Point 0 is p0 itself, point 1 lies 3 km east,
-    point 2 at 0.999 of the largest distance create accepts for the bin step."""
-    M, K, P, J, seed = RANDOM_CASES[name]
+def _generate(M, K, P, J, seed, bins="edge", plant=0, surface="uniform", grid="random", delays="edge"):
+    """The generator behind random_case and new_case.  The defaults are RANDOM_CASES' form and draw in its order.  The options:
+    bins "interior": every SV's bin is drawn so that b_k +- J stays inside the raster (k = 0, 1, 2 included);
+    plant -1 / +1: the surface is multiplied by 4 along [row_k, b_k + plant J, :] for every SV whose bin is inside the raster there;
+    surface "uniform" [0, 1), "zeros", "ones", "ternary" (values of {0, 0.5, 1}), "exp2" (squared exponential times 1e9);
+    grid "random" (with the three fixed points), "origin" (every point (0, 0, 0)), "repeat3" (the first P / 3 points three times over);
+    delays "edge" (within a sample of 0 and of M, the rest uniform), "whole" (whole numbers, 0 and M - 1 among them)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     n_bins = 2 * J + 9
     p0 = dpe.handoff.read_handoff(helpers.HANDOFF)["X_ECEF"][:3].copy()
@@ -149,17 +160,102 @@ def random_case(name):
     for k in range(K):
         az, el, rg = rng.uniform(0, 2 * np.pi), np.radians(rng.uniform(10.0, 90.0)), rng.uniform(2.0e7, 2.5e7)
         d = rg * np.array([np.cos(el) * np.sin(az), np.cos(el) * np.cos(az), np.sin(el)])
-        delay0 = (0.3, M - 0.4)[k] if k < 2 else float(rng.uniform(0, M))
-        bin0 = (0.4, n_bins - 1 - 0.3, 2.5)[k] if k < 3 else float(rng.uniform(J, n_bins - 1 - J))
+        if delays == "whole":
+            delay0 = float((0, M - 1)[k]) if k < 2 else float(rng.integers(0, M))
+        else:
+            delay0 = (0.3, M - 0.4)[k] if k < 2 else float(rng.uniform(0, M))
+        if bins == "interior":
+            bin0 = float(rng.uniform(J, n_bins - 1 - J))
+        else:
+            bin0 = (0.4, n_bins - 1 - 0.3, 2.5)[k] if k < 3 else float(rng.uniform(J, n_bins - 1 - J))
         sv.append(dict(prn=k + 1, row=int(rows[k]), sat=p0 + R @ d, delay0=delay0, bin0=bin0))
-    grid = np.concatenate([rng.uniform(-3000.0, 3000.0, (P, 2)), rng.uniform(-50.0, 50.0, (P, 1))], axis=1)
-    far = 0.999 * 0.5 * RANDOM_BIN_STEP / cd_ref.DOPPLER_HZ_PER_KM * 1000.0
-    for i, d in enumerate(([0.0, 0.0, 0.0], [3000.0, 0.0, 0.0], [far * 0.6, -far * 0.8, 0.0])[:P]):
-        grid[i] = d
-    surface = rng.random((K + 1, n_bins, M), dtype=np.float32)
-    bins = -1000.0 + RANDOM_BIN_STEP * np.arange(n_bins)
-    ref = cd_ref.scan(surface, sv, p0, R, grid, FS, J)
-    return dict(surface=surface, sv=sv, p0=p0, R=R, grid=grid, fs=FS, J=J, M=M, K=K, P=P, bins=bins, ref=ref)
+    if grid == "origin":
+        pts = np.zeros((P, 3))
+    else:
+        n = P // 3 if grid == "repeat3" else P
+        pts = np.concatenate([rng.uniform(-3000.0, 3000.0, (n, 2)), rng.uniform(-50.0, 50.0, (n, 1))], axis=1)
+        far = 0.999 * 0.5 * RANDOM_BIN_STEP / cd_ref.DOPPLER_HZ_PER_KM * 1000.0
+        for i, d in enumerate(([0.0, 0.0, 0.0], [3000.0, 0.0, 0.0], [far * 0.6, -far * 0.8, 0.0])[:n]):
+            pts[i] = d
+        if grid == "repeat3":
+            pts = np.concatenate([pts, pts, pts])
+    shape = (K + 1, n_bins, M)
+    if surface == "uniform":
+        surf = rng.random(shape, dtype=np.float32)
+    elif surface == "exp2":
+        surf = (rng.standard_exponential(shape) ** 2 * 1.0e9).astype(np.float32)
+    elif surface == "ternary":
+        surf = (rng.integers(0, 3, shape) * 0.5).astype(np.float32)
+    else:
+        surf = np.full(shape, {"zeros": 0.0, "ones": 1.0}[surface], dtype=np.float32)
+    if plant:
+        for s, b in zip(sv, cd_ref.bins_of(sv) + plant * J):
+            if 0 <= b < n_bins:
+                surf[s["row"], b, :] *= np.float32(4.0)
+    bin_hz = -1000.0 + RANDOM_BIN_STEP * np.arange(n_bins)
+    ref = cd_ref.scan(surf, sv, p0, R, pts, FS, J)
+    return dict(surface=surf, sv=sv, p0=p0, R=R, grid=pts, fs=FS, J=J, M=M, K=K, P=P, bins=bin_hz, ref=ref)
+
+
+@functools.lru_cache(maxsize=None)
+def random_case(name):
+    """-> dict(surface fp32 [K + 1, nBins, M], sv, p0, R, grid, fs, J, bins, ref = cd_ref.scan of it).  SV 0 has delay0 within a
+    sample of 0 and its bin at the raster's low edge, SV 1 delay0 within a sample of M and its bin at the high edge (so some (k, j)
+    leave the raster whenever J > 0), SV 2 a bin0 of exactly 2.5 (half to even: 2).  Point 0 is p0 itself, point 1 lies 3 km east,
+    point 2 at 0.999 of the largest distance create accepts for the bin step."""
+    return _generate(*RANDOM_CASES[name])
+
+
+# ---- the second table: what RANDOM_CASES' seven shapes leave undecided (tests/test_cd_world_cpu.py asserts of each case what it is
+# here for).  name: ((M, K, P, J, seed), generator options)
+DRIFT_CASES = {                                       # the drift axis decides: a wrong bin row, a wrong jj or a wrong SV dropped shows
+    "interior-2500-k8": ((2500, 8, 49, 2, 31), dict(bins="interior")),
+    "interior-2046-k4-j32": ((2046, 4, 131, 32, 32), dict(bins="interior")),
+    "interior-l2-5000-k8": ((5000, 8, 5, 2, 33), dict(bins="interior")),
+    "plant-minus-2500-k8": ((2500, 8, 9, 2, 25), dict(plant=-1)),
+    "plant-plus-2500-k8": ((2500, 8, 9, 2, 25), dict(plant=+1)),
+    "plant-minus-l2-2500-k16": ((2500, 16, 3, 2, 26), dict(plant=-1)),
+}
+TIE_CASES = {                                         # every point (0, 0, 0), whole delays, values of {0, 0.5, 1}: exact ties
+    "tie-250-zeros": ((250, 2, 40, 2, 41), dict(surface="zeros", grid="origin", delays="whole")),
+    "tie-250-ones": ((250, 2, 40, 2, 42), dict(surface="ones", grid="origin", delays="whole")),
+    "tie-250-ternary": ((250, 2, 40, 2, 43), dict(surface="ternary", grid="origin", delays="whole")),
+    "tie-2561-zeros": ((2561, 3, 40, 32, 44), dict(surface="zeros", grid="origin", delays="whole")),
+    "tie-2561-ones": ((2561, 3, 40, 32, 45), dict(surface="ones", grid="origin", delays="whole")),
+    "tie-2561-ternary": ((2561, 3, 40, 32, 46), dict(surface="ternary", grid="origin", delays="whole")),
+}
+SHAPE_CASES = {
+    "repeat-2046-k4-j32": ((2046, 4, 60, 32, 10), dict(grid="repeat3")),    # 20 offsets three times over: blocks and flush slots differ
+    "k3": ((250, 3, 9, 1, 11), {}),                   # the remainder of the SV loop unrolled by four: K mod 4 = 3 (3, 7), 1 (5, 13);
+                                                      # K mod 4 = 2 in the K = 2 cases below
+    "k5": ((250, 5, 9, 1, 12), {}),
+    "k7": ((250, 7, 9, 1, 13), {}),
+    "k13": ((250, 13, 9, 1, 14), {}),
+    "lds-4092-k2": ((4092, 2, 5, 1, 15), {}),         # 819 runs: a lane of the LDS form takes a second one
+    "lds-32768-k1": ((32768, 1, 3, 0, 16), {}),       # the M maximum: 6 554 runs, 13 passes, 131 092 B
+    "lds-2475-k16": ((2475, 16, 3, 0, 17), {}),       # 16 x 2 480 x 4 = 158 720 B: the LDS limit itself
+    "l2-2476-k16": ((2476, 16, 3, 0, 18), {}),        # 158 784 B: its other side
+    "lds-4955-k8": ((4955, 8, 3, 0, 19), {}),         # 8 x 4 960 x 4 = 158 720 B
+    "runs-512": ((2560, 2, 5, 1, 20), {}),            # exactly one run per lane
+    "runs-513": ((2561, 2, 5, 1, 21), {}),            # a second pass of one lane
+    "m-16": ((16, 2, 9, 2, 22), {}),                  # the M minimum: 4 runs, seven of eight waves without one
+    "walk-20": ((64, 2, 289, 32, 23), {}),            # 15 blocks per j walk 19 or 20 points: a flush slot is used three times
+    "walk-64": ((16, 1, 65536, 0, 24), {}),           # the P maximum: 1 024 blocks walk 64 points
+    "dynamic-range": ((2500, 8, 9, 2, 27), dict(surface="exp2")),
+}
+NEW_CASES = {**DRIFT_CASES, **TIE_CASES, **SHAPE_CASES}
+PARITY_CASES = {**DRIFT_CASES, **SHAPE_CASES}         # judged by tests/cd_checks.py check_parity; the tie cases by exact equality
+
+
+@functools.lru_cache(maxsize=None)
+def new_case(name):
+    """random_case's dict for a case of NEW_CASES."""
+    shape, opts = NEW_CASES[name]
+    return _generate(*shape, **opts)
+
+
+def any_case(name):
+    return random_case(name) if name in RANDOM_CASES else new_case(name)
 
 
 def tolerance(ref):

@@ -45,12 +45,71 @@ def _hip_include():
     return None
 
 
-def test_plan_predictions_and_refusals(tmp_path, oracle):
+def _build(tmp_path):
     if _cxx() is None or _hip_include() is None:
         pytest.skip("no host C++ compiler, or no HIP headers for csrc/dpe_common.h")
     exe = str(tmp_path / "test_cd_plan")
     subprocess.run([_cxx(), "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__", "-I" + _hip_include(), SRC,
                     "-o", exe], check=True)
+    return exe
+
+
+THREADS, FLUSH, LDS_MAX = 512, 8, 155 * 1024       # kCdThreads, kCdFlush, kCdLdsMax
+
+# What each shape of tests/cd_world.py's second table is there to reach, in cd_plan's own values.
+# name -> (rows in LDS, LDS bytes, runs per row, blocks per j, points per block)
+NEW_CASE_PLANS = {
+    "k3": (1, 3060, 50, 9, 1), "k5": (1, 5100, 50, 9, 1), "k7": (1, 7140, 50, 9, 1), "k13": (1, 13260, 50, 9, 1),
+    "lds-4092-k2": (1, 32776, 819, 5, 1),            # LDS form, 819 runs: lanes 0..306 take a second run
+    "lds-32768-k1": (1, 131092, 6554, 3, 1),         # the M maximum: 13 passes (12 full ones and 410 runs)
+    "lds-2475-k16": (1, 158720, 495, 3, 1),          # the limit itself ...
+    "l2-2476-k16": (0, 0, 496, 3, 1),                # ... and 64 B over it
+    "lds-4955-k8": (1, 158720, 991, 3, 1),
+    "runs-512": (1, 20520, 512, 5, 1),
+    "runs-513": (1, 20528, 513, 5, 1),
+    "m-16": (1, 168, 4, 9, 1),
+    "walk-20": (1, 552, 13, 15, 20),
+    "walk-64": (1, 84, 4, 1024, 64),
+    "repeat-2046-k4-j32": (1, 32816, 410, 15, 4),
+    "tie-2561-ones": (1, 30792, 513, 15, 3),
+    "interior-l2-5000-k8": (0, 0, 1000, 5, 1),
+    "plant-minus-l2-2500-k16": (0, 0, 500, 3, 1),
+}
+
+
+def test_new_cases_reach_what_they_are_named_for(tmp_path):
+    exe = _build(tmp_path)
+    names = list(NEW_CASE_PLANS)
+    path = tmp_path / "plans.txt"
+    shapes = [cd_world.NEW_CASES[n][0] for n in names]                              # (M, K, P, J, seed)
+    path.write_text("".join("plan %d %d %d %d\n" % (M, K, J, P) for M, K, P, J, _ in shapes))
+    got = subprocess.run([exe, str(path)], check=True, stdout=subprocess.PIPE, text=True).stdout.splitlines()
+    assert len(got) == len(names)
+    plan = {}
+    for n, line in zip(names, got):
+        run, n_runs, pitch, use_lds, lds_bytes, n_j, blocks_x, per_block = (int(v) for v in line.split())
+        assert (use_lds, lds_bytes, n_runs, blocks_x, per_block) == NEW_CASE_PLANS[n], (n, line)
+        M, K, P, J, _ = cd_world.NEW_CASES[n][0]
+        plan[n] = dict(lds=use_lds, bytes=lds_bytes, need=K * pitch * 4, passes=-(-n_runs // THREADS), runs=n_runs, blocks=blocks_x,
+                       per_block=per_block, short=blocks_x * per_block - P)
+    assert sorted(cd_world.NEW_CASES[n][0][1] % 4 for n in ("k3", "k5", "k7", "k13", "runs-512")) == [1, 1, 2, 3, 3]
+    assert plan["lds-4092-k2"]["lds"] and plan["lds-4092-k2"]["passes"] == 2
+    assert plan["lds-32768-k1"]["lds"] and plan["lds-32768-k1"]["passes"] == 13 and cd_world.NEW_CASES["lds-32768-k1"][0][0] == 32768
+    assert plan["lds-2475-k16"]["bytes"] == LDS_MAX == plan["lds-4955-k8"]["bytes"]
+    assert not plan["l2-2476-k16"]["lds"] and plan["l2-2476-k16"]["need"] == LDS_MAX + 64
+    assert plan["runs-512"]["runs"] == THREADS and plan["runs-513"]["runs"] == THREADS + 1 and plan["runs-513"]["passes"] == 2
+    assert plan["m-16"]["runs"] == 4 and cd_world.NEW_CASES["m-16"][0][0] == 16
+    # a flush slot is reused more than once, and the blocks' point counts differ (19 and 20)
+    assert plan["walk-20"]["per_block"] > 2 * FLUSH and 0 < plan["walk-20"]["short"] < plan["walk-20"]["blocks"]
+    assert plan["walk-64"]["per_block"] == 8 * FLUSH and cd_world.NEW_CASES["walk-64"][0][2] == 65536 and plan["walk-64"]["short"] == 0
+    # the repeated offsets p, p + 20, p + 40 fall to different blocks (20 and 40 are no multiples of 15) and to different slots
+    assert 20 % plan["repeat-2046-k4-j32"]["blocks"] and 40 % plan["repeat-2046-k4-j32"]["blocks"]
+    assert plan["tie-2561-ones"]["per_block"] == 3 and plan["tie-2561-ones"]["passes"] == 2
+    assert not plan["interior-l2-5000-k8"]["lds"] and not plan["plant-minus-l2-2500-k16"]["lds"]
+
+
+def test_plan_predictions_and_refusals(tmp_path, oracle):
+    exe = _build(tmp_path)
     h = float.hex
     g = cd_world.geometry()
     b = cd_world.bins()
