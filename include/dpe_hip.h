@@ -1247,7 +1247,8 @@ int dpe_fe_info(const dpe_fe *h, dpe_fe_info_t *info);
  * [rawFirstSample, rawFirstSample + rawCount) of the record (a packed format's rawFirstSample on a byte boundary).  recordLength:
  * samples at and beyond it count as zero, as the samples before 0 do (-1: no end).  The outputs need the input samples
  * [outFirst D - T0, (outFirst + outCount - 1) D + T - 1 - T0] cut to [0, recordLength); the call is refused when the buffer does
- * not hold them all.  The handle keeps nothing of the record between calls.  Asynchronous on `stream`, like dpe_syn_record. */
+ * not hold them all.  1 <= outCount <= 2^30, and every output index lies in 0 .. 2^55 - 1: outFirst + outCount <= 2^55.  The handle
+ * keeps nothing of the record between calls.  Asynchronous on `stream`, like dpe_syn_record. */
 int dpe_fe_convert(dpe_fe *h, const void *raw_dev, int64_t rawFirstSample, int64_t rawCount, int64_t recordLength, void *out_dev,
                    int64_t outFirst, int64_t outCount, dpe_stream_t stream);
 /* Output components the last int16 convert call clipped to a rail.  Synchronises with that call's stream. */

@@ -29,7 +29,7 @@ constexpr int kFeMaxD = 64;
 constexpr int kFeMaxT = 1023;
 constexpr int kFeLdsBytes = 32 * 1024;      // the staged tile's upper limit: five blocks per CU keep enough loads in flight
 constexpr int64_t kFeMaxCount = INT64_C(1) << 30;    // outputs per call
-constexpr int64_t kFeMaxIndex = INT64_C(1) << 55;    // output indices: (index + count) D + T stays far inside 64 bits
+constexpr int64_t kFeMaxIndex = INT64_C(1) << 55;    // every output index of a call lies below it: (index + count) D + T stays far inside 64 bits
 
 enum FeMode { kFeRealIn = 0, kFeComplex = 1, kFeComplexMix = 2 };   // what the tap loop multiplies (fe_taps)
 
@@ -214,7 +214,8 @@ inline bool fe_convert_problem(const dpe_fe_config &cfg, bool rawNull, bool outN
     DPE_FE_REFUSE(outAlign % outBytes != 0, "[FrontEnd] convert: the output is not aligned to an I/Q pair (%u bytes)", outBytes);
     DPE_FE_REFUSE(den == 1 && rawAlign % (unsigned)num != 0, "[FrontEnd] convert: the input is not aligned to a sample (%d bytes)", num);
     DPE_FE_REFUSE(outCount < 1 || outCount > kFeMaxCount, "[FrontEnd] convert: %lld outputs outside 1..2^30 per call", (long long)outCount);
-    DPE_FE_REFUSE(outFirst < 0 || outFirst > kFeMaxIndex, "[FrontEnd] convert: first output %lld outside 0..2^55", (long long)outFirst);
+    DPE_FE_REFUSE(outFirst < 0 || outFirst > kFeMaxIndex - outCount, "[FrontEnd] convert: first output %lld with %lld outputs outside 0..2^55",
+                  (long long)outFirst, (long long)outCount);
     DPE_FE_REFUSE(rawFirst < 0 || rawCount < 0 || rawFirst > (INT64_C(1) << 61) || rawCount > (INT64_C(1) << 61),
                   "[FrontEnd] convert: input range %lld + %lld negative or beyond 2^61", (long long)rawFirst, (long long)rawCount);
     DPE_FE_REFUSE(recordLength < -1, "[FrontEnd] convert: record length %lld (-1: no end)", (long long)recordLength);

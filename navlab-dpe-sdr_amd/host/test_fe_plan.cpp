@@ -9,6 +9,7 @@
 //     geom D T real                      -> tileOut rowLen pitch ldsBytes Q rem
 //     owner D T real i                   -> block lane slot
 //     tap D T real delta t               -> mode-2 table entry of tap t as four hex floats, for gain 1 and h[t] = 1
+//     taps D T mode                      -> the whole table [D][qPitch][4] of mode 0, 1 or 2 as hex floats, for gain 1, delta 0 and h[t] = t + 1
 //     cfg fmt out D T fs fIF             -> the refusal of dpe_fe_create's checks, or "ok"
 //     conv fmt D T rawFirst rawCount len outFirst outCount rawAlign outAlign -> the refusal of dpe_fe_convert's checks, or "ok"
 #include <cinttypes>
@@ -176,6 +177,14 @@ int main(int argc, char **argv)
             const int t = (int)I(5);
             const float *e = tab.data() + ((size_t)(t % g.D) * g.qPitch + t / g.D) * 4;
             printf("%a %a %a %a\n", e[0], e[1], e[2], e[3]);
+        } else if (!strcmp(w[0], "taps") && n == 4) {
+            static double ramp[kFeMaxT + 2];
+            for (int t = 0; t < kFeMaxT + 2; ++t) ramp[t] = t + 1.0;
+            const int mode = (int)I(3);
+            const FeGeom g = fe_geom((int)I(1), (int)I(2), mode == kFeRealIn);
+            const std::vector<float> tab = fe_taps(g, (FeMode)mode, 0u, 1.0, ramp);
+            for (size_t i = 0; i < tab.size(); ++i) printf("%s%a", i ? " " : "", tab[i]);
+            printf("\n");
         } else if (!strcmp(w[0], "cfg") && n == 7) {
             const dpe_fe_config c = config((int)I(1), (int)I(2), (int)I(3), (int)I(4), D(5), D(6));
             printf("%s\n", fe_config_problem(&c, ones, msg, sizeof(msg)) ? msg : "ok");

@@ -32,6 +32,15 @@ def _tap(d, t):
     return np.array([np.cos(a), -np.sin(a), np.sin(a), np.cos(a)])
 
 
+def _table(D, T, mode):
+    """The whole table [D][ceil(T / D)][4] for gain 1, delta 0 and the distinct taps h[t] = t + 1: entry (t mod D, t div D) carries
+    t + 1 -- (h, 0, 0, 0) for real input, (h, h, 0, 0) for real taps, (h, 0, 0, h) for complex taps -- and every other entry is zero."""
+    tab = np.zeros((D, -(-T // D), 4))
+    for t in range(T):
+        tab[t % D, t // D] = ((t + 1, 0, 0, 0), (t + 1, t + 1, 0, 0), (t + 1, 0, 0, t + 1))[mode]
+    return tab.ravel()
+
+
 def _cases():
     rng = np.random.Generator(np.random.PCG64(21))
     h = float.hex
@@ -60,6 +69,8 @@ def _cases():
         for d in (2 ** 30, 3 * 2 ** 30, 530243895):
             for t in sorted({0, min(1, T - 1), T // 2, T - 1}):
                 out.append(("tap %d %d 0 %d %d" % (D, T, d, t), _tap(d, t)))
+        for mode in (0, 1, 2):
+            out.append(("taps %d %d %d" % (D, T, mode), _table(D, T, mode)))
     I16C, P2R, P2C = FMT["I16C"], FMT["P2R"], FMT["P2C"]
     for line, pat in (("cfg %d 0 4 33 %s %s" % (I16C, h(1e7), h(0.0)), "ok"), ("cfg %d 1 64 1023 %s %s" % (P2C, h(1e7), h(-1e7)), "ok"),
                       ("cfg %d 0 4 32 %s %s" % (I16C, h(1e7), h(0.0)), "T = 32 taps is even"), ("cfg %d 0 0 33 %s %s" % (I16C, h(1e7), h(0.0)), "D = 0 outside 1..64"),
@@ -75,7 +86,12 @@ def _cases():
                       ("conv %d 4 33 383 70 -1 100 10 0 0" % P2C, "not on a byte boundary (2 samples per byte)"),
                       ("conv %d 4 33 384 69 -1 100 10 2 0" % I16C, "input is not aligned to a sample (4 bytes)"), ("conv %d 4 33 384 69 -1 100 10 0 2" % I16C, "output is not aligned"),
                       ("conv %d 4 33 384 69 -1 100 0 0 0" % I16C, "0 outputs outside"), ("conv %d 4 33 384 69 -1 -1 10 0 0" % I16C, "first output -1"),
-                      ("conv %d 4 33 384 69 -2 100 10 0 0" % I16C, "record length -2"), ("conv %d 4 33 0 0 0 100 10 0 0" % I16C, "ok")):
+                      ("conv %d 4 33 384 69 -2 100 10 0 0" % I16C, "record length -2"), ("conv %d 4 33 0 0 0 100 10 0 0" % I16C, "ok"),
+                      # every output index below 2^55: D 64 T 513, the buffer holds what 201 outputs from 2^55 - 200 would read
+                      ("conv %d 64 513 %d 14000 -1 %d 200 0 0" % (FMT["I8C"], 2 ** 61 - 13056, 2 ** 55 - 200), "ok"),
+                      ("conv %d 64 513 %d 14000 -1 %d 201 0 0" % (FMT["I8C"], 2 ** 61 - 13056, 2 ** 55 - 200), "with 201 outputs outside 0..2^55"),
+                      ("conv %d 64 513 %d 14000 -1 %d 1 0 0" % (FMT["I8C"], 2 ** 61 - 13056, 2 ** 55 - 1), "ok"),
+                      ("conv %d 64 513 %d 14000 -1 %d 1 0 0" % (FMT["I8C"], 2 ** 61 - 13056, 2 ** 55), "first output 36028797018963968 with 1 outputs outside 0..2^55")):
         out.append((line, pat))
     return out
 
@@ -102,6 +118,8 @@ def test_plan_properties_and_mappings(tmp_path):
             e = np.array([float.fromhex(v) for v in have.split()])
             assert np.all(np.abs(e - want) <= 2.0 ** -24) and e[2] == -e[1] and e[3] == e[0], line
             assert np.all(e == e.astype(np.float32)), line
+        elif kind == "taps":
+            assert np.array_equal(np.array([float.fromhex(v) for v in have.split()]), want), line      # (-0.0 equals 0.0)
         elif kind in ("cfg", "conv"):
             assert (have == "ok") if want == "ok" else (have.startswith("[FrontEnd] ") and want in have), (line, have)
         else:

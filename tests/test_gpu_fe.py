@@ -25,7 +25,7 @@ def _built():
 
 
 def _fe(c, out_f32, fs=fe_world.FS):
-    return dpe.FrontEnd(fs, c["fmt"], c["D"], c["h"], gain=c["gain"], f_if=c["f_if"], out_f32=out_f32)
+    return dpe.FrontEnd(fs, c["fmt"], c["D"], c["h"], gain=c["gain"], f_if=c["f_if"], levels=c.get("levels", fe_ref.LEVELS), out_f32=out_f32)
 
 
 def _device(raw):
