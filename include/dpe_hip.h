@@ -1254,6 +1254,74 @@ int dpe_fe_convert(dpe_fe *h, const void *raw_dev, int64_t rawFirstSample, int64
 /* Output components the last int16 convert call clipped to a rail.  Synchronises with that call's stream. */
 int dpe_fe_clipped(dpe_fe *h, int64_t *count);
 
+/* ------------------------------------------------------------------ Interference excision ---- */
+/* Complex baseband samples in a device buffer -- what dpe_fe_convert has just written -- to the same samples, at the same rate,
+ * without pulses and narrow-band interferers, written into a device buffer (csrc/dpe_ix.hip, csrc/dpe_ix_plan.h): a
+ * pulse blanker, then an overlapped, windowed transform whose strong bins are set to zero before it is inverted.  No counterpart
+ * in the reference, which assumes that the band holds satellites and white noise.  One kernel; no FFT library; a frame stays in
+ * the LDS from its load to its store.  With the frame length N, the hop H = N / 2 and x[n] = 0 outside [0, recordLength), in
+ * exact arithmetic
+ *   b[n]     = 0 where |x[n]|^2 > blankPower, else x[n]                     (blankPower = 0: no blanking)
+ *   X_k[f]   = sum_{i < N} w[i] b[(k - 1) H + i] exp(-2 pi j f i / N),      w[i] = sin(pi (i + 1/2) / N), frame k >= 0
+ *   P_k[f]   = |X_k[f]|^2,   m_k = the lower median of P_k (element N / 2 - 1 of the ascending sort)
+ *   e_k[f]   = static[f] or (P_k[g] > threshold m_k for a bin g within +-guard of f, cyclically)
+ *   y_k[i]   = (1 / N) sum_f X_k[f] (1 - e_k[f]) exp(+2 pi j f i / N)
+ *   out[n]   = gain (w[r + H] y_h[r + H] + w[r] y_{h+1}[r]),   h = n div H, r = n mod H
+ * and the output out[n] as fp32 pairs, or clip(rint(out), -32768, 32767) per component (round to nearest even) as int16 pairs.
+ * w[i]^2 + w[i + H]^2 = 1: where nothing is excised the output is gain x.  The comparison with the median is strict, so a frame
+ * of zeros excises nothing.  For int16 input the blanker's comparison is exact: I^2 + Q^2 as a 32-bit unsigned integer against
+ * floor(blankPower); for fp32 input both sides are fp32.  fp32 input must be finite: an infinity or a NaN spreads over the two
+ * frames that hold it, and the median of a frame with a NaN is not defined.  The device forms X, P and y in fp32 with twiddles
+ * and window rounded from fp64; a frame's arithmetic depends on its index, the handle and the input values alone, so any split
+ * of an output range into calls gives the bytes of one call, in both output formats. */
+#define DPE_IX_IN_I16 0
+#define DPE_IX_IN_F32 1
+typedef struct dpe_ix dpe_ix;
+typedef struct dpe_ix_config {
+    double threshold;             /* kappa > 0: a bin is detected above kappa times the frame's lower median power */
+    double blankPower;            /* >= 0; 0: the pulse blanker is off */
+    double gain;
+    int32_t frameLength;          /* N, a power of two in 64..4096 */
+    int32_t guard;                /* bins excised on either side of a detected one, 2 guard + 1 < N */
+    int32_t inputFormat;          /* DPE_IX_IN_I16 / DPE_IX_IN_F32 */
+    int32_t outputFormat;         /* DPE_FE_OUT_I16 / DPE_FE_OUT_F32 */
+} dpe_ix_config;
+typedef struct dpe_ix_info_t {
+    int32_t hop;                  /* H = N / 2 */
+    int32_t hopsPerBlock;         /* consecutive hops a block of the launch owns */
+    int32_t ldsBytes;             /* of a block */
+    int32_t leadHops, tailHops;   /* outputs [a, a + c) read the inputs [(a div H - leadHops) H, ((a + c - 1) div H + tailHops) H) */
+    int32_t reserved;
+} dpe_ix_info_t;
+typedef struct dpe_ix_stats_t {
+    int64_t frames;               /* frames whose centre k H is one of the call's outputs: the counted frames */
+    int64_t excisedBins;          /* bins set to zero in the counted frames */
+    int64_t blanked;              /* input samples among the call's outputs and inside the record that the blanker zeroed */
+    int64_t clipped;              /* int16 output components clipped to a rail */
+} dpe_ix_stats_t;
+/* staticMask: host uint8 [N], nonzero = always excised, or NULL.  Everything outside the limits is refused with a message before
+ * anything is allocated. */
+int dpe_ix_create(const dpe_ix_config *cfg, const uint8_t *staticMask, dpe_ix **out);
+int dpe_ix_destroy(dpe_ix *h);
+int dpe_ix_info(const dpe_ix *h, dpe_ix_info_t *info);
+/* Outputs [outFirst, outFirst + outCount) into out_dev[0 ..) (int16 or float pairs) from x_dev, which holds the input samples
+ * [xFirst, xFirst + xCount) of the record (int16 or float pairs).  recordLength: samples at and beyond it count as zero, as the
+ * samples before 0 do (-1: no end).  The outputs need the input samples [(outFirst div H - 1) H, ((outFirst + outCount - 1) div H
+ * + 2) H) cut to [0, recordLength); the call is refused when the buffer does not hold them all, and a refused call launches
+ * nothing.  1 <= outCount <= 2^30, outFirst + outCount <= 2^55.  The handle keeps nothing of the record between calls.
+ * Asynchronous on `stream`. */
+int dpe_ix_process(dpe_ix *h, const void *x_dev, int64_t xFirst, int64_t xCount, int64_t recordLength, void *out_dev, int64_t outFirst,
+                   int64_t outCount, dpe_stream_t stream);
+/* The counters of the last process call; perBin: host int64 [N], the counted frames' excisions per bin, or NULL.  Additive over
+ * any split of an output range into calls.  Synchronises with that call's stream. */
+int dpe_ix_stats(dpe_ix *h, dpe_ix_stats_t *stats, int64_t *perBin);
+/* The device's own detection for the frames [frameFirst, frameFirst + frameCount), by the device function process runs: P_k[f]
+ * into power_dev (float [frameCount][N]), m_k into median_dev (float [frameCount]), e_k[f] into mask_dev (uint8 [frameCount][N], 0
+ * or 1); each may be NULL.  The frames need the input samples [(frameFirst - 1) H, (frameFirst + frameCount) H) cut to the
+ * record.  1 <= frameCount <= 2^24.  Leaves the counters of dpe_ix_stats alone.  Asynchronous on `stream`. */
+int dpe_ix_analyse(dpe_ix *h, const void *x_dev, int64_t xFirst, int64_t xCount, int64_t recordLength, int64_t frameFirst,
+                   int64_t frameCount, float *power_dev, float *median_dev, uint8_t *mask_dev, dpe_stream_t stream);
+
 /* Timing helper for bench.py: HIP events on the stream the kernels run on. */
 int dpe_event_create(void **ev);
 int dpe_event_record(void *ev, dpe_stream_t stream);

@@ -49,6 +49,7 @@ EXPORTS = [
     "dpe_syn_create", "dpe_syn_destroy", "dpe_syn_set_nav_bits", "dpe_syn_windows", "dpe_syn_record",
     "dpe_cd_create", "dpe_cd_destroy", "dpe_cd_predict", "dpe_cd_update", "dpe_cd_results", "dpe_cd_map",
     "dpe_fe_create", "dpe_fe_destroy", "dpe_fe_info", "dpe_fe_convert", "dpe_fe_clipped",
+    "dpe_ix_create", "dpe_ix_destroy", "dpe_ix_info", "dpe_ix_process", "dpe_ix_stats", "dpe_ix_analyse",
 ]
 
 
@@ -2265,6 +2266,97 @@ class FrontEnd:
     def close(self):
         if self._h:
             lib().dpe_fe_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:            # at interpreter shutdown module globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+class IxConfig(C.Structure):        # dpe_ix_config
+    _fields_ = [("threshold", C.c_double), ("blankPower", C.c_double), ("gain", C.c_double), ("frameLength", C.c_int32), ("guard", C.c_int32),
+                ("inputFormat", C.c_int32), ("outputFormat", C.c_int32)]
+
+
+class IxInfo(C.Structure):          # dpe_ix_info_t
+    _fields_ = [("hop", C.c_int32), ("hopsPerBlock", C.c_int32), ("ldsBytes", C.c_int32), ("leadHops", C.c_int32), ("tailHops", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class IxStats(C.Structure):         # dpe_ix_stats_t
+    _fields_ = [("frames", C.c_int64), ("excisedBins", C.c_int64), ("blanked", C.c_int64), ("clipped", C.c_int64)]
+
+
+class Excisor:
+    """Interference excision on complex baseband samples on the device (dpe_ix_*, csrc/dpe_ix.hip): a pulse blanker,
+    then frames of N samples at a hop of N / 2 whose bins above `threshold` times the frame's lower median power (widened by
+    `guard`, plus the always-excised `static_mask`) are set to zero before the frame is put back.  Takes and gives interleaved
+    int16 I/Q (in_f32 / out_f32: float pairs) at the same rate, so it sits between FrontEnd.convert and every other stage.  The
+    handle keeps nothing of the record: any split of an output range into calls gives the bytes of one call."""
+
+    def __init__(self, N, threshold, guard=1, blank_power=0.0, gain=1.0, static_mask=None, in_f32=False, out_f32=False):
+        self.N, self.in_f32, self.out_f32 = int(N), bool(in_f32), bool(out_f32)
+        cfg = IxConfig(float(threshold), float(blank_power), float(gain), self.N, int(guard), 1 if in_f32 else 0, 1 if out_f32 else 0)
+        mask = None
+        if static_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(static_mask) != 0, dtype=np.uint8).ravel()
+            if mask.size != self.N:
+                raise DpeError("[Excisor] create: the static mask holds %d bins, the frame %d" % (mask.size, self.N))
+        self._h = C.c_void_p(None)
+        _check(lib().dpe_ix_create(C.byref(cfg), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(self._h)))
+        info = IxInfo()
+        _check(lib().dpe_ix_info(self._h, C.byref(info)))
+        self.hop, self.hops_per_block, self.lds_bytes = int(info.hop), int(info.hopsPerBlock), int(info.ldsBytes)
+        self.lead_hops, self.tail_hops = int(info.leadHops), int(info.tailHops)
+
+    def needed(self, out_first, out_count, record_length=None):
+        """[lo, hi): the input samples the outputs [out_first, out_first + out_count) read, cut to the record."""
+        H = self.N // 2
+        lo = max((int(out_first) // H - 1) * H, 0)
+        hi = ((int(out_first) + int(out_count) - 1) // H + 2) * H
+        if record_length is not None:
+            hi = min(hi, int(record_length))
+        return lo, max(hi, lo)
+
+    def _count(self, x, x_count):
+        return x.numel() // 2 if x_count is None else int(x_count)
+
+    def process(self, x, x_first, out_first, out_count, record_length=None, x_count=None, out=None, stream=None):
+        """Outputs [out_first, out_first + out_count) from `x`, a device tensor (int16 or float32 [2 n]) holding the record's samples
+        from x_first on.  Asynchronous.  Returns int16 [2 out_count], or float32 [2 out_count] for out_f32."""
+        import torch
+        if out is None:
+            out = torch.empty(2 * int(out_count), dtype=torch.float32 if self.out_f32 else torch.int16, device="cuda")
+        _check(lib().dpe_ix_process(self._h, _ptr(x), C.c_int64(int(x_first)), C.c_int64(self._count(x, x_count)),
+                                    C.c_int64(-1 if record_length is None else int(record_length)), _ptr(out), C.c_int64(int(out_first)),
+                                    C.c_int64(int(out_count)), _stream(stream)))
+        return out
+
+    def stats(self):
+        """The last process call's counters: frames, excisedBins, blanked, clipped, and excisedPerBin (int64 [N]).  Synchronises."""
+        st = IxStats()
+        per = np.zeros(self.N, dtype=np.int64)
+        _check(lib().dpe_ix_stats(self._h, C.byref(st), per.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(frames=int(st.frames), excisedBins=int(st.excisedBins), blanked=int(st.blanked), clipped=int(st.clipped), excisedPerBin=per)
+
+    def analyse(self, x, x_first, frame_first, frame_count, record_length=None, x_count=None, stream=None):
+        """The device's own detection for the frames [frame_first, frame_first + frame_count): (P float32 [frames, N], m float32
+        [frames], e uint8 [frames, N]) as device tensors -- the spectrogram of the record, and what process excises."""
+        import torch
+        n = max(int(frame_count), 0)
+        P = torch.empty((n, self.N), dtype=torch.float32, device="cuda")
+        m = torch.empty(n, dtype=torch.float32, device="cuda")
+        e = torch.empty((n, self.N), dtype=torch.uint8, device="cuda")
+        _check(lib().dpe_ix_analyse(self._h, _ptr(x), C.c_int64(int(x_first)), C.c_int64(self._count(x, x_count)),
+                                    C.c_int64(-1 if record_length is None else int(record_length)), C.c_int64(int(frame_first)),
+                                    C.c_int64(int(frame_count)), _ptr(P), _ptr(m), _ptr(e), _stream(stream)))
+        return P, m, e
+
+    def close(self):
+        if self._h:
+            lib().dpe_ix_destroy(self._h)
             self._h = C.c_void_p(None)
 
     def __del__(self):

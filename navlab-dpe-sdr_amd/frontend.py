@@ -1,6 +1,7 @@
 """Helpers around engine.FrontEnd (dpe_fe_*): a low-pass designer for the decimator, the input format of the
 reference's raw-file dtypes (pygnss rawfile.py:102-108, 152-158), and a generator that takes a raw file through the front end
-piece by piece.  No device is needed to import this module or to design a filter."""
+piece by piece, with an excisor behind the front end where one is wanted (Excised).  No device is needed to import this module or
+to design a filter."""
 import numpy as np
 
 
@@ -56,3 +57,38 @@ def convert_file(path, fe, chunk_out, record_length=None):
             raw = np.frombuffer(f.read(-(-(hi - lo) * num // den)), dtype=np.uint8)
             dev = torch.from_numpy(raw.copy()).to("cuda")
             yield fe.convert(dev, lo, first, count, record_length=record_length, raw_count=hi - lo)
+
+
+class Excised:
+    """An engine.FrontEnd followed by an engine.Excisor, with the face convert_file reads a front end by: convert_file(path,
+    Excised(fe, excisor), chunk_out) yields each chunk of the front end's output excised.  A chunk of excised outputs needs front-end
+    outputs on both sides of it (Excisor.needed), so `needed` asks for the raw samples of that wider range and `convert` takes the
+    wider range through the front end before it excises the chunk.  By the split property of both stages the pieces are the bytes
+    of one FrontEnd.convert call over the whole record put through one Excisor.process call.  Both stages give int16."""
+
+    def __init__(self, fe, excisor):
+        if fe.out_f32 or excisor.in_f32:
+            raise ValueError("Excised joins a front end with int16 output to an excisor with int16 input")
+        self.fe, self.excisor = fe, excisor
+        self.D, self.bytes_num, self.bytes_den = fe.D, fe.bytes_num, fe.bytes_den
+
+    def _mid(self, out_first, out_count, record_length):
+        """The front-end outputs the excised outputs read; the front end's record of n_in input samples holds ceil(n_in / D)."""
+        n_mid = None if record_length is None else -(-int(record_length) // self.D)
+        lo, hi = self.excisor.needed(out_first, out_count, n_mid)
+        return lo, hi, n_mid
+
+    def needed(self, out_first, out_count, record_length=None):
+        lo, hi, _ = self._mid(out_first, out_count, record_length)
+        if hi <= lo:
+            return 0, 0
+        return self.fe.needed(lo, hi - lo, record_length)
+
+    def convert(self, raw, raw_first, out_first, out_count, record_length=None, raw_count=None, out=None, stream=None):
+        import torch
+        lo, hi, n_mid = self._mid(out_first, out_count, record_length)
+        if hi > lo:
+            mid = self.fe.convert(raw, raw_first, lo, hi - lo, record_length=record_length, raw_count=raw_count, stream=stream)
+        else:                                                # (outputs wholly beyond the record read nothing)
+            mid = torch.zeros(2, dtype=torch.int16, device="cuda")
+        return self.excisor.process(mid, lo, out_first, out_count, record_length=n_mid, x_count=hi - lo, out=out, stream=stream)
