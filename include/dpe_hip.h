@@ -1322,6 +1322,70 @@ int dpe_ix_stats(dpe_ix *h, dpe_ix_stats_t *stats, int64_t *perBin);
 int dpe_ix_analyse(dpe_ix *h, const void *x_dev, int64_t xFirst, int64_t xCount, int64_t recordLength, int64_t frameFirst,
                    int64_t frameCount, float *power_dev, float *median_dev, uint8_t *mask_dev, dpe_stream_t stream);
 
+/* ------------------------------------------------------------------ Antenna array combiner ---- */
+/* M element streams of interleaved int16 I/Q, each in its own device buffer, to B streams at the same rate in which adaptive
+ * weights have put a null on whatever dominates the elements' covariance (csrc/dpe_arr.hip, csrc/dpe_arr_plan.h):
+ * the spatial defence against a broadband jammer, which the excisor cannot remove.  No counterpart in the reference, which takes
+ * one stream.  With the block length L, block k covering the samples [k L, (k + 1) L) cut to the record, and x_a[n] = 0 outside
+ * [0, recordLength), in exact arithmetic
+ *   S_k[a][b] = sum_{n in block k} x_a[n] conj(x_b[n])                       exact integers (int64)
+ *   R_k       = S_k + loading (tr S_k / M) I                                 fp64
+ *   u         = R_k^-1 c_b  (Cholesky),   w_b = u / (c_b^H u)                so w_b^H c_b = 1
+ *   fallback  w_b = c_b / (c_b^H c_b) where block k holds fewer than 2 M samples of the record, tr S_k = 0 (an integer test), or
+ *             a component of u or w_b is not finite
+ *   v_{b,a}   = fp32(gain conj(w_{b,a}))                                     rounded once per component
+ *   y_b[n]    = sum_a v_{b,a} x_a[n],  n in block k                          fp32, one FMA chain per component, a ascending
+ * and the output y_b[n] as fp32 pairs, or clip(rint(y), -32768, 32767) per component (round to nearest even) as int16 pairs.
+ * One constraint with c = the unit vector of the reference element is power inversion (that element passes with unit weight); a
+ * steering vector as c_b is the MVDR beam toward it.  Nothing but the handle, k and block k's input values enters a block's
+ * weights, and nothing but those weights and sample n enters output n: any split of an output range into calls gives the bytes
+ * of one call, in both output formats. */
+typedef struct dpe_arr dpe_arr;
+typedef struct dpe_arr_config {
+    double loading;               /* lambda >= 0, finite */
+    double gain;
+    int32_t nElements;            /* M, 2..8 */
+    int32_t blockLength;          /* L, a power of two in 256..65536 */
+    int32_t nConstraints;         /* B, 1..4: the number of outputs */
+    int32_t reference;            /* constraints == NULL: the element whose unit vector is the one constraint */
+    int32_t outputFormat;         /* DPE_FE_OUT_I16 / DPE_FE_OUT_F32 */
+    int32_t reserved;
+} dpe_arr_config;
+typedef struct dpe_arr_info_t {
+    int32_t blockLength;          /* L: outputs [a, a + c) read the inputs [(a div L) L, ((a + c - 1) div L + 1) L) of every element */
+    int32_t blocksPerUnit;        /* consecutive blocks a workgroup of the launch owns */
+    int32_t ldsBytes;             /* of a workgroup */
+    int32_t minSamples;           /* 2 M: a block with fewer samples inside the record takes the fallback */
+} dpe_arr_info_t;
+typedef struct dpe_arr_stats_t {
+    int64_t blocks;               /* blocks whose first sample k L lies inside the record and among the call's outputs: the counted blocks */
+    int64_t fallbackBlocks;       /* counted blocks in which a constraint took the fallback */
+    int64_t clipped;              /* int16 output components clipped to a rail */
+} dpe_arr_stats_t;
+/* constraints: host double [B][M][2] (re, im), finite, none zero; NULL: B = 1 and the unit vector of cfg->reference.  Everything
+ * outside the limits is refused with a message before anything is allocated. */
+int dpe_arr_create(const dpe_arr_config *cfg, const double *constraints, dpe_arr **out);
+int dpe_arr_destroy(dpe_arr *h);
+int dpe_arr_info(const dpe_arr *h, dpe_arr_info_t *info);
+/* Outputs [outFirst, outFirst + outCount) of constraint b into out_dev[b][0 ..) (int16 or float pairs) from x_dev[a], each of
+ * which holds the input samples [xFirst, xFirst + xCount) of element a (int16 pairs).  x_dev and out_dev are host arrays of M and
+ * B device pointers.  recordLength: samples at and beyond it count as zero (-1: no end).  The outputs need the input samples
+ * [(outFirst div L) L, ((outFirst + outCount - 1) div L + 1) L) cut to [0, recordLength) from every element; the call is refused
+ * when the buffers do not hold them all, when a pointer is NULL or an output range overlaps an input range, and a refused call
+ * launches nothing.  1 <= outCount <= 2^30, outFirst + outCount <= 2^55.  The handle keeps nothing of the record between calls.
+ * Asynchronous on `stream`. */
+int dpe_arr_process(dpe_arr *h, const void *const *x_dev, int64_t xFirst, int64_t xCount, int64_t recordLength, void *const *out_dev,
+                    int64_t outFirst, int64_t outCount, dpe_stream_t stream);
+/* The counters of the last process call.  Additive over any split of an output range into calls.  Synchronises with that call's
+ * stream. */
+int dpe_arr_stats(dpe_arr *h, dpe_arr_stats_t *stats);
+/* The device's own covariances and weights for the blocks [blockFirst, blockFirst + blockCount), by the device functions process
+ * runs: S_k into cov_dev (int64 [blockCount][M][M][2]), w into weights_dev (double [blockCount][B][M][2]), v into applied_dev
+ * (float [blockCount][B][M][2]); each may be NULL.  The blocks need the input samples [blockFirst L, (blockFirst + blockCount) L)
+ * cut to the record.  1 <= blockCount <= 2^24.  Leaves the counters of dpe_arr_stats alone.  Asynchronous on `stream`. */
+int dpe_arr_analyse(dpe_arr *h, const void *const *x_dev, int64_t xFirst, int64_t xCount, int64_t recordLength, int64_t blockFirst,
+                    int64_t blockCount, int64_t *cov_dev, double *weights_dev, float *applied_dev, dpe_stream_t stream);
+
 /* Timing helper for bench.py: HIP events on the stream the kernels run on. */
 int dpe_event_create(void **ev);
 int dpe_event_record(void *ev, dpe_stream_t stream);

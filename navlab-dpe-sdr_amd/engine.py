@@ -50,6 +50,7 @@ EXPORTS = [
     "dpe_cd_create", "dpe_cd_destroy", "dpe_cd_predict", "dpe_cd_update", "dpe_cd_results", "dpe_cd_map",
     "dpe_fe_create", "dpe_fe_destroy", "dpe_fe_info", "dpe_fe_convert", "dpe_fe_clipped",
     "dpe_ix_create", "dpe_ix_destroy", "dpe_ix_info", "dpe_ix_process", "dpe_ix_stats", "dpe_ix_analyse",
+    "dpe_arr_create", "dpe_arr_destroy", "dpe_arr_info", "dpe_arr_process", "dpe_arr_stats", "dpe_arr_analyse",
 ]
 
 
@@ -2357,6 +2358,125 @@ class Excisor:
     def close(self):
         if self._h:
             lib().dpe_ix_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:            # at interpreter shutdown module globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+class ArrConfig(C.Structure):       # dpe_arr_config
+    _fields_ = [("loading", C.c_double), ("gain", C.c_double), ("nElements", C.c_int32), ("blockLength", C.c_int32), ("nConstraints", C.c_int32),
+                ("reference", C.c_int32), ("outputFormat", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ArrInfo(C.Structure):         # dpe_arr_info_t
+    _fields_ = [("blockLength", C.c_int32), ("blocksPerUnit", C.c_int32), ("ldsBytes", C.c_int32), ("minSamples", C.c_int32)]
+
+
+class ArrStats(C.Structure):        # dpe_arr_stats_t
+    _fields_ = [("blocks", C.c_int64), ("fallbackBlocks", C.c_int64), ("clipped", C.c_int64)]
+
+
+L1_WAVELENGTH = 299792458.0 / 1575.42e6
+
+
+def steering_vectors(element_pos_m, los_unit, wavelength=L1_WAVELENGTH):
+    """exp(2 pi j pos . los / wavelength) as complex128 [B, M]: the phase of a plane wave from the unit vectors los_unit [B, 3]
+    (receiver to source) at the elements element_pos_m [M, 3] relative to the array's origin -- the constraints of ArrayCombiner for
+    MVDR beams toward the line-of-sight vectors the channel manager holds."""
+    pos = np.asarray(element_pos_m, dtype=np.float64).reshape(-1, 3)
+    los = np.asarray(los_unit, dtype=np.float64).reshape(-1, 3)
+    return np.exp(2j * np.pi * (los @ pos.T) / float(wavelength))
+
+
+class ArrayCombiner:
+    """Antenna array combiner on the device (dpe_arr_*, csrc/dpe_arr.hip): n_elements streams of interleaved int16 I/Q
+    to one stream per constraint, with weights adapted per block of block_length samples from the block's exact covariance, loaded
+    by `loading` times its mean diagonal.  constraints=None is power inversion: the `reference` element passes with unit weight and
+    whatever dominates the covariance is nulled; complex constraints [B, M] (steering_vectors) give B MVDR beams.  The output
+    ("i16", or "f32" for float pairs before rounding) is what Acquisition.search, the trackers and every scan take.  The handle
+    keeps nothing of the record: any split of an output range into calls gives the bytes of one call."""
+
+    def __init__(self, n_elements, block_length, constraints=None, reference=0, loading=1e-3, gain=1.0, output="i16"):
+        if output not in ("i16", "f32"):
+            raise DpeError("[ArrayCombiner] create: output %r is neither 'i16' nor 'f32'" % (output,))
+        self.M, self.L, self.out_f32 = int(n_elements), int(block_length), output == "f32"
+        cons = None
+        self.B = 1
+        if constraints is not None:
+            cons = np.ascontiguousarray(np.atleast_2d(np.asarray(constraints, dtype=np.complex128)))
+            if cons.ndim != 2 or cons.shape[1] != self.M:
+                raise DpeError("[ArrayCombiner] create: constraints of shape %s, not [B, %d]" % (tuple(cons.shape), self.M))
+            self.B = int(cons.shape[0])
+        cfg = ArrConfig(float(loading), float(gain), self.M, self.L, self.B, int(reference), 1 if self.out_f32 else 0, 0)
+        self._h = C.c_void_p(None)
+        _check(lib().dpe_arr_create(C.byref(cfg), None if cons is None else cons.ctypes.data_as(C.POINTER(C.c_double)), C.byref(self._h)))
+        info = ArrInfo()
+        _check(lib().dpe_arr_info(self._h, C.byref(info)))
+        self.blocks_per_unit, self.lds_bytes, self.min_samples = int(info.blocksPerUnit), int(info.ldsBytes), int(info.minSamples)
+
+    def info(self):
+        """dict(block_length, blocks_per_unit, lds_bytes, min_samples) of the handle"""
+        return dict(block_length=self.L, blocks_per_unit=self.blocks_per_unit, lds_bytes=self.lds_bytes, min_samples=self.min_samples)
+
+    def needed(self, first, count, record_length=None):
+        """[lo, hi): the input samples of every element the outputs [first, first + count) read, cut to the record."""
+        lo = int(first) // self.L * self.L
+        hi = ((int(first) + int(count) - 1) // self.L + 1) * self.L
+        if record_length is not None:
+            hi = min(hi, int(record_length))
+        return lo, max(hi, lo)
+
+    def _elements(self, x, x_count):
+        """-> (the host array of M device pointers, the samples each buffer holds)"""
+        xs = list(x)
+        if len(xs) != self.M:
+            raise DpeError("[ArrayCombiner] %d input buffers for %d elements" % (len(xs), self.M))
+        if x_count is None:
+            x_count = xs[0].numel() // 2
+        return (C.c_void_p * self.M)(*[_ptr(t) for t in xs]), int(x_count)
+
+    def process(self, x, x_first, out_first, out_count, record_length=None, x_count=None, out=None, stream=None):
+        """Outputs [out_first, out_first + out_count) of every constraint from `x`, a sequence of M device tensors (int16 [2 n], or
+        the rows of one [M, 2 n] tensor), each holding its element's samples from x_first on.  Asynchronous.  Returns a list of B
+        device tensors, int16 [2 out_count] or float32 [2 out_count] for "f32" (`out`: B tensors to write into)."""
+        import torch
+        ptrs, n = self._elements(x, x_count)
+        if out is None:
+            out = [torch.empty(2 * int(out_count), dtype=torch.float32 if self.out_f32 else torch.int16, device="cuda") for _ in range(self.B)]
+        outs = list(out)
+        if len(outs) != self.B:
+            raise DpeError("[ArrayCombiner] %d output buffers for %d constraints" % (len(outs), self.B))
+        optrs = (C.c_void_p * self.B)(*[_ptr(t) for t in outs])
+        _check(lib().dpe_arr_process(self._h, ptrs, C.c_int64(int(x_first)), C.c_int64(n), C.c_int64(-1 if record_length is None else int(record_length)),
+                                     optrs, C.c_int64(int(out_first)), C.c_int64(int(out_count)), _stream(stream)))
+        return outs
+
+    def stats(self):
+        """The last process call's counters: blocks, fallbackBlocks, clipped.  Synchronises."""
+        st = ArrStats()
+        _check(lib().dpe_arr_stats(self._h, C.byref(st)))
+        return dict(blocks=int(st.blocks), fallbackBlocks=int(st.fallbackBlocks), clipped=int(st.clipped))
+
+    def analyse(self, x, x_first, block_first, block_count, record_length=None, x_count=None, stream=None):
+        """The device's own (S int64 [blocks, M, M, 2], w float64 [blocks, B, M, 2], v float32 [blocks, B, M, 2]) for the blocks
+        [block_first, block_first + block_count) as device tensors: the covariances, the weights and what process applies."""
+        import torch
+        ptrs, n = self._elements(x, x_count)
+        k = max(int(block_count), 0)
+        S = torch.empty((k, self.M, self.M, 2), dtype=torch.int64, device="cuda")
+        w = torch.empty((k, self.B, self.M, 2), dtype=torch.float64, device="cuda")
+        v = torch.empty((k, self.B, self.M, 2), dtype=torch.float32, device="cuda")
+        _check(lib().dpe_arr_analyse(self._h, ptrs, C.c_int64(int(x_first)), C.c_int64(n), C.c_int64(-1 if record_length is None else int(record_length)),
+                                     C.c_int64(int(block_first)), C.c_int64(int(block_count)), _ptr(S), _ptr(w), _ptr(v), _stream(stream)))
+        return S, w, v
+
+    def close(self):
+        if self._h:
+            lib().dpe_arr_destroy(self._h)
             self._h = C.c_void_p(None)
 
     def __del__(self):
