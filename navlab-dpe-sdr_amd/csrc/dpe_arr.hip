@@ -22,7 +22,7 @@ struct ArrArgs {
     double *weights;
     float *applied;
     long long xFirst;
-    long long lo, hi;               // the input samples that exist and lie in the buffers: [0, recordLength) cut to the buffers' range
+    int64_t lo, hi;                 // the input samples that exist and lie in the buffers: [0, recordLength) cut to the buffers' range
     long long recordLength;
     long long outFirst, outEnd;
     long long k0, k1;               // the call's first and last block
@@ -174,9 +174,7 @@ __global__ __launch_bounds__(kArrThreads) void arr_kernel(ArrArgs a)
                 int xi[M], xq[M];
 #pragma unroll
                 for (int e = 0; e < M; ++e) {
-                    const int w = a.x[e][n - a.xFirst];
-                    xi[e] = (short)(w & 0xFFFF);
-                    xq[e] = w >> 16;
+                    stream_unpack(a.x[e][n - a.xFirst], xi[e], xq[e]);
                 }
 #pragma unroll
                 for (int e = 0; e < M; ++e) {
@@ -262,20 +260,11 @@ __global__ __launch_bounds__(kArrThreads) void arr_kernel(ArrArgs a)
                 const bool in = n >= a.lo && n < a.hi;
 #pragma unroll
                 for (int e = 0; e < M; ++e) {
-                    const int w = in ? a.x[e][n - a.xFirst] : 0;
-                    xi[e] = (float)(short)(w & 0xFFFF);
-                    xq[e] = (float)(w >> 16);
+                    stream_unpack(in ? a.x[e][n - a.xFirst] : 0, xi[e], xq[e]);
                 }
                 float re, im;
                 arr_apply(M, vr, vi, xi, xq, re, im);
-                if (a.outF32) {
-                    reinterpret_cast<float2 *>(a.out[b])[n - a.outFirst] = float2{re, im};
-                } else {
-                    const float ri = rintf(re), rq = rintf(im);
-                    nClipped += (ri < -32768.f || ri > 32767.f) + (rq < -32768.f || rq > 32767.f);
-                    const int qi = (int)fminf(fmaxf(ri, -32768.f), 32767.f), qq = (int)fminf(fmaxf(rq, -32768.f), 32767.f);
-                    reinterpret_cast<int *>(a.out[b])[n - a.outFirst] = (qi & 0xFFFF) | (qq << 16);
-                }
+                stream_store(a.out[b], n - a.outFirst, re, im, a.outF32, nClipped);
             }
         }
     }
@@ -309,7 +298,7 @@ static ArrArgs arr_args(const dpe_arr *h, const void *const *x_dev, int64_t xFir
     a.xFirst = xFirst;
     a.lo = xFirst;
     a.hi = xFirst + xCount;
-    if (recordLength >= 0 && a.hi > recordLength) a.hi = recordLength;
+    stream_cut(recordLength, a.lo, a.hi);
     a.recordLength = recordLength;
     a.loading = h->cfg.loading;
     a.gain = h->cfg.gain;
@@ -419,8 +408,7 @@ int dpe_arr_stats(dpe_arr *h, dpe_arr_stats_t *stats)
 {
     DPE_REQUIRE(h && stats, "[ArrayCombiner] stats: null argument");
     unsigned long long v[4] = {};
-    DPE_CHECK_HIP(hipMemcpyAsync(v, h->counters_d, sizeof(v), hipMemcpyDeviceToHost, h->last));
-    DPE_CHECK_HIP(hipStreamSynchronize(h->last));
+    if (read_counters(v, h->counters_d, 4, h->last)) return -1;
     stats->blocks = (int64_t)v[0];
     stats->fallbackBlocks = (int64_t)v[1];
     stats->clipped = (int64_t)v[2];

@@ -228,6 +228,14 @@ static inline void upload_params(void *dst_dev, const void *src_pinned_devptr, s
 }
 #endif
 
+// n counters of a handle read back behind everything its last call enqueued on `st`; -1 with the error set
+static inline int read_counters(unsigned long long *host, const unsigned long long *dev, size_t n, hipStream_t st)
+{
+    DPE_CHECK_HIP(hipMemcpyAsync(host, dev, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    DPE_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 template <typename T>
 static inline T *dev_alloc(size_t n)
 {

@@ -22,7 +22,7 @@ struct FeArgs {
     unsigned long long *clipped;
     unsigned long long magic;
     long long rawFirst;
-    long long lo, hi;           // the input samples that exist and lie in the buffer: [0, recordLength) cut to the buffer's range
+    int64_t lo, hi;             // the input samples that exist and lie in the buffer: [0, recordLength) cut to the buffer's range
     long long outFirst;
     int outCount, D, T0, Q, rem, tileOut, rowLen, pitch, qPitch;
     int format, outF32;
@@ -41,8 +41,9 @@ template <int FMT>
 __device__ __forceinline__ fe2 fe_load(const FeArgs &a, long long rel)
 {
     if constexpr (FMT == DPE_FE_I16C) {
-        const int v = reinterpret_cast<const int *>(a.raw)[rel];
-        return fe2{(float)(short)(v & 0xFFFF), (float)(v >> 16)};
+        float i, q;
+        stream_unpack(reinterpret_cast<const int *>(a.raw)[rel], i, q);
+        return fe2{i, q};
     } else if constexpr (FMT == DPE_FE_I8C) {
         const int v = reinterpret_cast<const unsigned short *>(a.raw)[rel];
         return fe2{(float)(signed char)(v & 0xFF), (float)(signed char)(v >> 8)};
@@ -198,15 +199,7 @@ __global__ __launch_bounds__(kFeThreads) void fe_kernel(FeArgs a)
             const float c = fmaf(-s0, b, c0), s = fmaf(c0, b, s0);
             y = fe2{fmaf(acc[r].y, s, acc[r].x * c), fmaf(-acc[r].x, s, acc[r].y * c)};
         }
-        const long long o = i0 + k0 + r;
-        if (a.outF32) {
-            reinterpret_cast<fe2 *>(a.out)[o] = y;
-        } else {
-            const float ri = rintf(y.x), rq = rintf(y.y);
-            nClip += (ri < -32768.f || ri > 32767.f) + (rq < -32768.f || rq > 32767.f);
-            const int qi = (int)fminf(fmaxf(ri, -32768.f), 32767.f), qq = (int)fminf(fmaxf(rq, -32768.f), 32767.f);
-            reinterpret_cast<int *>(a.out)[o] = (qi & 0xFFFF) | (qq << 16);
-        }
+        stream_store(a.out, i0 + k0 + r, y.x, y.y, a.outF32, nClip);
     }
     if (nClip) atomicAdd(a.clipped, (unsigned long long)nClip);
 }
@@ -302,9 +295,9 @@ int dpe_fe_convert(dpe_fe *h, const void *raw_dev, int64_t rawFirstSample, int64
     a.clipped = h->clipped_d;
     a.magic = g.magic;
     a.rawFirst = rawFirstSample;
-    a.lo = rawFirstSample > 0 ? rawFirstSample : 0;
+    a.lo = rawFirstSample;
     a.hi = rawFirstSample + rawCount;
-    if (recordLength >= 0 && a.hi > recordLength) a.hi = recordLength;
+    stream_cut(recordLength, a.lo, a.hi);
     a.outFirst = outFirst;
     a.outCount = (int)outCount;
     a.D = g.D;
@@ -335,8 +328,7 @@ int dpe_fe_clipped(dpe_fe *h, int64_t *count)
 {
     DPE_REQUIRE(h && count, "[FrontEnd] clipped: null argument");
     unsigned long long v = 0;
-    DPE_CHECK_HIP(hipMemcpyAsync(&v, h->clipped_d, sizeof(v), hipMemcpyDeviceToHost, h->last));
-    DPE_CHECK_HIP(hipStreamSynchronize(h->last));
+    if (read_counters(&v, h->clipped_d, 1, h->last)) return -1;
     *count = (int64_t)v;
     return 0;
 }

@@ -1,25 +1,17 @@
 // dpe_fe_plan.h -- the front end's host-side planning as plain C++: the phase word of the mixer, the input range a range of outputs
 // needs, the tile geometry (which block, lane and slot owns an output, where a staged input sample lies in the LDS, how many bytes
 // that takes), the modulated tap table the kernel reads, and every refusal with its message.  Nothing of HIP is included:
-// dpe_fe.hip passes sizes and alignments in, the kernel calls the same index functions (DPE_FE_HD), and host/test_fe_plan.cpp holds
-// them to their properties with a plain C++ compiler.  DESIGN.md 7h.
+// dpe_fe.hip passes sizes and alignments in, the kernel calls the same index functions (DPE_STREAM_HD), and host/test_fe_plan.cpp
+// holds them to their properties with a plain C++ compiler.  The index limits, the record cut and the refusals every stream stage
+// makes are dpe_stream_plan.h's.  DESIGN.md 7h.
 //
 // The stage:  y[m] = gain sum_t h[t] z[m D + t - T0],  z[n] = x[n] exp(-2 pi j ((n delta) mod 2^32) / 2^32),  T0 = (T - 1) / 2.
 // The phase word is additive modulo 2^32, so  z-phase(m D + t - T0) = phase(m D - T0) + phase(t)  exactly: the kernel sums
 // x[...] c[t] with the modulated taps c[t] = gain h[t] exp(-j phase(t)) (fp64 here, held as fp32) and rotates each output once.
 #pragma once
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <vector>
 
-#include "../../include/dpe_hip.h"
-
-#if defined(__HIPCC__)
-#define DPE_FE_HD __host__ __device__ inline
-#else
-#define DPE_FE_HD inline
-#endif
+#include "dpe_stream_plan.h"
 
 namespace dpe {
 
@@ -28,8 +20,6 @@ constexpr int kFeRun = 5;                   // consecutive outputs per lane; odd
 constexpr int kFeMaxD = 64;
 constexpr int kFeMaxT = 1023;
 constexpr int kFeLdsBytes = 32 * 1024;      // the staged tile's upper limit: five blocks per CU keep enough loads in flight
-constexpr int64_t kFeMaxCount = INT64_C(1) << 30;    // outputs per call
-constexpr int64_t kFeMaxIndex = INT64_C(1) << 55;    // every output index of a call lies below it: (index + count) D + T stays far inside 64 bits
 
 enum FeMode { kFeRealIn = 0, kFeComplex = 1, kFeComplexMix = 2 };   // what the tap loop multiplies (fe_taps)
 
@@ -56,7 +46,7 @@ inline uint32_t fe_delta(double fIF, double fsIn)
     return (uint32_t)(uint64_t)r;
 }
 // the mixer's phase word of input sample n: (n delta) mod 2^32, exact for any n (two's complement below zero)
-DPE_FE_HD uint32_t fe_phase(int64_t n, uint32_t delta) { return (uint32_t)((uint64_t)n * (uint64_t)delta); }
+DPE_STREAM_HD uint32_t fe_phase(int64_t n, uint32_t delta) { return (uint32_t)((uint64_t)n * (uint64_t)delta); }
 // the frequency delta realises, in (-fs/2, fs/2]
 inline double fe_realised_if(uint32_t delta, double fsIn)
 {
@@ -83,9 +73,7 @@ inline void fe_needed(int64_t outFirst, int64_t outCount, int D, int T, int64_t 
     const int T0 = (T - 1) / 2;
     lo = outFirst * D - T0;
     hi = (outFirst + outCount - 1) * D + T - T0;
-    if (lo < 0) lo = 0;
-    if (recordLength >= 0 && hi > recordLength) hi = recordLength;
-    if (hi < lo) hi = lo;
+    stream_cut(recordLength, lo, hi);
 }
 
 // ---- tile geometry.  A block owns tileOut consecutive outputs of the call, lane l of it the outputs l kFeRun .. l kFeRun +
@@ -124,15 +112,15 @@ inline FeGeom fe_geom(int D, int T, bool realIn)
     g.magic = 4294967296ULL / (uint64_t)D + 1ULL;
     return g;
 }
-DPE_FE_HD int fe_phase_taps(int p, int Q, int rem) { return p < rem ? Q : Q - 1; }
+DPE_STREAM_HD int fe_phase_taps(int p, int Q, int rem) { return p < rem ? Q : Q - 1; }
 // staged input i of a tile -> its row position k = i / D and phase p = i mod D
-DPE_FE_HD void fe_split(uint32_t i, int D, uint64_t magic, int &k, int &p)
+DPE_STREAM_HD void fe_split(uint32_t i, int D, uint64_t magic, int &k, int &p)
 {
     k = (int)(((uint64_t)i * magic) >> 32);
     p = (int)i - k * D;
 }
 // the same for staged input i + kFeThreads, from (k, p) of input i: kStep = kFeThreads / D, pStep = kFeThreads mod D
-DPE_FE_HD void fe_advance(int &k, int &p, int D, int kStep, int pStep)
+DPE_STREAM_HD void fe_advance(int &k, int &p, int D, int kStep, int pStep)
 {
     k += kStep;
     p += pStep;
@@ -174,31 +162,22 @@ inline std::vector<float> fe_taps(const FeGeom &g, FeMode mode, uint32_t delta, 
 }
 
 // ---- what is refused before anything is allocated or launched.  true: refused, `msg` holds the reason.
-#define DPE_FE_REFUSE(cond, ...)                 \
-    do {                                         \
-        if (cond) {                              \
-            snprintf(msg, len, __VA_ARGS__);     \
-            return true;                         \
-        }                                        \
-    } while (0)
-
 inline bool fe_config_problem(const dpe_fe_config *cfg, const double *taps, char *msg, size_t len)
 {
-    DPE_FE_REFUSE(!cfg || !taps, "[FrontEnd] create: null argument");
+    DPE_STREAM_REFUSE(!cfg || !taps, "[FrontEnd] create: null argument");
     int num, den;
     bool realIn;
-    DPE_FE_REFUSE(!fe_format(cfg->format, num, den, realIn), "[FrontEnd] create: input format %d is none of DPE_FE_I16C .. DPE_FE_P2C", cfg->format);
-    DPE_FE_REFUSE(cfg->outputFormat != DPE_FE_OUT_I16 && cfg->outputFormat != DPE_FE_OUT_F32,
-                  "[FrontEnd] create: output format %d is neither DPE_FE_OUT_I16 nor DPE_FE_OUT_F32", cfg->outputFormat);
-    DPE_FE_REFUSE(cfg->decimation < 1 || cfg->decimation > kFeMaxD, "[FrontEnd] create: decimation D = %d outside 1..%d", cfg->decimation, kFeMaxD);
-    DPE_FE_REFUSE(cfg->nTaps < 1 || cfg->nTaps > kFeMaxT, "[FrontEnd] create: T = %d taps outside 1..%d", cfg->nTaps, kFeMaxT);
-    DPE_FE_REFUSE(cfg->nTaps % 2 == 0, "[FrontEnd] create: T = %d taps is even (the group delay (T - 1) / 2 has to be whole samples)", cfg->nTaps);
-    DPE_FE_REFUSE(!(std::isfinite(cfg->samplingFrequency) && cfg->samplingFrequency > 0.0), "[FrontEnd] create: sampling frequency not positive");
-    DPE_FE_REFUSE(!(std::isfinite(cfg->intermediateFrequency) && std::fabs(cfg->intermediateFrequency) <= cfg->samplingFrequency),
-                  "[FrontEnd] create: intermediate frequency not finite or beyond the sampling frequency");
-    DPE_FE_REFUSE(!std::isfinite(cfg->gain), "[FrontEnd] create: gain not finite");
-    for (int i = 0; i < 4; ++i) DPE_FE_REFUSE(!std::isfinite(cfg->levels[i]), "[FrontEnd] create: level %d not finite", i);
-    for (int t = 0; t < cfg->nTaps; ++t) DPE_FE_REFUSE(!std::isfinite(taps[t]), "[FrontEnd] create: tap %d not finite", t);
+    DPE_STREAM_REFUSE(!fe_format(cfg->format, num, den, realIn), "[FrontEnd] create: input format %d is none of DPE_FE_I16C .. DPE_FE_P2C", cfg->format);
+    if (stream_format_problem("[FrontEnd]", "create", cfg->outputFormat, msg, len)) return true;
+    DPE_STREAM_REFUSE(cfg->decimation < 1 || cfg->decimation > kFeMaxD, "[FrontEnd] create: decimation D = %d outside 1..%d", cfg->decimation, kFeMaxD);
+    DPE_STREAM_REFUSE(cfg->nTaps < 1 || cfg->nTaps > kFeMaxT, "[FrontEnd] create: T = %d taps outside 1..%d", cfg->nTaps, kFeMaxT);
+    DPE_STREAM_REFUSE(cfg->nTaps % 2 == 0, "[FrontEnd] create: T = %d taps is even (the group delay (T - 1) / 2 has to be whole samples)", cfg->nTaps);
+    DPE_STREAM_REFUSE(!(std::isfinite(cfg->samplingFrequency) && cfg->samplingFrequency > 0.0), "[FrontEnd] create: sampling frequency not positive");
+    DPE_STREAM_REFUSE(!(std::isfinite(cfg->intermediateFrequency) && std::fabs(cfg->intermediateFrequency) <= cfg->samplingFrequency),
+                      "[FrontEnd] create: intermediate frequency not finite or beyond the sampling frequency");
+    if (stream_gain_problem("[FrontEnd]", "create", cfg->gain, msg, len)) return true;
+    for (int i = 0; i < 4; ++i) DPE_STREAM_REFUSE(!std::isfinite(cfg->levels[i]), "[FrontEnd] create: level %d not finite", i);
+    for (int t = 0; t < cfg->nTaps; ++t) DPE_STREAM_REFUSE(!std::isfinite(taps[t]), "[FrontEnd] create: tap %d not finite", t);
     return false;
 }
 
@@ -206,28 +185,20 @@ inline bool fe_config_problem(const dpe_fe_config *cfg, const double *taps, char
 inline bool fe_convert_problem(const dpe_fe_config &cfg, bool rawNull, bool outNull, unsigned rawAlign, unsigned outAlign, int64_t rawFirst,
                                int64_t rawCount, int64_t recordLength, int64_t outFirst, int64_t outCount, char *msg, size_t len)
 {
-    DPE_FE_REFUSE(rawNull || outNull, "[FrontEnd] convert: null %s buffer", rawNull ? "input" : "output");
+    DPE_STREAM_REFUSE(rawNull || outNull, "[FrontEnd] convert: null %s buffer", rawNull ? "input" : "output");
     int num = 1, den = 1;
     bool realIn = false;
     (void)fe_format(cfg.format, num, den, realIn);
     const unsigned outBytes = cfg.outputFormat == DPE_FE_OUT_F32 ? 8u : 4u;
-    DPE_FE_REFUSE(outAlign % outBytes != 0, "[FrontEnd] convert: the output is not aligned to an I/Q pair (%u bytes)", outBytes);
-    DPE_FE_REFUSE(den == 1 && rawAlign % (unsigned)num != 0, "[FrontEnd] convert: the input is not aligned to a sample (%d bytes)", num);
-    DPE_FE_REFUSE(outCount < 1 || outCount > kFeMaxCount, "[FrontEnd] convert: %lld outputs outside 1..2^30 per call", (long long)outCount);
-    DPE_FE_REFUSE(outFirst < 0 || outFirst > kFeMaxIndex - outCount, "[FrontEnd] convert: first output %lld with %lld outputs outside 0..2^55",
-                  (long long)outFirst, (long long)outCount);
-    DPE_FE_REFUSE(rawFirst < 0 || rawCount < 0 || rawFirst > (INT64_C(1) << 61) || rawCount > (INT64_C(1) << 61),
-                  "[FrontEnd] convert: input range %lld + %lld negative or beyond 2^61", (long long)rawFirst, (long long)rawCount);
-    DPE_FE_REFUSE(recordLength < -1, "[FrontEnd] convert: record length %lld (-1: no end)", (long long)recordLength);
-    DPE_FE_REFUSE(rawFirst % den != 0, "[FrontEnd] convert: the buffer's first sample %lld is not on a byte boundary (%d samples per byte)",
-                  (long long)rawFirst, den);
+    DPE_STREAM_REFUSE(outAlign % outBytes != 0, "[FrontEnd] convert: the output is not aligned to an I/Q pair (%u bytes)", outBytes);
+    DPE_STREAM_REFUSE(den == 1 && rawAlign % (unsigned)num != 0, "[FrontEnd] convert: the input is not aligned to a sample (%d bytes)", num);
+    if (stream_outputs_problem("[FrontEnd]", "convert", outFirst, outCount, msg, len)) return true;
+    if (stream_held_problem("[FrontEnd]", "convert", rawFirst, rawCount, recordLength, msg, len)) return true;
+    DPE_STREAM_REFUSE(rawFirst % den != 0, "[FrontEnd] convert: the buffer's first sample %lld is not on a byte boundary (%d samples per byte)",
+                      (long long)rawFirst, den);
     int64_t lo, hi;
     fe_needed(outFirst, outCount, cfg.decimation, cfg.nTaps, recordLength, lo, hi);
-    DPE_FE_REFUSE(lo < hi && (lo < rawFirst || hi > rawFirst + rawCount),
-                  "[FrontEnd] convert: outputs %lld..%lld need the input samples %lld..%lld, the buffer holds %lld..%lld", (long long)outFirst,
-                  (long long)(outFirst + outCount - 1), (long long)lo, (long long)(hi - 1), (long long)rawFirst, (long long)(rawFirst + rawCount - 1));
-    return false;
+    return stream_coverage_problem("[FrontEnd]", "convert", "outputs", "the buffer holds", outFirst, outCount, lo, hi, rawFirst, rawCount, msg, len);
 }
-#undef DPE_FE_REFUSE
 
 }  // namespace dpe

@@ -26,7 +26,7 @@ struct IxArgs {
     float *power, *median;      // analyse: [frames][N], [frames], [frames][N]; each may be null
     uint8_t *mask;
     long long xFirst;
-    long long lo, hi;           // the input samples that exist and lie in the buffer: [0, recordLength) cut to the buffer's range
+    int64_t lo, hi;             // the input samples that exist and lie in the buffer: [0, recordLength) cut to the buffer's range
     long long outFirst, outEnd;
     long long h0, h1;           // the call's first and last hop (analyse: its first and last frame)
     int N, H, logN, guard, inF32, outF32, analyse;
@@ -187,8 +187,8 @@ __global__ __launch_bounds__(kIxThreads) void ix_kernel(IxArgs a)
                     v = reinterpret_cast<const ix2 *>(a.x)[n - a.xFirst];
                     blank = a.blankPower > 0.f && ix_power(v) > a.blankPower;
                 } else {
-                    const int w = reinterpret_cast<const int *>(a.x)[n - a.xFirst];
-                    const int vi = (short)(w & 0xFFFF), vq = w >> 16;
+                    int vi, vq;
+                    stream_unpack(reinterpret_cast<const int *>(a.x)[n - a.xFirst], vi, vq);
                     v = ix2{(float)vi, (float)vq};
                     blank = a.blankWord != 0u && (unsigned)(vi * vi) + (unsigned)(vq * vq) > a.blankWord;
                 }
@@ -248,14 +248,7 @@ __global__ __launch_bounds__(kIxThreads) void ix_kernel(IxArgs a)
                     const ix2 y = s[r];
                     const ix2 t = ix2{__fmul_rn(w, __fmul_rn(y.x, a.invN)), __fmul_rn(w, __fmul_rn(y.y, a.invN))};
                     const ix2 o = ix2{__fmul_rn(a.gain, __fadd_rn(carry[m].x, t.x)), __fmul_rn(a.gain, __fadd_rn(carry[m].y, t.y))};
-                    if (a.outF32) {
-                        reinterpret_cast<ix2 *>(a.out)[n - a.outFirst] = o;
-                    } else {
-                        const float ri = rintf(o.x), rq = rintf(o.y);
-                        nClipped += (ri < -32768.f || ri > 32767.f) + (rq < -32768.f || rq > 32767.f);
-                        const int qi = (int)fminf(fmaxf(ri, -32768.f), 32767.f), qq = (int)fminf(fmaxf(rq, -32768.f), 32767.f);
-                        reinterpret_cast<int *>(a.out)[n - a.outFirst] = (qi & 0xFFFF) | (qq << 16);
-                    }
+                    stream_store(a.out, n - a.outFirst, o.x, o.y, a.outF32, nClipped);
                 }
                 const float w2 = a.win[r + H];
                 const ix2 y2 = s[r + H];
@@ -303,7 +296,7 @@ static IxArgs ix_args(const dpe_ix *h, const void *x_dev, int64_t xFirst, int64_
     a.xFirst = xFirst;
     a.lo = xFirst;
     a.hi = xFirst + xCount;
-    if (recordLength >= 0 && a.hi > recordLength) a.hi = recordLength;
+    stream_cut(recordLength, a.lo, a.hi);
     a.N = h->N;
     a.H = h->N / 2;
     a.logN = ix_log2(h->N);
@@ -408,8 +401,7 @@ int dpe_ix_stats(dpe_ix *h, dpe_ix_stats_t *stats, int64_t *perBin)
 {
     DPE_REQUIRE(h && stats, "[Excisor] stats: null argument");
     std::vector<unsigned long long> v((size_t)(4 + h->N));
-    DPE_CHECK_HIP(hipMemcpyAsync(v.data(), h->counters_d, v.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->last));
-    DPE_CHECK_HIP(hipStreamSynchronize(h->last));
+    if (read_counters(v.data(), h->counters_d, v.size(), h->last)) return -1;
     stats->frames = (int64_t)v[0];
     stats->excisedBins = (int64_t)v[1];
     stats->blanked = (int64_t)v[2];

@@ -2214,11 +2214,44 @@ class FeInfo(C.Structure):          # dpe_fe_info_t
 FE_FORMATS = {"I16C": 0, "I8C": 1, "I16R": 2, "I8R": 3, "ARGPI4": 4, "P2R": 5, "P2C": 6}      # DPE_FE_*
 
 
-class FrontEnd:
+class _StreamStage:
+    """What FrontEnd, Excisor and ArrayCombiner share (csrc/dpe_stream_plan.h): the end of the handle, the output tensors, the record
+    length as the C ABI takes it, and the record cut that ends needed().  A subclass names its destroy symbol and sets out_f32."""
+    _destroy = None
+
+    def _new_out(self, out_count):
+        import torch
+        return torch.empty(2 * int(out_count), dtype=torch.float32 if self.out_f32 else torch.int16, device="cuda")
+
+    @staticmethod
+    def _record(record_length):
+        return C.c_int64(-1 if record_length is None else int(record_length))
+
+    @staticmethod
+    def _cut(lo, hi, record_length):
+        if record_length is not None:
+            hi = min(hi, int(record_length))
+        lo = max(lo, 0)
+        return lo, max(hi, lo)
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:            # at interpreter shutdown module globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+class FrontEnd(_StreamStage):
     """Raw record bytes on the device to interleaved int16 I/Q at zero IF and fs_in / D (dpe_fe_*, csrc/dpe_fe.hip):
     unpack, mix by the integer phase word, low-pass with the caller's odd-length taps, decimate.  The output is a torch int16
     tensor on the device that Acquisition.search, the trackers and every scan take as it is (out_f32: float pairs before
     rounding).  The handle keeps nothing of the record: any split of an output range into calls gives the bytes of one call."""
+    _destroy = "dpe_fe_destroy"
 
     def __init__(self, fs_in, fmt, D, taps, gain=1.0, f_if=0.0, levels=(-3.0, -1.0, 1.0, 3.0), out_f32=False):
         if isinstance(fmt, str):
@@ -2238,23 +2271,18 @@ class FrontEnd:
 
     def needed(self, out_first, out_count, record_length=None):
         """[lo, hi): the input samples the outputs [out_first, out_first + out_count) read, cut to the record."""
-        lo = max(int(out_first) * self.D - self.T0, 0)
-        hi = (int(out_first) + int(out_count) - 1) * self.D + self.T - self.T0
-        if record_length is not None:
-            hi = min(hi, int(record_length))
-        return lo, max(hi, lo)
+        return self._cut(int(out_first) * self.D - self.T0, (int(out_first) + int(out_count) - 1) * self.D + self.T - self.T0, record_length)
 
     def convert(self, raw, raw_first, out_first, out_count, record_length=None, raw_count=None, out=None, stream=None):
         """Outputs [out_first, out_first + out_count) from `raw`, a device tensor holding the record's input samples from
         raw_first on (raw_count of them; default: all its bytes hold).  Asynchronous.  Returns int16 [2 out_count], or float32
         [2 out_count] for out_f32."""
-        import torch
         if raw_count is None:
             raw_count = raw.numel() * raw.element_size() * self.bytes_den // self.bytes_num
         if out is None:
-            out = torch.empty(2 * int(out_count), dtype=torch.float32 if self.out_f32 else torch.int16, device="cuda")
+            out = self._new_out(out_count)
         _check(lib().dpe_fe_convert(self._h, _ptr(raw), C.c_int64(int(raw_first)), C.c_int64(int(raw_count)),
-                                    C.c_int64(-1 if record_length is None else int(record_length)), _ptr(out), C.c_int64(int(out_first)),
+                                    self._record(record_length), _ptr(out), C.c_int64(int(out_first)),
                                     C.c_int64(int(out_count)), _stream(stream)))
         return out
 
@@ -2263,17 +2291,6 @@ class FrontEnd:
         n = C.c_int64(0)
         _check(lib().dpe_fe_clipped(self._h, C.byref(n)))
         return int(n.value)
-
-    def close(self):
-        if self._h:
-            lib().dpe_fe_destroy(self._h)
-            self._h = C.c_void_p(None)
-
-    def __del__(self):
-        try:            # at interpreter shutdown module globals may already be gone
-            self.close()
-        except Exception:
-            pass
 
 
 class IxConfig(C.Structure):        # dpe_ix_config
@@ -2290,12 +2307,13 @@ class IxStats(C.Structure):         # dpe_ix_stats_t
     _fields_ = [("frames", C.c_int64), ("excisedBins", C.c_int64), ("blanked", C.c_int64), ("clipped", C.c_int64)]
 
 
-class Excisor:
+class Excisor(_StreamStage):
     """Interference excision on complex baseband samples on the device (dpe_ix_*, csrc/dpe_ix.hip): a pulse blanker,
     then frames of N samples at a hop of N / 2 whose bins above `threshold` times the frame's lower median power (widened by
     `guard`, plus the always-excised `static_mask`) are set to zero before the frame is put back.  Takes and gives interleaved
     int16 I/Q (in_f32 / out_f32: float pairs) at the same rate, so it sits between FrontEnd.convert and every other stage.  The
     handle keeps nothing of the record: any split of an output range into calls gives the bytes of one call."""
+    _destroy = "dpe_ix_destroy"
 
     def __init__(self, N, threshold, guard=1, blank_power=0.0, gain=1.0, static_mask=None, in_f32=False, out_f32=False):
         self.N, self.in_f32, self.out_f32 = int(N), bool(in_f32), bool(out_f32)
@@ -2315,11 +2333,7 @@ class Excisor:
     def needed(self, out_first, out_count, record_length=None):
         """[lo, hi): the input samples the outputs [out_first, out_first + out_count) read, cut to the record."""
         H = self.N // 2
-        lo = max((int(out_first) // H - 1) * H, 0)
-        hi = ((int(out_first) + int(out_count) - 1) // H + 2) * H
-        if record_length is not None:
-            hi = min(hi, int(record_length))
-        return lo, max(hi, lo)
+        return self._cut((int(out_first) // H - 1) * H, ((int(out_first) + int(out_count) - 1) // H + 2) * H, record_length)
 
     def _count(self, x, x_count):
         return x.numel() // 2 if x_count is None else int(x_count)
@@ -2327,11 +2341,10 @@ class Excisor:
     def process(self, x, x_first, out_first, out_count, record_length=None, x_count=None, out=None, stream=None):
         """Outputs [out_first, out_first + out_count) from `x`, a device tensor (int16 or float32 [2 n]) holding the record's samples
         from x_first on.  Asynchronous.  Returns int16 [2 out_count], or float32 [2 out_count] for out_f32."""
-        import torch
         if out is None:
-            out = torch.empty(2 * int(out_count), dtype=torch.float32 if self.out_f32 else torch.int16, device="cuda")
+            out = self._new_out(out_count)
         _check(lib().dpe_ix_process(self._h, _ptr(x), C.c_int64(int(x_first)), C.c_int64(self._count(x, x_count)),
-                                    C.c_int64(-1 if record_length is None else int(record_length)), _ptr(out), C.c_int64(int(out_first)),
+                                    self._record(record_length), _ptr(out), C.c_int64(int(out_first)),
                                     C.c_int64(int(out_count)), _stream(stream)))
         return out
 
@@ -2351,20 +2364,9 @@ class Excisor:
         m = torch.empty(n, dtype=torch.float32, device="cuda")
         e = torch.empty((n, self.N), dtype=torch.uint8, device="cuda")
         _check(lib().dpe_ix_analyse(self._h, _ptr(x), C.c_int64(int(x_first)), C.c_int64(self._count(x, x_count)),
-                                    C.c_int64(-1 if record_length is None else int(record_length)), C.c_int64(int(frame_first)),
+                                    self._record(record_length), C.c_int64(int(frame_first)),
                                     C.c_int64(int(frame_count)), _ptr(P), _ptr(m), _ptr(e), _stream(stream)))
         return P, m, e
-
-    def close(self):
-        if self._h:
-            lib().dpe_ix_destroy(self._h)
-            self._h = C.c_void_p(None)
-
-    def __del__(self):
-        try:            # at interpreter shutdown module globals may already be gone
-            self.close()
-        except Exception:
-            pass
 
 
 class ArrConfig(C.Structure):       # dpe_arr_config
@@ -2392,13 +2394,14 @@ def steering_vectors(element_pos_m, los_unit, wavelength=L1_WAVELENGTH):
     return np.exp(2j * np.pi * (los @ pos.T) / float(wavelength))
 
 
-class ArrayCombiner:
+class ArrayCombiner(_StreamStage):
     """Antenna array combiner on the device (dpe_arr_*, csrc/dpe_arr.hip): n_elements streams of interleaved int16 I/Q
     to one stream per constraint, with weights adapted per block of block_length samples from the block's exact covariance, loaded
     by `loading` times its mean diagonal.  constraints=None is power inversion: the `reference` element passes with unit weight and
     whatever dominates the covariance is nulled; complex constraints [B, M] (steering_vectors) give B MVDR beams.  The output
     ("i16", or "f32" for float pairs before rounding) is what Acquisition.search, the trackers and every scan take.  The handle
     keeps nothing of the record: any split of an output range into calls gives the bytes of one call."""
+    _destroy = "dpe_arr_destroy"
 
     def __init__(self, n_elements, block_length, constraints=None, reference=0, loading=1e-3, gain=1.0, output="i16"):
         if output not in ("i16", "f32"):
@@ -2424,11 +2427,7 @@ class ArrayCombiner:
 
     def needed(self, first, count, record_length=None):
         """[lo, hi): the input samples of every element the outputs [first, first + count) read, cut to the record."""
-        lo = int(first) // self.L * self.L
-        hi = ((int(first) + int(count) - 1) // self.L + 1) * self.L
-        if record_length is not None:
-            hi = min(hi, int(record_length))
-        return lo, max(hi, lo)
+        return self._cut(int(first) // self.L * self.L, ((int(first) + int(count) - 1) // self.L + 1) * self.L, record_length)
 
     def _elements(self, x, x_count):
         """-> (the host array of M device pointers, the samples each buffer holds)"""
@@ -2443,15 +2442,14 @@ class ArrayCombiner:
         """Outputs [out_first, out_first + out_count) of every constraint from `x`, a sequence of M device tensors (int16 [2 n], or
         the rows of one [M, 2 n] tensor), each holding its element's samples from x_first on.  Asynchronous.  Returns a list of B
         device tensors, int16 [2 out_count] or float32 [2 out_count] for "f32" (`out`: B tensors to write into)."""
-        import torch
         ptrs, n = self._elements(x, x_count)
         if out is None:
-            out = [torch.empty(2 * int(out_count), dtype=torch.float32 if self.out_f32 else torch.int16, device="cuda") for _ in range(self.B)]
+            out = [self._new_out(out_count) for _ in range(self.B)]
         outs = list(out)
         if len(outs) != self.B:
             raise DpeError("[ArrayCombiner] %d output buffers for %d constraints" % (len(outs), self.B))
         optrs = (C.c_void_p * self.B)(*[_ptr(t) for t in outs])
-        _check(lib().dpe_arr_process(self._h, ptrs, C.c_int64(int(x_first)), C.c_int64(n), C.c_int64(-1 if record_length is None else int(record_length)),
+        _check(lib().dpe_arr_process(self._h, ptrs, C.c_int64(int(x_first)), C.c_int64(n), self._record(record_length),
                                      optrs, C.c_int64(int(out_first)), C.c_int64(int(out_count)), _stream(stream)))
         return outs
 
@@ -2470,20 +2468,9 @@ class ArrayCombiner:
         S = torch.empty((k, self.M, self.M, 2), dtype=torch.int64, device="cuda")
         w = torch.empty((k, self.B, self.M, 2), dtype=torch.float64, device="cuda")
         v = torch.empty((k, self.B, self.M, 2), dtype=torch.float32, device="cuda")
-        _check(lib().dpe_arr_analyse(self._h, ptrs, C.c_int64(int(x_first)), C.c_int64(n), C.c_int64(-1 if record_length is None else int(record_length)),
+        _check(lib().dpe_arr_analyse(self._h, ptrs, C.c_int64(int(x_first)), C.c_int64(n), self._record(record_length),
                                      C.c_int64(int(block_first)), C.c_int64(int(block_count)), _ptr(S), _ptr(w), _ptr(v), _stream(stream)))
         return S, w, v
-
-    def close(self):
-        if self._h:
-            lib().dpe_arr_destroy(self._h)
-            self._h = C.c_void_p(None)
-
-    def __del__(self):
-        try:            # at interpreter shutdown module globals may already be gone
-            self.close()
-        except Exception:
-            pass
 
 
 class HipEventTimer:

@@ -12,6 +12,7 @@
 //     taps D T mode                      -> the whole table [D][qPitch][4] of mode 0, 1 or 2 as hex floats, for gain 1, delta 0 and h[t] = t + 1
 //     cfg fmt out D T fs fIF             -> the refusal of dpe_fe_create's checks, or "ok"
 //     conv fmt D T rawFirst rawCount len outFirst outCount rawAlign outAlign -> the refusal of dpe_fe_convert's checks, or "ok"
+//     quant re im                        -> the int16 I/Q word of the fp32 pair (dpe_stream_plan.h) and the components it clipped
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -191,6 +192,10 @@ int main(int argc, char **argv)
         } else if (!strcmp(w[0], "conv") && n == 11) {
             const dpe_fe_config c = config((int)I(1), 0, (int)I(2), (int)I(3), 1.0e7, 0.0);
             printf("%s\n", fe_convert_problem(c, false, false, (unsigned)I(9), (unsigned)I(10), I(4), I(5), I(6), I(7), I(8), msg, sizeof(msg)) ? msg : "ok");
+        } else if (!strcmp(w[0], "quant") && n == 3) {
+            unsigned clipped = 0;
+            const int word = stream_quantise((float)D(1), (float)D(2), clipped);
+            printf("%u %u\n", (unsigned)word, clipped);
         } else {
             fprintf(stderr, "test_fe_plan: bad line: %s", line);
             fclose(f);

@@ -1,8 +1,8 @@
 """The front end's host-side planning (csrc/dpe_fe_plan.h) without a GPU: host/test_fe_plan.cpp, built with the host compiler,
 checks the tile geometry's properties itself (every output of a call has exactly one owner, the staged tile covers what its outputs
 read, every index stays inside the LDS allocation and the exact range of the division, at the extreme D and T too) and evaluates
-the mappings -- phase increment, phase word, needed range, geometry, owner, modulated taps, refusals -- for the cases written here,
-which are held to Python integers and to numpy exactly."""
+the mappings -- phase increment, phase word, needed range, geometry, owner, modulated taps, refusals, the int16 output word -- for the
+cases written here, which are held to Python integers and to numpy exactly."""
 import os
 import shutil
 import subprocess
@@ -39,6 +39,14 @@ def _table(D, T, mode):
     for t in range(T):
         tab[t % D, t // D] = ((t + 1, 0, 0, 0), (t + 1, t + 1, 0, 0), (t + 1, 0, 0, t + 1))[mode]
     return tab.ravel()
+
+
+def _quant(re, im):
+    """The int16 I/Q word of an fp32 pair and the components clipped: rounded half to even in fp32, clipped to the rails, I in the low
+    half of the little-endian word."""
+    r = np.rint(np.array([re, im], dtype=np.float32))
+    q = np.clip(r, -32768.0, 32767.0)
+    return "%d %d" % (q.astype("<i2").view("<u4")[0], np.count_nonzero(q != r))
 
 
 def _cases():
@@ -93,6 +101,14 @@ def _cases():
                       ("conv %d 64 513 %d 14000 -1 %d 1 0 0" % (FMT["I8C"], 2 ** 61 - 13056, 2 ** 55 - 1), "ok"),
                       ("conv %d 64 513 %d 14000 -1 %d 1 0 0" % (FMT["I8C"], 2 ** 61 - 13056, 2 ** 55), "first output 36028797018963968 with 1 outputs outside 0..2^55")):
         out.append((line, pat))
+    # ties, the signed zero, either side of both rails (32767.5 rounds to 32768 and clips, -32768.5 to -32768 and does not), far
+    # outside, both components clipped
+    pairs = [(0.5, 1.5), (2.5, -0.5), (-1.5, -0.0), (-0.0, 0.0), (32767.49, 32767.5), (32768.0, 32767.0), (-32768.5, -32769.0), (-32768.0, -32768.49),
+             (1e9, -1e9), (-1e9, 12345.0), (40000.0, -40000.0), (32767.5, -32769.0), (-1.0, 1.0), (-32767.5, 32766.5)]
+    pairs += [tuple(v) for v in (rng.integers(-2 ** 17, 2 ** 17, (12, 2)) / 4.0).tolist()]
+    for re, im in pairs:
+        re, im = float(np.float32(re)), float(np.float32(im))
+        out.append(("quant %s %s" % (h(re), h(im)), _quant(re, im)))
     return out
 
 
