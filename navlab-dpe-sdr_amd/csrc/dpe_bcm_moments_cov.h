@@ -8,13 +8,7 @@
 #pragma once
 #include <cmath>
 
-#ifndef DPE_HD
-#ifdef __HIPCC__
-#define DPE_HD __host__ __device__
-#else
-#define DPE_HD
-#endif
-#endif
+#include "dpe_consts.h"   // DPE_HD
 
 namespace dpe {
 

@@ -23,7 +23,7 @@
 #include "dpe_common.h"
 #include "dpe_bcs_plan.h"   // the launch plan and its constants (kSub, kSumSlots, kPass, ...): plain C++
 #include "dpe_prep.h"
-#include "dpe_chm_dev.h"   // chm_k2: the device-resident channel manager's time update, carried as an extra block (FUSE form)
+#include "dpe_chm_k2.h"    // chm_k2 / chm_k3: the device-resident channel manager's time update, carried as extra blocks (FUSE form)
 #include "dpe_bcs_pieces.h"   // what the forms of stage 1 share: cmul, wipe_seed, phases, BcsParamBlock, window_mean, replica / store pieces
 
 namespace dpe {

@@ -4,13 +4,14 @@
 // launches: dpe_cd.hip passes sizes in, its kernels read the same constants, and host/test_cd_plan.cpp holds predictions and plans
 // to tests/test_cd_plan_cpu.py's numpy values and table with a host compiler.  DESIGN.md 7g.
 //
-// The Kepler / SV-clock arithmetic is dpe_chm_dev.h's sat_state and rotate_state (through dpe_nav_dev.h, which takes the arithmetic
-// without the kernels); nothing of it is restated.
+// The Kepler / SV-clock arithmetic is dpe_sat.h's sat_state and rotate_state; nothing of it is restated.
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 
-#include "dpe_nav_dev.h"
+#include "../../include/dpe_hip.h"
+#include "dpe_sat.h"
 
 namespace dpe {
 

@@ -137,7 +137,7 @@ int dpe_chm_outputs(dpe_chanmgr *h, dpe_chan_start *start, dpe_chan_end *end, dp
 }  // extern "C"
 
 // ============================================================================================
-// Device-resident form (dpe_chm_dev_*): handle and entry points; the kernels are in dpe_chm_dev.h
+// Device-resident form (dpe_chm_dev_*): handle and entry points; the kernels are in dpe_chm_dev.h (chm_k1) and dpe_chm_k2.h (chm_k2, chm_k3)
 #ifdef __HIPCC__
 struct dpe_chm_dev {
     dpe::ChmDevState *st_d = nullptr;
@@ -434,7 +434,7 @@ int dpe_chm_dev_set_ekf(dpe_chm_dev *h, const dpe_ekf_config *cfg)
     memcpy(e[0].Pk1k1, cfg->P0, sizeof(e[0].Pk1k1));
     memcpy(e[0].xk1k1, cfg->x0, sizeof(e[0].xk1k1));
     memcpy(e[0].xkk1, cfg->x0, sizeof(e[0].xkk1));
-    e[0].coupled = cfg->coupleVelocity ? 1 : 0;                               // (the structure the device step exploits: dpe_chm_dev.h, ekf_dev_step)
+    e[0].coupled = cfg->coupleVelocity ? 1 : 0;                               // (the structure the device step exploits: dpe_ekf_dev.h, ekf_dev_step)
     e[0].Tc = cfg->sampleLength;
     (void)hipFree(h->ekf_d);
     h->ekf_d = dev_alloc<EkfDev>(1);

@@ -2,6 +2,13 @@
 // by the host-only headers that a plain C++ compiler builds (dpe_bcs_plan.h).
 #pragma once
 
+// host and device under hipcc, plain functions for a host compiler: the one definition every shared-arithmetic header uses
+#ifdef __HIPCC__
+#define DPE_HD __host__ __device__
+#else
+#define DPE_HD
+#endif
+
 namespace dpe {
 
 // cudarecv/utils/inc/consthelper.h:5-27 -- bit-for-bit

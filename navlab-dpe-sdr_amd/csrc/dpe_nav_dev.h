@@ -1,24 +1,15 @@
 // dpe_nav_dev.h -- the scalar navigation solution's arithmetic (pygnss/pythonreceiver/scalar/naveng.py:10-224 with
 // libgnss/utils.py:117-228), shared by its host form (dpe_nav_solve) and its device form (nav_solve_log_kernel), both in dpe_nav.hip.
-// Satellite clock correction and ECEF state are dpe_chm_dev.h's sat_state_t, which restates libgnss/satpos.py:8-185 operation for
+// Satellite clock correction and ECEF state are dpe_sat.h's sat_state_t, which restates libgnss/satpos.py:8-185 operation for
 // operation -- satellite_clock_correction at the transmit time, locate_satellite at transmit time - clock bias -- here with the
 // twin's remainder: np.mod takes the divisor's sign where the reference's fmod takes the dividend's, and since 2 x 3.1415926535898
 // is 1.4e-14 short of a period, an anomaly reduced the other way moves a satellite by 3.7e-7 m (measured against fixture O15: a
 // constant 1.2e-7 m in the fix).
 #pragma once
-#define DPE_CHM_ARITH_ONLY   // the channel manager's host / device arithmetic without its kernels
-#include "dpe_chm_dev.h"
+#include "../../include/dpe_hip.h"
+#include "dpe_sat.h"   // sat_state_t, ModFloor (np.mod)
 
 namespace dpe {
-
-struct ModFloor {   // np.mod
-    DPE_HD double operator()(double a, double m) const
-    {
-        double r = std::fmod(a, m);
-        if (r != 0.0 && ((r < 0.0) != (m < 0.0))) r += m;
-        return r;
-    }
-};
 
 struct NavChan {      // what a channel's decode (or the caller) supplies
     Eph eph;

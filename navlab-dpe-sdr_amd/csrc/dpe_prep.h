@@ -151,7 +151,7 @@ int dpe_bcs_hook_get(dpe_bcs *h, dpe_bcs_hook *out);
 typedef void (*dpe_owner_detach_fn)(void *owner, int which);
 int dpe_bcs_hook_set_owner(dpe_bcs *h, dpe_owner_detach_fn detach, void *owner);
 int dpe_bcm_hook_set_owner(dpe_bcm *h, dpe_owner_detach_fn detach, void *owner);
-// The device-resident channel manager's time update (chm_k2, dpe_chm_dev.h) as a task for this handle's next stage-1 launch:
+// The device-resident channel manager's time update (chm_k2, dpe_chm_k2.h) as a task for this handle's next stage-1 launch:
 // `args` = a dpe::ChmKArgs; the launch carries it as an extra block when its kernel form can (single-window bcs_bank_kernel),
 // otherwise -- and from dpe_bcs_cotask_flush -- it runs as a kernel of its own first.
 int dpe_bcs_cotask_set(dpe_bcs *h, const void *args, size_t bytes);

@@ -7,8 +7,8 @@
 // math library behind sincos / atan2 / sqrt.  Rows of the update are the included channels in channel order -- range rows, then rate
 // rows -- so the arithmetic does not depend on which lanes the channels occupy.
 #pragma once
-#define DPE_CHM_ARITH_ONLY   // the channel manager's host / device arithmetic without its kernels
-#include "dpe_chm_dev.h"
+#include "../../include/dpe_hip.h"
+#include "dpe_sat.h"   // Eph, sat_state, rotate_state, wrap_pos
 
 namespace dpe {
 

@@ -1,8 +1,7 @@
 // test_cd_plan.cpp -- csrc/dpe_cd_plan.h with a host C++ compiler, no GPU: the launch plan's properties are checked here (exit 1
 // with a message on the first that fails), and plans, predictions and refusals are evaluated for the cases of a text file, one answer
 // per line, for tests/test_cd_plan_cpu.py to hold against its table and against numpy.  Doubles travel as C99 hex floats.  (The
-// header takes the Kepler arithmetic from dpe_chm_dev.h, whose includes need the HIP headers on the include path -- nothing of the
-// runtime is called or linked.)
+// header and the orbit arithmetic it takes from dpe_sat.h are plain C++: no HIP header is on the include path.)
 //
 //   test_cd_plan cases.txt
 //     plan M K J P                                   -> run nRuns pitch useLds ldsBytes nJ blocksX pointsPerBlock
@@ -20,9 +19,6 @@
 
 #include "../csrc/dpe_cd_plan.h"
 
-namespace dpe {
-void set_error(const char *, ...) {}   // declared by dpe_common.h; nothing here reports through it
-}
 using namespace dpe;
 
 #define CHECK(cond, ...)                                   \

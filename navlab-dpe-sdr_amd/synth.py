@@ -192,7 +192,7 @@ def write_grid_csv(path, grid):
 
 
 def enu2ecef_matrix(p0):
-    """Row-major ENU -> ECEF rotation [3, 3] at the ECEF position p0: the arithmetic of csrc/dpe_chm_dev.h's enu2ecef_matrix
+    """Row-major ENU -> ECEF rotation [3, 3] at the ECEF position p0: the arithmetic of csrc/dpe_sat.h's enu2ecef_matrix
     (CHM_Dev_ECEF2LL_Rad + CHM_Dev_R_ENU2ECEF, cuchanmgr.cu:37-73) in numpy."""
     a, b, e, ep = 6378137.0, 6356752.314245, 0.08181919084262149, 0.08209443794969568
     x, y, z = (float(v) for v in np.asarray(p0, dtype=np.float64)[:3])

@@ -289,7 +289,7 @@ def merge_worst(acc, w):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# P_k|k-1 matrices that take the filter's LU inverse (dpe_ekf.hip::invert, dpe_chm_dev.h::ekf_lu_column) off the diagonal-pivot
+# P_k|k-1 matrices that take the filter's LU inverse (dpe_ekf.hip::invert, dpe_ekf_dev.h::ekf_lu_column) off the diagonal-pivot
 # path.  The filter forms S = P + I (H = I, R = I) -- exactly, for the entries used here.
 
 def lu_pivots(Smat):

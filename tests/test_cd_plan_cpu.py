@@ -38,19 +38,11 @@ def _cxx():
     return None
 
 
-def _hip_include():
-    for root in (os.environ.get("ROCM_PATH"), "/opt/rocm"):
-        if root and os.path.exists(os.path.join(root, "include", "hip", "hip_runtime.h")):
-            return os.path.join(root, "include")
-    return None
-
-
 def _build(tmp_path):
-    if _cxx() is None or _hip_include() is None:
-        pytest.skip("no host C++ compiler, or no HIP headers for csrc/dpe_common.h")
+    if _cxx() is None:
+        pytest.skip("no host C++ compiler")
     exe = str(tmp_path / "test_cd_plan")
-    subprocess.run([_cxx(), "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__", "-I" + _hip_include(), SRC,
-                    "-o", exe], check=True)
+    subprocess.run([_cxx(), "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", SRC, "-o", exe], check=True)
     return exe
 
 

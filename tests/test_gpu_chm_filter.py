@@ -1,4 +1,4 @@
-"""The filter inside the measurement kernel (ekf_dev_step / ekf_lu_column, csrc/dpe_chm_dev.h) against the host filter
+"""The filter inside the measurement kernel (ekf_dev_step / ekf_lu_column, csrc/dpe_ekf_dev.h) against the host filter
 (csrc/dpe_ekf.hip) with the LU inverse OFF the diagonal-pivot path.  P_k|k-1 starts as I in both forms and every run of the suite
 keeps S = P + I diagonally dominant, so p == C in every column of every window: the row-swap half of ekf_lu_column -- the shuffle
 sources, the pivot permutation, diagOld, ownOdd / ownEven, the unsigned-magnitude pivot search -- and the singular exit never ran.

@@ -1,4 +1,4 @@
-"""The device-resident channel manager (chm_k1 / chm_k2 / chm_k3, csrc/dpe_chm_dev.h) on the worlds of tests/chm_world.py -- week
+"""The device-resident channel manager (chm_k1, csrc/dpe_chm_dev.h; chm_k2 / chm_k3, csrc/dpe_chm_k2.h) on the worlds of tests/chm_world.py -- week
 crossovers, eccentric orbits, four other sites, a wide and even time grid, 37 channels, a Kepler failure, long runs at 1 and 5 ms --
 against the host form, port by port, at the bounds of tests/test_gpu_chm_dev.py (chm_world.compare; the one derived change: the
 satellite-state and fc bounds of an e = 0.3 channel times 1 / (1 - e)).  Then the attached loop replayed port by port by a host
